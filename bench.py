@@ -1,13 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- grid-point-steps/s of the HIP RK4 path on the BASELINE.json workload (FHN torus 8192^2, fp64).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one classical RK4 step of the whole grid on synthetic initial conditions made by the reference's own rule; the state
 is resident in HBM before the timed region; the grid is fixed as N grows (strong scaling); rank r owns phi-slab r of N; rank 0
 prints ONE JSON line.  Order of a run: set-up and halo self-check, launch-plan measurement (crd_plan_launches, or --launch-plan),
-rehearsals (N > 1), --preheat-ms of untimed stepping, W warm-up steps, K timed steps between two fences (MAX over ranks).
+rehearsals (N > 1), about --preheat-ms of untimed stepping, W warm-up steps, K timed steps between two fences (MAX over ranks).  The
+pre-heat's step count is fixed by the arguments (preheat_steps), so the timed steps start from the same state in every run with the
+same arguments, and --dump-outputs DIR writes what they computed: DIR/y.npy, rows of the final state in the layout Slab.download
+returns and the device precision (all rows when they fit in 32 MB, otherwise a fixed seeded sample of rows), and DIR/y_rows.npy,
+their global row indices.
+
+A plain run does only that.  --full adds the figures that take runs of their own: the staged stepper and the one-step-per-launch
+kernel beside a fused run, the K timed steps repeated (`timing_spread`), the per-rank diagnostic pass of ring runs and the CPU
+baseline.
 
 How N > 1 runs -- one state machine, whoever starts it:
 
@@ -59,13 +67,17 @@ def parse(argv=None):
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"])
     ap.add_argument("--stepper", default="auto", choices=["auto", "staged", "fused"])
     ap.add_argument("--dt", type=float, default=0.0, help="RK4 step; default 0.8 x the stability limit of the grid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: staged and one-step-per-launch legs, "
+                                                           "repeats, per-rank diagnostics of ring runs, CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the state the timed steps computed to DIR/y.npy (rows: DIR/y_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--t-boundary", type=float, default=0.0, help="tBoundary: > 0 keeps the absorbing rows on for the whole run (SURVEY 8d's extra run)")
-    ap.add_argument("--cpu-rows", type=int, default=4096, help="phi rows of the grid the CPU baseline integrates")
-    ap.add_argument("--cpu-steps", type=int, default=72, help="RK4 steps of the CPU baseline (about 12 s on 16 cores)")
+    ap.add_argument("--cpu-rows", type=int, default=4096, help="--full: phi rows of the grid the CPU baseline integrates")
+    ap.add_argument("--cpu-steps", type=int, default=72, help="--full: RK4 steps of the CPU baseline (about 12 s on 16 cores)")
     ap.add_argument("--force-rccl", action="store_true", help="world size 1 only: route the halos through an RCCL ring to self (rehearses the N>1 code path)")
     ap.add_argument("--halo-slack-threshold-ms", type=float, default=0.03, help="ring runs: exposed wait per exchange (max over ranks) above which the halo gets a third sweep of cover")
-    ap.add_argument("--preheat-ms", type=float, default=300.0, help="untimed stepping in front of the warm-up, so that a short timed region runs at the clocks a long run settles at")
+    ap.add_argument("--preheat-ms", type=float, default=300.0, help="untimed stepping in front of the warm-up, so that a short timed region runs at the clocks a long run settles at "
+                                                                     "(steps: this long at a nominal rate, preheat_steps)")
     ap.add_argument("--launch-plan", default="", metavar="MODE,MAPPING,COLUMNS[,NT[,STEPS]]", help="pin the step kernel's launch plan (crd_set_launch_plan) instead of measuring it")
     ap.add_argument("--transport", default="auto", choices=["auto", "rccl", "local"], help="N > 1: rccl = one rank process per GPU; local = one process, LOCAL group; auto = rccl, then local")
     ap.add_argument("--ring-timeout-s", type=float, default=150.0, help="a rank stops waiting for the RCCL ring's bring-up after this long (0 = wait for ever)")
@@ -74,9 +86,9 @@ def parse(argv=None):
     ap.add_argument("--devices", default="", help="--transport local: device ordinal of each slab, e.g. 0,0 to rehearse two slabs on one GPU (default 0..N-1)")
     ap.add_argument("--issuing-threads", type=int, default=0, help="--transport local: host threads issuing the group's work (0 = one per device)")
     ap.add_argument("--crd-module", default="crdmodel_amd", help=argparse.SUPPRESS)  # tests: a stand-in for the device API (tests/standin_crd.py)
-    ap.add_argument("--repeats", type=int, default=4, help="the K timed steps again, this many times, AFTER the timed region (spread of the figure; not part of `value`)")
-    ap.add_argument("--one-step-steps", type=int, default=40, help="steps of the one-step-per-launch kernel timed beside a two-step run (0 = skip)")
-    ap.add_argument("--staged-steps", type=int, default=40, help="steps of the staged stepper timed beside a fused run for the `staged` sub-record (0 = skip)")
+    ap.add_argument("--repeats", type=int, default=4, help="--full: the K timed steps again, this many times, AFTER the timed region (spread of the figure; not part of `value`)")
+    ap.add_argument("--one-step-steps", type=int, default=40, help="--full: steps of the one-step-per-launch kernel timed beside a two-step run (0 = skip)")
+    ap.add_argument("--staged-steps", type=int, default=40, help="--full: steps of the staged stepper timed beside a fused run for the `staged` sub-record (0 = skip)")
     ap.add_argument("--preflight", action="store_true", help="N ranks: roll call, RCCL ring bring-up, communicator self-report and the 32-row halo self-check ONLY; one JSON "
                                                              "line ({\"preflight\": true, \"ok\": ...}) within a minute -- why a multi-GPU run would fail, without running it")
     return ap.parse_args(argv)
@@ -106,6 +118,55 @@ def cpu_baseline(args, beta, dt):
             "sample": "%dx%d band of the %dx%d grid, %d RK4 steps, faithful per-point sin/cos RHS (oracle/crd_oracle.c), OpenMP over rows, %.1f s"
                       % (args.size, rows, args.size, args.size, args.cpu_steps, el),
             "value_1core": args.size * rows1 * steps1 / el1, "sample_1core": "%dx%d band, %d RK4 steps, one thread, %.1f s" % (args.size, rows1, steps1, el1)}
+
+
+# Grid-point-steps per ms of one MI355X (FHN, the tuned plan: profiles/r06) that size the pre-heat.  A step count set by the arguments rather
+# than by a clock keeps the state the timed steps start from -- and so what --dump-outputs writes -- the same from run to run.
+NOMINAL_POINT_STEPS_PER_MS = {"f64": 3.0e8, "f32": 6.0e8}
+
+
+def preheat_steps(args, world):
+    """Untimed steps in front of the warm-up: about --preheat-ms at the nominal rate of `world` GPUs sharing the grid, 8 .. 5000."""
+    if args.preheat_ms <= 0:
+        return 0
+    return int(min(5000, max(8, round(args.preheat_ms * NOMINAL_POINT_STEPS_PER_MS[args.precision] * world / (args.size * args.size)))))
+
+
+# ---- --dump-outputs ------------------------------------------------------------------------------------------------------------------
+DUMP_BYTES = 32 << 20  # state rows written at most (fp64 8192^2: 256 of the 8192 rows)
+DUMP_SEED = 20240607
+
+
+def dump_rows(ny, nx, itemsize):
+    """The global rows --dump-outputs writes: all of them when they fit in DUMP_BYTES, otherwise a fixed seeded sample, ascending."""
+    k = max(1, DUMP_BYTES // (2 * nx * itemsize))
+    if k >= ny:
+        return np.arange(ny)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ny, k, replace=False))
+
+
+def owned_rows(slab, rows):
+    """(the global rows of `rows` this slab owns, their state as (k, nx, 2) in the device precision), read off the device."""
+    mine = rows[(rows >= slab.js) & (rows <= slab.je)]
+    y = np.empty((len(mine), slab.nx, 2), dtype=slab.dtype)
+    i = 0
+    for run in np.split(mine, np.flatnonzero(np.diff(mine) != 1) + 1):  # one read per contiguous run of rows
+        if len(run):
+            for var in (0, 1):
+                y[i:i + len(run), :, var] = slab.download_rows(var, int(run[0]) - slab.js, len(run))
+            i += len(run)
+    return mine, y
+
+
+def write_outputs(directory, parts, ny):
+    """DIR/y.npy and DIR/y_rows.npy from every slab's owned_rows(); returns the line's `outputs` record."""
+    rows, y = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    order = np.argsort(rows, kind="stable")
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "y.npy"), y[order])
+    np.save(os.path.join(directory, "y_rows.npy"), rows[order].astype(np.float64))
+    return {"dir": directory, "files": ["y.npy", "y_rows.npy"], "rows": int(len(rows)), "of_rows": int(ny),
+            "sample": "all rows" if len(rows) == ny else "rows drawn by numpy default_rng(%d)" % DUMP_SEED}
 
 
 # ---- the launcher side of the state machine (module docstring) ---------------------------------------------------------------------
@@ -445,18 +506,16 @@ def run_local(args, crd, ndev, emit):
             s.plan_launches()
         if not args.exchange_period and all(s.launch_plan().get("steps_per_launch", 1) == 3 for s in grp.slabs):
             grp.set_exchange_period(9)  # (plans that step triples inside the cycles -- fp32 -- want a period they divide: see the ring's rehearsal)
-        preheat = {"ms_requested": args.preheat_ms, "steps": 0}
-        if args.preheat_ms > 0:
+        preheat = {"ms_requested": args.preheat_ms, "steps": preheat_steps(args, world)}
+        if preheat["steps"]:
             t0 = time.perf_counter()
-            grp.step_rk4(0.0, dt, 8)
-            est_ms = max((time.perf_counter() - t0) * 1e3 / 8, 0.01)
-            n_pre = int(min(5000, max(0, args.preheat_ms / est_ms)))
-            grp.step_rk4(0.0, dt, n_pre)
-            preheat.update({"steps": 8 + n_pre, "ms": (time.perf_counter() - t0) * 1e3})
+            grp.step_rk4(0.0, dt, preheat["steps"])
+            preheat["ms"] = (time.perf_counter() - t0) * 1e3
         grp.step_rk4(0.0, dt, args.warmup)  # (returns when every slab's last step is done)
         t0 = time.perf_counter()
         timings = grp.step_rk4_timed(args.warmup * dt, dt, args.steps)  # one dict per slab (crd_step_timing)
         elapsed = time.perf_counter() - t0
+        outputs = write_outputs(args.dump_outputs, [owned_rows(s, dump_rows(n, n, np.dtype(s.dtype).itemsize)) for s in grp.slabs], n) if args.dump_outputs else None
         peak = max(s.max_abs() for s in grp.slabs)
         if not (np.isfinite(peak) and peak <= 1e3):
             raise SystemExit("solution blew up (max|u| = %r): dt too large?" % peak)
@@ -475,9 +534,12 @@ def run_local(args, crd, ndev, emit):
         per_rank = [{"rank": k, "rows": s.nyl, "device": devices[k], "kernel_ms": timings[k]["kernel_ms"], "device_ms_per_step": timings[k]["ms_total"] / args.steps,
                      "launch_plan": s.launch_plan()} for k, s in enumerate(grp.slabs)]
         geometry = lead.launch_geometry() if fused and hasattr(lead, "launch_geometry") else None
-        emit(json.dumps(build_line(args, crd, world, dt, beta, elapsed, kernel=lead.dominant_kernel(), kernel_ms=kernel_ms, launches=1 if fused else 2, pts_launch=pts,
-                                   device_ms_per_step=max(t["ms_total"] for t in timings) / args.steps, plan=plan, comm=comm, preheat=preheat, staged=None, per_rank=per_rank,
-                                   kernel_ms_source=source, per_launch=per_launch, geometry=geometry)))
+        out = build_line(args, crd, world, dt, beta, elapsed, kernel=lead.dominant_kernel(), kernel_ms=kernel_ms, launches=1 if fused else 2, pts_launch=pts,
+                         device_ms_per_step=max(t["ms_total"] for t in timings) / args.steps, plan=plan, comm=comm, preheat=preheat, staged=None, per_rank=per_rank,
+                         kernel_ms_source=source, per_launch=per_launch, geometry=geometry)
+        if outputs:
+            out["outputs"] = outputs
+        emit(json.dumps(out))
     finally:
         grp.close()
 
@@ -574,10 +636,10 @@ def run(args, crd, world, rank, local_rank, device_sync, emit, t_start=None):
     y_init = crd.initial_conditions(cfg, slab.js, slab.je)
     slab.upload(y_init)
 
-    # Beside a fused run (N = 1): the staged stepper -- the scheme SURVEY 8(d)'s 256 B per grid-point-step describes -- in the same process.
+    # Beside a fused run (N = 1, --full): the staged stepper -- the scheme SURVEY 8(d)'s 256 B per grid-point-step describes -- in the same process.
     staged = None
     will_fuse = args.stepper != "staged" and slab.dominant_kernel().startswith("crd_rk4_fused")
-    if world == 1 and will_fuse and args.staged_steps > 0:
+    if args.full and world == 1 and will_fuse and args.staged_steps > 0:
         slab.set_stepper("staged")
         slab.step_rk4(0.0, dt, 4, sync=True)
         fence()
@@ -634,14 +696,11 @@ def run(args, crd, world, rank, local_rank, device_sync, emit, t_start=None):
 
     # Pre-heat (the same 20 steps measured 5 % slower behind 5 warm-up steps than behind 800: profiles/r03/warm_clocks.txt), warm-up, then
     # the timed region: barrier + device synchronisation, K steps, device synchronisation, time stamp, barrier; MAX over the ranks.
-    preheat = {"ms_requested": args.preheat_ms, "steps": 0}
-    if args.preheat_ms > 0:
+    preheat = {"ms_requested": args.preheat_ms, "steps": preheat_steps(args, world)}
+    if preheat["steps"]:
         t0 = time.perf_counter()
-        slab.step_rk4(0.0, dt, 8, sync=True)
-        est_ms = max((time.perf_counter() - t0) * 1e3 / 8, 0.01)
-        n_pre = int(min(5000, max(0, ctl.max_float(args.preheat_ms / est_ms))))
-        slab.step_rk4(0.0, dt, n_pre, sync=True)
-        preheat.update({"steps": 8 + n_pre, "ms": (time.perf_counter() - t0) * 1e3})
+        slab.step_rk4(0.0, dt, preheat["steps"], sync=True)
+        preheat["ms"] = (time.perf_counter() - t0) * 1e3
     slab.step_rk4(0.0, dt, args.warmup, sync=True)
     fence()
     t0 = time.perf_counter()
@@ -651,8 +710,12 @@ def run(args, crd, world, rank, local_rank, device_sync, emit, t_start=None):
     ctl.barrier()
     elapsed = ctl.max_float(elapsed_rank)
     timed = slab.step_timing()
-    spread = []  # the same K steps again, a few times, same fences: the spread of the figure on this box (never part of `value`)
-    for r in range(max(0, args.repeats)):
+    outputs = None
+    if args.dump_outputs:  # (before anything else steps the state)
+        parts = ctl.gather(owned_rows(slab, dump_rows(slab.grid.ny, slab.nx, np.dtype(slab.dtype).itemsize)))
+        outputs = write_outputs(args.dump_outputs, parts, slab.grid.ny) if rank == 0 else None
+    spread = []  # --full: the same K steps again, a few times, same fences: the spread of the figure on this box (never part of `value`)
+    for r in range(max(0, args.repeats) if args.full else 0):
         fence()
         t0 = time.perf_counter()
         slab.step_rk4((args.warmup + (r + 1) * args.steps) * dt, dt, args.steps, sync=True)
@@ -660,9 +723,9 @@ def run(args, crd, world, rank, local_rank, device_sync, emit, t_start=None):
         spread.append(ctl.max_float(time.perf_counter() - t0) * 1e3 / args.steps)
     plan_used = dict(slab.launch_plan(), measured_in_s=round(t_plan, 3))
     geometry = slab.launch_geometry() if will_fuse and hasattr(slab, "launch_geometry") else None
-    # Beside a two-steps-per-launch run (N = 1): the one-step-per-launch kernel, which crosses memory once per step, in this same process.
+    # Beside a two-steps-per-launch run (N = 1, --full): the one-step-per-launch kernel, which crosses memory once per step, in this same process.
     one_step = None
-    if world == 1 and will_fuse and plan_used.get("steps_per_launch", 1) >= 2 and not args.launch_plan and args.one_step_steps > 0:
+    if args.full and world == 1 and will_fuse and plan_used.get("steps_per_launch", 1) >= 2 and not args.launch_plan and args.one_step_steps > 0:
         slab.set_launch_plan(0, plan_used["xcd_mapping"], plan_used["columns_per_lane"], 1, 1)
         slab.step_rk4(0.0, dt, 8, sync=True)
         o_ms, o_kms, _ = slab.step_rk4_timed(0.0, dt, args.one_step_steps)
@@ -672,23 +735,25 @@ def run(args, crd, world, rank, local_rank, device_sync, emit, t_start=None):
     if blown:
         bail("solution blew up on %d rank(s) (this rank: max|u| = %r): dt too large?" % (blown, peak))
 
-    # Per-rank figures (ring runs): the timed region's own, then a short pass with per-exchange event pairs -- three cycles, outside the rate.
+    # Per-rank figures (ring runs): the timed region's own, then (--full) a short pass with per-exchange event pairs -- three cycles, outside the rate.
     per_rank = None
     if transport == "rccl":
         rec = {"rank": rank, "rows": slab.nyl, "kernel_ms": kernel_ms, "kernel_rows": slab.dominant_kernel_rows(), "ms_per_step": elapsed_rank * 1e3 / args.steps,
                "device_ms_per_step": ms_dev / args.steps, "launch_plan": slab.launch_plan()}
-        diag_steps = 3 * slab.exchange_period()
-        slab.set_diagnostics(True)
-        d_ms, _, _ = slab.step_rk4_timed((args.warmup + args.steps) * dt, dt, diag_steps)
-        tm = slab.step_timing()
-        slab.set_diagnostics(False)
-        rec.update({"diag_steps": diag_steps, "diag_ms_per_step": d_ms / diag_steps, "halo_waits": tm["halo_waits"], "exchanges": tm["exchanges"],
-                    "exposed_halo_ms": tm["exposed_halo_ms"] / max(1, tm["halo_waits"]), "exchange_ms": tm["exchange_ms"] / max(1, tm["exchanges"]),
-                    "halo_slack": tm["halo_slack"], "agreement_restarts": tm["agreement_restarts"]})
+        if args.full:
+            diag_steps = 3 * slab.exchange_period()
+            slab.set_diagnostics(True)
+            d_ms, _, _ = slab.step_rk4_timed((args.warmup + args.steps) * dt, dt, diag_steps)
+            tm = slab.step_timing()
+            slab.set_diagnostics(False)
+            rec.update({"diag_steps": diag_steps, "diag_ms_per_step": d_ms / diag_steps, "halo_waits": tm["halo_waits"], "exchanges": tm["exchanges"],
+                        "exposed_halo_ms": tm["exposed_halo_ms"] / max(1, tm["halo_waits"]), "exchange_ms": tm["exchange_ms"] / max(1, tm["exchanges"]),
+                        "halo_slack": tm["halo_slack"], "agreement_restarts": tm["agreement_restarts"]})
         per_rank = ctl.gather(rec)
-        # did RCCL see N ranks, and did the exchange hide?  At a glance, at the top level of config.halo:
-        comm["exposed_halo_ms_per_rank"] = [q["exposed_halo_ms"] for q in per_rank]
-        comm["exchange_ms_per_rank"] = [q["exchange_ms"] for q in per_rank]
+        if args.full:
+            # did RCCL see N ranks, and did the exchange hide?  At a glance, at the top level of config.halo:
+            comm["exposed_halo_ms_per_rank"] = [q["exposed_halo_ms"] for q in per_rank]
+            comm["exchange_ms_per_rank"] = [q["exchange_ms"] for q in per_rank]
 
     if rank == 0:
         out = build_line(args, crd, world, dt, beta, elapsed, kernel=slab.dominant_kernel(), kernel_ms=kernel_ms, launches=launches,
@@ -697,9 +762,12 @@ def run(args, crd, world, rank, local_rank, device_sync, emit, t_start=None):
                          kernel_ms_source="HIP events around sampled launches on the library's compute stream inside the timed region",
                          per_launch=timed.get("timed_steps_per_launch") or None, geometry=geometry)
         if per_rank:
-            out["per_rank_note"] = ("kernel_ms / ms_per_step / device_ms_per_step: each rank's own figures from the timed region; exposed_halo_ms: average time its compute "
-                                    "stream stood at the wait for a halo, per exchange, and exchange_ms: average duration of an exchange on the second stream -- both from a "
-                                    "%d-step diagnostic pass after the timed region" % per_rank[0].get("diag_steps", 0))
+            out["per_rank_note"] = "kernel_ms / ms_per_step / device_ms_per_step: each rank's own figures from the timed region"
+            if args.full:
+                out["per_rank_note"] += ("; exposed_halo_ms: average time its compute stream stood at the wait for a halo, per exchange, and exchange_ms: average "
+                                         "duration of an exchange on the second stream -- both from a %d-step diagnostic pass after the timed region" % per_rank[0]["diag_steps"])
+        if outputs:
+            out["outputs"] = outputs
         if one_step:
             o_rate = 4 * (8 if args.precision == "f64" else 4) * n * n / (one_step[1] * 1e-3) / 1e9
             out["roofline"]["one_step_per_launch"] = {"kernel_ms": one_step[1], "device_ms_per_step": one_step[0], "steps": args.one_step_steps, "achieved": o_rate,
@@ -708,7 +776,7 @@ def run(args, crd, world, rank, local_rank, device_sync, emit, t_start=None):
         if spread:
             out["timing_spread"] = {"repeats_ms_per_step": spread, "min": min(spread), "max": max(spread),
                                     "note": "the K timed steps repeated %d times after the timed region, same fences; `value` is the first, timed pass only" % len(spread)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, beta, dt)
         emit(json.dumps(out))
     slab.close()

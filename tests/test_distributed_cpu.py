@@ -209,7 +209,7 @@ def _bench_worker(rank, world, port, result_dir, exposed_rank, size):
 
     fake.exposed_ms_by_rank = {exposed_rank: 0.08} if exposed_rank >= 0 else {}
     lines = []
-    args = bench.parse(["--gpus", str(world), "--size", str(size), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"])
+    args = bench.parse(["--gpus", str(world), "--size", str(size), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"])
     try:
         bench.run(args, fake, world, rank, rank, lambda: None, lines.append)
     finally:
@@ -411,3 +411,70 @@ def test_preflight_says_within_a_minute_whether_a_multi_rank_run_would_come_up()
     assert [o[0] for o in outs] == [0, 0], outs
     d = json.loads(outs[0][1].strip().splitlines()[-1])
     assert d["preflight"] and d["ok"] and d["n_gpus"] == 2 and not outs[1][1].strip()
+
+
+def test_a_plain_bench_run_does_only_what_its_figure_needs(tmp_path, monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` -- bench.run against the stand-in: set-up, plan, pre-heat, W warm-up and K timed steps, the
+    line, and nothing else steps the state; --full adds the staged and one-step-per-launch legs, the repeats and the CPU baseline.  --dump-outputs
+    writes the state's rows in the device precision (the stand-in does not compute: the initial conditions)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from tests import standin_crd as fake
+
+    def run(*argv):
+        lines = []
+        args = bench.parse(["--size", "64", "--steps", "7", "--warmup", "3", "--preheat-ms", "0"] + list(argv))
+        bench.run(args, fake, 1, 0, 0, lambda: None, lines.append)
+        assert len(lines) == 1
+        return args, fake.created[-1], json.loads(lines[0])
+
+    monkeypatch.setenv("STANDIN_STEPS_PER_LAUNCH", "2")  # (a plan the one-step-per-launch leg of --full is timed beside)
+    for precision, dtype in (("f64", np.float64), ("f32", np.float32)):
+        out = tmp_path / precision
+        args, slab, d = run("--precision", precision, "--dump-outputs", str(out))
+        assert slab.steps == 3 + 7 and slab.last_timed == 7 and d["steps"] == 7 and d["warmup"] == 3 and d["dtype"] == precision
+        assert not {"cpu_baseline", "staged", "timing_spread"} & set(d) and "one_step_per_launch" not in d["roofline"]
+        y, rows = np.load(out / "y.npy"), np.load(out / "y_rows.npy")
+        assert y.dtype == dtype and rows.dtype == np.float64 and np.array_equal(rows, np.arange(64.0))
+        assert d["outputs"]["rows"] == 64 and d["outputs"]["sample"] == "all rows"
+        assert np.array_equal(y, fake.initial_conditions(bench.problem(args, fake)[3]).astype(dtype))
+    # the pre-heat: a step count set by the arguments (about --preheat-ms at a nominal rate), not by a clock
+    args, slab, d = run("--preheat-ms", "0.001")
+    assert d["config"]["preheat"]["steps"] == bench.preheat_steps(args, 1) == round(0.001 * 3e8 / 64 ** 2) and slab.steps == d["config"]["preheat"]["steps"] + 3 + 7
+    args, slab, d = run("--full", "--staged-steps", "4", "--one-step-steps", "5", "--repeats", "2", "--cpu-rows", "16", "--cpu-steps", "2")
+    assert slab.steps == 3 + 7 + (4 + 4) + 2 * 7 + (8 + 5) and "outputs" not in d
+    assert d["staged"]["steps"] == 4 and len(d["timing_spread"]["repeats_ms_per_step"]) == 2 and d["roofline"]["one_step_per_launch"]["steps"] == 5
+    assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
+
+
+def test_the_dumped_sample_is_fixed_and_bounded():
+    """--dump-outputs on a grid too large to write whole: the same seeded rows every run, ascending, 32 MB of state at most."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    for itemsize in (8, 4):
+        rows = bench.dump_rows(8192, 8192, itemsize)
+        assert np.array_equal(rows, bench.dump_rows(8192, 8192, itemsize)) and np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 8192
+        assert len(rows) == (32 << 20) // (2 * 8192 * itemsize)
+    assert np.array_equal(bench.dump_rows(1024, 1024, 8), np.arange(1024))
+
+
+def test_every_leg_of_a_multi_slab_run_dumps_the_same_rows(tmp_path):
+    """--dump-outputs through the ring (rank processes, the rows gathered to rank 0), the LOCAL group and a single slab: the same
+    seeded sample of the whole grid's rows, each from the slab that owns it (stand-in: the initial conditions)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import crdmodel_amd as crd
+
+    size = 2560  # fp64: 819 of the 2560 rows, on both slabs
+    common = ["--size", str(size), "--steps", "6", "--warmup", "2", "--crd-module", "tests.standin_crd", "--preheat-ms", "0"]
+    y0 = crd.initial_conditions(bench.problem(bench.parse(common), crd)[3])
+    rows = bench.dump_rows(size, size, 8)
+    assert 0 < len(rows) < size and rows[0] < size // 2 <= rows[-1]
+    for name, leg in (("ring", ["--gpus", "2"]), ("local", ["--gpus", "2", "--transport", "local"]), ("single", ["--gpus", "1"])):
+        r = _run_bench(leg + common + ["--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, (name, r.stdout[-2000:], r.stderr[-4000:])
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["outputs"]["rows"] == len(rows) and d["outputs"]["of_rows"] == size, name
+        assert np.array_equal(np.load(tmp_path / name / "y_rows.npy"), rows.astype(np.float64)), name
+        assert np.array_equal(np.load(tmp_path / name / "y.npy"), y0[rows]), name

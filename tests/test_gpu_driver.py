@@ -377,7 +377,7 @@ def test_bench_line_end_to_end(gpu_device):
         assert len(lines) == 1, r.stdout[-2000:]
         return json.loads(lines[0])
 
-    d = run("--cpu-rows", "128", "--cpu-steps", "4", "--staged-steps", "4")
+    d = run("--full", "--cpu-rows", "128", "--cpu-steps", "4", "--staged-steps", "4")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
                 "roofline", "cpu_baseline"):
         assert key in d, key
@@ -396,7 +396,7 @@ def test_bench_line_end_to_end(gpu_device):
     assert d["config"]["preheat"]["steps"] >= 8 and d["staged"]["kernel"].startswith("crd_rk4_stage_kernel") and 0.0 < d["staged"]["frac"] <= 1.0
     assert d["config"]["launch_plan"]["tuned"] == 1  # 1024^2 = 1 Mi points: the smallest launch the library measures a plan for
 
-    d = run("--no-cpu-baseline", "--staged-steps", "0", "--force-rccl", "--launch-plan", "0,1,2,1")
+    d = run("--full", "--no-cpu-baseline", "--staged-steps", "0", "--force-rccl", "--launch-plan", "0,1,2,1")
     lp = d["config"]["launch_plan"]
     assert lp["pinned"] and (lp["one_round"], lp["xcd_mapping"], lp["columns_per_lane"], lp["nontemporal_stores"]) == (0, 1, 2, 1) and "cpu_baseline" not in d
     halo = d["config"]["halo"]
@@ -408,3 +408,33 @@ def test_bench_line_end_to_end(gpu_device):
     d = run("--no-cpu-baseline", "--stepper", "staged")
     assert d["roofline"]["kernel"].startswith("crd_rk4_stage_kernel") and d["roofline"]["launches_per_step"] == 2 and "staged" not in d  # (stages 2 and 3 are the launches of the dominant kernel)
     assert d["roofline"]["algorithmic_bytes_per_launch"] == 80 * 1024 * 1024
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_state_its_timed_steps_computed(gpu_device, tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the line has no figure of the --full legs, and DIR holds the state after the pre-heat,
+    the W warm-up and the K timed steps from the initial conditions -- the CPU oracle's RK4 trajectory --, the same bits in a second run
+    with the same arguments (the pre-heat's step count is set by them, not by a clock)."""
+    import json
+    import sys
+
+    import bench
+
+    argv = ["--size", "1024", "--steps", "8", "--warmup", "2", "--preheat-ms", "0.25"]
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads(r.stdout)
+        assert d["steps"] == 8 and not {"cpu_baseline", "staged", "timing_spread"} & set(d) and "one_step_per_launch" not in d["roofline"]
+        assert d["outputs"]["rows"] == 1024 and sorted(os.listdir(out)) == ["y.npy", "y_rows.npy"]
+        assert np.array_equal(np.load(out / "y_rows.npy"), np.arange(1024.0))
+        dumps.append(np.load(out / "y.npy"))
+    assert dumps[0].shape == (1024, 1024, 2) and dumps[0].dtype == np.float64 and np.array_equal(dumps[0], dumps[1])
+    args = bench.parse(argv)
+    steps = bench.preheat_steps(args, 1) + 2 + 8
+    assert d["config"]["preheat"]["steps"] == steps - 10 > 8
+    beta, params, dt, cfg = bench.problem(args, crd)
+    op = co.make_problem(co.FHN, co.TORUS, 1024, 80.0, 20.0, 0.12, beta, ny=1024)
+    assert rel_err(dumps[0], co.rk4(op, crd.initial_conditions(cfg), 0.0, dt, steps, nthreads=8)) <= 1e-9
