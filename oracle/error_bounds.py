@@ -1,0 +1,257 @@
+"""Per-point rounding-error bounds for the HIP right-hand side and one RK4 step.  TEST INFRASTRUCTURE ONLY.
+
+Only tests/ may import this module.  It states, point by point and field by field, how far a correct kernel in a given
+precision may land from a high-precision reference, so that a mistake that is large where it happens fails even when it is
+small next to the largest term on the grid (the joint max-norm gate of tests/conftest.py: rel_err).
+
+Reference
+---------
+fp64 kernels: oracle/crd_oracle_np.py in np.longdouble (64-bit significand; refused, not skipped, where the platform's long
+double is narrower).  fp32 kernels: the same restatement in float64, evaluated on the fp32 state widened exactly, so that
+rounding the input is never counted as kernel error.  The reference's own error (2^-64 or 2^-53 of the same terms) is at
+most 1/2048 of the bound and ignored.
+
+Right-hand side
+---------------
+With u the unit roundoff of the kernel's precision (2^-53 or 2^-24), every point's result is a short chain of products
+and sums.  The standard model fl(a op b) = (a op b)(1 + d), |d| <= u, bounds the error of ANY evaluation order of a sum of
+terms t_i, fused or not, by (n - 1) u sum |t_i| + O(u^2): each rounding is relative to a partial sum, and every partial
+sum is at most sum |t_i|.  So
+
+    |f_kernel - f_ref| <= K u S + rho |w|       per point and per field,
+
+where S sums the absolute values of every term and product the point function combines:
+
+    S_u = |cE gE| + |cWn gW| + |cP| (|uN| + 2|uC| + |uS|) + kinetics_u
+          FHN        kinetics_u = |v| + 3|u| + |u|^3,            S_v = eps (|u| + |b|)
+          Goldbeter  kinetics_u = |v2| + |v3| + kf |v| + k |u| + |v0 + v1 b|,   S_v = |v2| + |v3| + kf |v|
+          diffusion only: S_v = 0 (dv is exactly zero)
+
+with gE = uE - uC, gW = uC - uW (the theta differences are exact or correct to half an ulp of u, so the theta part is
+charged against the differences; the phi second difference is formed from values and charged against the values), and
+cE, cWn, cP the host's fp64 coefficient tables (crdmodel_amd/csrc/crd_host.cpp: build_coefficients).  The two Hill terms
+v2 and v3 are taken separately because they cancel in w = v2 - v3.  Rounding a table (cE, cWn, cP, the row parameter
+eps b or v0 + v1 b) to the device precision is one more relative u on a term already in S.
+
+The Goldbeter reciprocal (hardware estimate + one Newton step, crd_device.h: reciprocal) is not correctly rounded.  Its
+relative error rho multiplies the quotient w and is charged as its own term, rho |w|, so a change to the reciprocal (or
+to CRD_RCP_NEWTON) moves this bound rather than hiding inside K.
+
+Absorbing rows while t < tBoundary, dv of diffusion-only Goldbeter, and a uniform field's diffusion are exact zeros: the
+bound there is 0 and any nonzero result fails.
+
+One RK4 step
+------------
+Stages Y1 = y0, Y2 = y0 + dt/2 k1, Y3 = y0 + dt/2 k2, Y4 = y0 + dt k3 at times t, t + dt/2, t + dt/2, t + dt (the oracle's).
+With dY_s the bound on the stage input's error, the stage derivative's error is
+
+    e_s = K u S(Y_s) + rho |w(Y_s)| + |J(Y_s)| dY_s
+
+where |J| is the absolute Jacobian of f as a 5-point stencil: |cE| on the east neighbour, |cWn| on the west, |cP| on north
+and south, |cWn - cE - 2 cP + dg/du| on the centre, |dg/dv| on v; and |dh/du|, |dh/dv| for the v equation (kinetic partials
+analytic).  Stage inputs are one fused multiply-add with a rounded coefficient c dt:
+
+    dY_{s+1} = c dt e_s + 2 u (|y0| + c dt |k_s|)
+
+and the step's result, formed from y0 and the four k_s in any order (running accumulators on the device, the reference's
+y0 + dt/6 (k1 + 2 k2 + 2 k3 + k4) on the host):
+
+    bound = dt/6 (e1 + 2 e2 + 2 e3 + e4) + K_ACC u (|y0| + dt/6 sum w_s |k_s|).
+
+A stage at a time before tBoundary has exact zeros on the absorbing rows: e_s = 0 there.  The bound is evaluated at the
+reference's stage values; the kernel's differ by dY_s, which moves S and |J| by O(u) of themselves (second order).
+"""
+import numpy as np
+
+from oracle import crd_oracle as co
+from oracle import crd_oracle_np as cn
+
+UNIT = {"f64": 2.0 ** -53, "f32": 2.0 ** -24}  # unit roundoff of the kernel's precision (round to nearest)
+# K: FHN's longest chain sums 7 terms (u: east, west, three phi values, v, kinetics), 6 roundings, plus one for a table or row
+# parameter rounded to the device precision: 7, and 8 leaves one spare.  Goldbeter's u chain is longer (Hill quotients several
+# roundings deep), so there K is empirical: the host's fp32 restatements reach 0.37 (kernel order) and 0.78 (reference order) of it.
+K = 8.0
+# K_ACC: the reference's order rounds 6 times on the way to y (three sums of k, the rounded dt/6, its product, + y0); the
+# device's running sums 5 times (four fused multiply-adds, a rounded coefficient); 8 leaves two spare.
+K_ACC = 8.0
+# rho: relative error of the Goldbeter reciprocal.  fp64: v_rcp_f64 (2^-24.4) + one Newton step, 2.2e-15 as measured over
+# [2.6, 1e6] (crd_device.h: reciprocal; relative, so the range's scale does not matter).  fp32: the estimate's error squared
+# (2^-46) plus the refined value's rounding and the residual's, 3 u.
+RHO = {"f64": 2.2e-15, "f32": 3.0 * 2.0 ** -24}
+KF, KK, V0, V1, VM2, VM3, K2, KR, KA, EPS = 1.0, 10.0, 1.0, 7.3, 65.0, 500.0, 1.0, 2.0, 0.9, cn.EPSILON
+
+
+def reference_dtype(precision):
+    if precision == "f64":
+        assert np.finfo(np.longdouble).nmant >= 63, (
+            "the fp64 kernels' reference needs an 80-bit (or wider) np.longdouble; this platform's has %d mantissa bits"
+            % np.finfo(np.longdouble).nmant)
+        return np.longdouble
+    assert precision == "f32", precision
+    return np.float64
+
+
+class _Problem:
+    """The oracle Problem's whole-grid description in the numpy restatement's terms, plus the fp64 coefficient tables."""
+
+    def __init__(self, p):
+        self.model = {co.FHN: "fhn", co.GOLDBETER: "goldbeter"}[p.model]
+        self.surface = {co.TORUS: "torus", co.FLAT: "flat"}[p.surface]
+        self.g = dict(nx=p.nx, ny=p.ny, dx=p.dx, dy=p.dy, xmin=p.xmin, xmax=p.xmax, ymin=p.ymin, ymax=p.ymax, R=p.R, r=p.r)
+        self.D = p.diff
+        self.kw = dict(beta=p.beta, vary_beta=p.vary_beta, beta_min=p.beta_min, beta_max=p.beta_max, t_boundary=p.t_boundary,
+                       just_diffusion=p.just_diffusion)
+        self.diffusion_only = self.model == "goldbeter" and p.just_diffusion != 0
+        D, dx, dy = p.diff, p.dx, p.dy
+        if self.surface == "torus":  # the host's tables, as crd_host.cpp: build_coefficients forms them
+            theta = p.xmin + np.arange(p.nx, dtype=np.float64) * dx
+            rho = p.R + p.r * np.cos(theta)
+            cX = D * (1 / (p.r * p.r)) / (dx * dx)
+            cA = D * (-np.sin(theta) / (p.r * rho)) / (2 * dx)
+            cP = D * (1 / (rho * rho)) / (dy * dy)
+        else:
+            cX = D / dx / dx
+            cA = np.zeros(p.nx)
+            cP = np.full(p.nx, D / dy / dy)
+        self.cE, self.cWn, self.cP = cX + cA, cA - cX, cP
+
+    def rhs(self, t, u, v, dtype, j0):
+        return cn.rhs(self.model, self.surface, self.g, self.D, t, u, v, dtype=dtype, j0=j0, **self.kw)
+
+    def zero_rows(self, t, rows, j0):
+        """Rows (of a band starting at global row j0) whose derivative is exactly zero at time t."""
+        if self.diffusion_only or not t < self.kw["t_boundary"]:
+            return np.zeros(rows, dtype=bool)
+        return np.isin((j0 + np.arange(rows)) % self.g["ny"], (0, self.g["ny"] - 1))
+
+    def terms(self, u, v, j0):
+        """(S_u, S_v, |w|, centre, dg/dv, dh/du, dh/dv) per point, in float64, at the state (u, v) of a band from row j0."""
+        u, v = np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64)
+        uW, uE = np.roll(u, 1, axis=1), np.roll(u, -1, axis=1)
+        uS, uN = np.roll(u, 1, axis=0), np.roll(u, -1, axis=0)
+        cE, cWn, cP = self.cE[None, :], self.cWn[None, :], self.cP[None, :]
+        S_u = np.abs(cE * (uE - u)) + np.abs(cWn * (u - uW)) + np.abs(cP) * (np.abs(uN) + 2 * np.abs(u) + np.abs(uS))
+        centre_lin = cWn - cE - 2 * cP
+        zero = np.zeros_like(u)
+        if self.diffusion_only:
+            return S_u, zero, zero, np.abs(centre_lin + zero), zero, zero, zero
+        b = cn.beta_rows(self.g, self.kw["beta"], self.kw["vary_beta"], self.kw["beta_min"], self.kw["beta_max"], np.float64, j0,
+                         u.shape[0])[:, None]
+        if self.model == "fhn":
+            S_u = S_u + np.abs(v) + 3 * np.abs(u) + np.abs(u) ** 3
+            S_v = EPS * (np.abs(u) + np.abs(b))
+            gu, gv, hu, hv = 3 - 3 * u * u, -1.0 + zero, EPS + zero, zero
+            w = zero
+        else:
+            z2, y2 = u * u, v * v
+            z4 = z2 * z2
+            ka4 = KA ** 4
+            v2 = VM2 * z2 / (K2 * K2 + z2)
+            v3 = VM3 * y2 * z4 / ((KR * KR + y2) * (ka4 + z4))
+            hill = np.abs(v2) + np.abs(v3) + KF * np.abs(v)
+            S_u = S_u + hill + KK * np.abs(u) + np.abs(V0 + V1 * b)
+            S_v = hill
+            w_z = VM2 * 2 * u * K2 * K2 / (K2 * K2 + z2) ** 2 - VM3 * y2 / (KR * KR + y2) * 4 * u * z2 * ka4 / (ka4 + z4) ** 2
+            w_y = -VM3 * z4 / (ka4 + z4) * 2 * v * KR * KR / (KR * KR + y2) ** 2
+            gu, gv, hu, hv = -w_z - KK, -w_y + KF, w_z, w_y - KF
+            w = np.abs(v2 - v3)
+        return S_u, S_v, w, np.abs(centre_lin + gu), np.abs(gv), np.abs(hu), np.abs(hv)
+
+    def stage_error(self, precision, t, u, v, j0, du=None, dv=None):
+        """Bounds (e_u, e_v) on the error of f at a state known to within (du, dv) per point (None: exact input)."""
+        S_u, S_v, w, centre, gv, hu, hv = self.terms(u, v, j0)
+        rcp = RHO[precision] * w
+        eu = K * UNIT[precision] * S_u + rcp
+        ev = K * UNIT[precision] * S_v + rcp
+        if du is not None:
+            cE, cWn, cP = np.abs(self.cE)[None, :], np.abs(self.cWn)[None, :], np.abs(self.cP)[None, :]
+            eu = eu + (cE * np.roll(du, -1, axis=1) + cWn * np.roll(du, 1, axis=1) + cP * (np.roll(du, -1, axis=0) + np.roll(du, 1, axis=0))
+                       + centre * du + gv * dv)
+            ev = ev + hu * du + hv * dv
+        zero = self.zero_rows(t, u.shape[0], j0)
+        eu[zero] = 0.0
+        ev[zero] = 0.0
+        return eu, ev
+
+
+def _split(y, dtype):
+    y = np.asarray(y)
+    assert y.ndim == 3 and y.shape[2] == 2, y.shape
+    return y[..., 0].astype(dtype), y[..., 1].astype(dtype)
+
+
+def rhs_bound(problem, t, y, precision, j0=0):
+    """(ref, bound_u, bound_v) for f(t, y) of a kernel in `precision` ("f64" / "f32").  problem: the whole grid's oracle Problem
+    (co.make_problem); y: (rows, nx, 2), the whole grid or a band of whole rows starting at global row j0 (a band's first and
+    last rows wrap inside the band and are not meaningful).  ref has the reference's dtype (np.longdouble for f64)."""
+    P = _Problem(problem)
+    rd = reference_dtype(precision)
+    u, v = _split(y, rd)
+    fu, fv = P.rhs(t, u, v, rd, j0)
+    bu, bv = P.stage_error(precision, t, u, v, j0)
+    return np.stack([fu, fv], axis=-1), bu, bv
+
+
+def rk4_step_bound(problem, t, dt, y, precision, j0=0):
+    """(ref, bound_u, bound_v) for one classical RK4 step of size dt from (t, y), as rhs_bound (a band's first and last 4 rows
+    are not meaningful)."""
+    P = _Problem(problem)
+    rd = reference_dtype(precision)
+    un = UNIT[precision]
+    y0u, y0v = _split(y, rd)
+    a0u, a0v = np.abs(y0u.astype(np.float64)), np.abs(y0v.astype(np.float64))
+    h = rd(dt)
+    cs, ws = (0.0, 0.5, 0.5, 1.0), (1.0, 2.0, 2.0, 1.0)
+    Yu, Yv, du, dv = y0u, y0v, None, None
+    ks, es = [], []
+    for s in range(4):
+        ts = t + cs[s] * float(dt)
+        ku, kv = P.rhs(ts, Yu, Yv, rd, j0)
+        eu, ev = P.stage_error(precision, ts, Yu, Yv, j0, du, dv)
+        ks.append((ku, kv))
+        es.append((eu, ev))
+        if s < 3:
+            c = cs[s + 1]
+            Yu, Yv = y0u + (rd(c) * h) * ku, y0v + (rd(c) * h) * kv  # the oracle's stage inputs (crd_oracle_np.rk4)
+            du = c * float(dt) * eu + 2 * un * (a0u + c * float(dt) * np.abs(ku.astype(np.float64)))
+            dv = c * float(dt) * ev + 2 * un * (a0v + c * float(dt) * np.abs(kv.astype(np.float64)))
+    (k1u, k1v), (k2u, k2v), (k3u, k3v), (k4u, k4v) = ks
+    ref = np.stack([y0u + (h / 6) * (k1u + 2 * k2u + 2 * k3u + k4u), y0v + (h / 6) * (k1v + 2 * k2v + 2 * k3v + k4v)], axis=-1)
+    h6 = float(dt) / 6.0
+    bounds = []
+    for f, a0 in ((0, a0u), (1, a0v)):
+        prop = h6 * sum(w * e[f] for w, e in zip(ws, es))
+        size = a0 + h6 * sum(w * np.abs(k[f].astype(np.float64)) for w, k in zip(ws, ks))
+        bounds.append(prop + K_ACC * un * size)
+    return ref, bounds[0], bounds[1]
+
+
+def worst(got, ref, bound_u, bound_v, rows=None, j0=0):
+    """{"u": (ratio, row, column), "v": ...}: the largest err / bound per field (inf where a zero bound is missed, or where a
+    result is not finite), with its grid row (j0 + band row) and column.  rows: a slice of the band to judge (default all)."""
+    rows = slice(None) if rows is None else rows
+    start = rows.start or 0
+    out = {}
+    for f, name, b in ((0, "u", bound_u), (1, "v", bound_v)):
+        g = np.asarray(got)[rows, :, f]
+        err = np.abs(g.astype(ref.dtype) - ref[rows, :, f]).astype(np.float64)
+        bb = np.asarray(b, dtype=np.float64)[rows]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(err == 0.0, 0.0, err / bb)
+        r[~np.isfinite(g)] = np.inf
+        r = np.nan_to_num(r, nan=np.inf, posinf=np.inf)
+        j, i = np.unravel_index(int(np.argmax(r)), r.shape)
+        out[name] = (float(r[j, i]), j0 + start + int(j), int(i))
+    return out
+
+
+def describe(case, w):
+    return "%s: worst err/bound u %.3g at (row %d, col %d), v %.3g at (row %d, col %d)" % ((case,) + w["u"] + w["v"])
+
+
+def check(case, got, bounded, rows=None, j0=0):
+    """Assert got is inside the bound everywhere (bounded = rhs_bound / rk4_step_bound's result); returns worst()."""
+    ref, bu, bv = bounded
+    w = worst(got, ref, bu, bv, rows, j0)
+    assert w["u"][0] <= 1.0 and w["v"][0] <= 1.0, describe(case, w)
+    return w
