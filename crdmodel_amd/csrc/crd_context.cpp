@@ -29,18 +29,20 @@ int set_device(crd_ctx *c)
 	return CRD_OK;
 }
 
-// Upload a host double table converted to the device precision.
-int upload_table(crd_ctx *c, const std::vector<double> &src, void **dst)
+// Upload a host double table converted to the device precision (*dst: a new allocation, also when the copy fails).
+hipError_t upload_reals(int precision, const std::vector<double> &src, void **dst)
 {
 	const size_t n = src.size();
-	HIP_TRY(c, hipMalloc(dst, std::max<size_t>(n, 1) * c->real_size));
-	if (c->p.precision == CRD_PRECISION_F64) {
-		HIP_TRY(c, hipMemcpy(*dst, src.data(), n * sizeof(double), hipMemcpyHostToDevice));
-	} else {
-		std::vector<float> f(n);
-		for (size_t i = 0; i < n; i++) f[i] = (float)src[i];
-		HIP_TRY(c, hipMemcpy(*dst, f.data(), n * sizeof(float), hipMemcpyHostToDevice));
-	}
+	if (hipError_t e = hipMalloc(dst, std::max<size_t>(n, 1) * (precision == CRD_PRECISION_F64 ? 8 : 4)); e != hipSuccess) return e;
+	if (precision == CRD_PRECISION_F64) return hipMemcpy(*dst, src.data(), n * sizeof(double), hipMemcpyHostToDevice);
+	std::vector<float> f(n);
+	for (size_t i = 0; i < n; i++) f[i] = (float)src[i];
+	return hipMemcpy(*dst, f.data(), n * sizeof(float), hipMemcpyHostToDevice);
+}
+
+int upload_table(crd_ctx *c, const std::vector<double> &src, void **dst)
+{
+	HIP_TRY(c, upload_reals(c->p.precision, src, dst));
 	return CRD_OK;
 }
 
@@ -242,13 +244,8 @@ int crd_create_block(const crd_params *p, int c0, int d0, int c1, int d1, int de
 #undef CREATE_TRY
 
 	Coefficients co;
-	build_coefficients(c->p, c->g, &co);
 	std::vector<double> brow;
-	build_beta_rows(c->p, c->g, c->js - kGhost, c->je + 1 + kGhost, &brow);
-	if (p->model == CRD_MODEL_GOLDBETER)  // the kernels take the row-constant source term v0 + v1 b(j) of src/GoldbeterModel_torus.cpp:715 ready-made
-		for (double &b : brow) b = std::fma(kGbV1, b, kGbV0);
-	else  // FHN: EPSILON b(j), the addend of dv = fma(EPSILON, u, EPSILON b) (src/FHNmodel_torus.cpp:660)
-		for (double &b : brow) b = kFhnEpsilon * b;
+	build_step_tables(c->p, c->g, c->js - kGhost, c->je + 1 + kGhost, &co, &brow);
 	if (d0 > 1) {  // the block's own columns of the per-column tables
 		co.cE = std::vector<double>(co.cE.begin() + c->is, co.cE.begin() + c->ie + 1);
 		co.cWn = std::vector<double>(co.cWn.begin() + c->is, co.cWn.begin() + c->ie + 1);

@@ -225,6 +225,7 @@ int fail(crd_ctx *c, int code, const std::string &msg);  // records msg (thread-
 		if (r_ != ncclSuccess) return fail((ctx), CRD_ERCCL, std::string(#expr) + ": " + g_rccl.GetErrorString(r_)); \
 	} while (0)
 int set_device(crd_ctx *c);
+hipError_t upload_reals(int precision, const std::vector<double> &src, void **dst);  // host doubles -> a new device table in that precision
 int upload_table(crd_ctx *c, const std::vector<double> &src, void **dst);  // host doubles -> device precision
 int ensure_staging(crd_ctx *c, size_t bytes);                              // AoS staging of the *_host entry points
 int alloc_plane(crd_ctx *c, int k, int f);                                 // one field plane of state k, zeroed

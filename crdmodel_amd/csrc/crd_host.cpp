@@ -82,6 +82,16 @@ void build_beta_rows(const crd_params &p, const crd_grid &g, int64_t j0, int64_t
 	}
 }
 
+void build_step_tables(const crd_params &p, const crd_grid &g, int64_t j0, int64_t j1, Coefficients *co, std::vector<double> *brow)
+{
+	build_coefficients(p, g, co);
+	build_beta_rows(p, g, j0, j1, brow);
+	if (p.model == CRD_MODEL_GOLDBETER)  // the kernels take the row-constant source term v0 + v1 b(j) of src/GoldbeterModel_torus.cpp:715 ready-made
+		for (double &b : *brow) b = std::fma(kGbV1, b, kGbV0);
+	else  // FHN: EPSILON b(j), the addend of dv = fma(EPSILON, u, EPSILON b) (src/FHNmodel_torus.cpp:660)
+		for (double &b : *brow) b = kFhnEpsilon * b;
+}
+
 }  // namespace crd
 
 using namespace crd;

@@ -52,6 +52,11 @@ void build_coefficients(const crd_params &p, const crd_grid &g, Coefficients *ou
 // b(j) of src/FHNmodel_torus.cpp:623-632 for global rows [j0, j1).
 void build_beta_rows(const crd_params &p, const crd_grid &g, int64_t j0, int64_t j1, std::vector<double> *out);
 
+// Everything the step kernels read about a problem besides its state: the coefficient tables and the kinetics' row parameter of rows
+// [j0, j1) as the kernels take it (FHN EPSILON b(j); Goldbeter v0 + v1 b(j)).  crd_create (a slab's rows and ghost rows), crd_ensemble_create
+// (each member's).
+void build_step_tables(const crd_params &p, const crd_grid &g, int64_t j0, int64_t j1, Coefficients *co, std::vector<double> *brow);
+
 bool validate_params(const crd_params &p, std::string *why);
 
 // crd_trace.cpp: roctx ranges (no-ops unless a profiler listens)

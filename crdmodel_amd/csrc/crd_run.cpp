@@ -11,9 +11,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <filesystem>
 #include <iostream>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "crd.h"
@@ -37,6 +39,8 @@ struct Options {
 	int d0 = 0, d1 = 0;  // --decomp d0xd1: the reference's 2-D block layout (theta x phi) instead of phi-slabs; "--decomp mpi" = MPI_Dims_create(gpus)
 	bool block_contexts = false;  // --block-contexts: also COMPUTE on those blocks (staged kernels); default: files in that layout, computed on phi-slabs
 	bool decomp_mpi = false;
+	// --ensemble KEY=v1,v2,...: members that differ in one or more parameters, zipped over the lists (run_ensemble)
+	std::vector<std::pair<std::string, std::vector<double>>> ensemble;
 };
 
 [[noreturn]] void usage(const char *argv0, bool alias)
@@ -47,7 +51,7 @@ struct Options {
 		std::cerr << "Usage: " << argv0
 		          << " --model fhn|goldbeter --surface torus|flat [--gpus G] [--devices D] [--dt DT] [--stepper auto|staged|fused]\n"
 		             "       [--precision 64|32] [--adaptive|--adaptive-rk43|--fixed] [--binary|--binary-only] [--ref-steady-state] [--decomp D0xD1|mpi [--block-contexts]]\n"
-		             "       [--outdir DIR] [--quiet]\n"
+		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary=V1,V2,... (repeatable)]\n"
 		             "       <Config file path>\n";
 	}
 	std::exit(EXIT_FAILURE);
@@ -60,6 +64,65 @@ bool preset_from_name(const std::string &base, Options *o)
 	if (base == "GoldbeterModel_torus") { o->model = CRD_MODEL_GOLDBETER; o->surface = CRD_SURFACE_TORUS; return true; }
 	if (base == "GoldbeterModel_flat") { o->model = CRD_MODEL_GOLDBETER; o->surface = CRD_SURFACE_FLAT; return true; }
 	return false;
+}
+
+// Keys --ensemble takes: the parameters members of one ensemble may differ in (crd_ensemble_create), by their ini names.
+double *ensemble_field(const std::string &key, crd_params *p)
+{
+	if (key == "beta") return &p->beta;
+	if (key == "betaMin") return &p->beta_min;
+	if (key == "betaMax") return &p->beta_max;
+	if (key == "diffusion") return &p->diffusion;
+	if (key == "tBoundary") return &p->t_boundary;
+	return nullptr;
+}
+
+[[noreturn]] void usage_error(const std::string &msg)
+{
+	std::cerr << "\nCRD_ERROR: " << msg << "\n\n";
+	std::exit(EXIT_FAILURE);  // (the status of any bad option)
+}
+
+void parse_ensemble(const std::string &arg, Options *o)
+{
+	const size_t eq = arg.find('=');
+	const std::string key = arg.substr(0, eq);
+	crd_params probe{};
+	if (eq == std::string::npos || !ensemble_field(key, &probe))
+		usage_error("--ensemble takes KEY=V1,V2,... with KEY one of beta, betaMin, betaMax, diffusion, tBoundary (got '" + arg + "')");
+	std::vector<double> values;
+	size_t at = eq + 1;
+	while (true) {
+		const size_t comma = arg.find(',', at);
+		const std::string v = arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+		char *end = nullptr;
+		const double x = std::strtod(v.c_str(), &end);
+		if (v.empty() || *end != '\0' || !std::isfinite(x)) usage_error("--ensemble " + key + ": '" + v + "' is not a number");
+		values.push_back(x);
+		if (comma == std::string::npos) break;
+		at = comma + 1;
+	}
+	for (const auto &kv : o->ensemble)
+		if (kv.first == key) usage_error("--ensemble " + key + " given twice");
+	o->ensemble.emplace_back(key, values);
+}
+
+// What --ensemble cannot be combined with, and lists of unequal length: refused before the ini is read or any device touched.
+void check_ensemble_options(const Options &o)
+{
+	if (o.ensemble.empty()) return;
+	if (o.adaptive == 1 || o.adaptive == 2) usage_error("--ensemble steps fixed-step RK4 only: not with --adaptive / --adaptive-rk43");
+	if (o.gpus > 1) usage_error("--ensemble runs on one GPU: not with --gpus " + std::to_string(o.gpus));
+	if (o.d0 > 0 || o.decomp_mpi) usage_error("--ensemble members are single slabs: not with --decomp");
+	if (o.block_contexts) usage_error("--ensemble members are single slabs: not with --block-contexts");
+	if (o.binary) usage_error("--ensemble writes the text files only: not with --binary / --binary-only");
+	const size_t n = o.ensemble[0].second.size();
+	for (const auto &kv : o.ensemble)
+		if (kv.second.size() != n) {
+			std::string lens;
+			for (const auto &x : o.ensemble) lens += (lens.empty() ? "" : ", ") + x.first + " has " + std::to_string(x.second.size());
+			usage_error("--ensemble lists differ in length (" + lens + "): they are zipped into members");
+		}
 }
 
 void banner(const crd_run_config &cfg, const crd_grid &g, int n_slabs, int64_t nxl0, int64_t nyl0, double s0, double s1, double dt, int64_t steps_per_output)
@@ -122,6 +185,126 @@ int die(const char *what, int rc, crd_ctx *ctx)
 
 }  // namespace
 
+// --ensemble: the run of the ini once per member, the members' parameters zipped from the lists, all stepped together on one GPU
+// (crd_ensemble_*).  Member k writes the reference's files of a single-rank run into <outdir>/member_<k>/, from its own initial
+// conditions; all members take one step size: the ini's / --dt's, else the smallest member's dtSafety x crd_stable_dt.  A member whose
+// state goes non-finite is written no further from that output on, as a lone run stops there; the others run to tFinal, and the run
+// then exits 1 naming it.
+int run_ensemble(const Options &o, crd_run_config cfg)
+{
+	if (cfg.adaptive) usage_error("--ensemble steps fixed-step RK4 only: the ini asks for [Solver] adaptive (pass --fixed)");
+	if (cfg.n_gpus > 1) usage_error("--ensemble runs on one GPU: the ini asks for [Solver] gpus = " + std::to_string(cfg.n_gpus) + " (pass --gpus 1)");
+	const int B = (int)o.ensemble[0].second.size();
+	std::vector<crd_run_config> mc((size_t)B, cfg);
+	std::vector<crd_params> mp((size_t)B);
+	for (int k = 0; k < B; k++) {
+		for (const auto &kv : o.ensemble) *ensemble_field(kv.first, &mc[(size_t)k].params) = kv.second[(size_t)k];
+		mp[(size_t)k] = mc[(size_t)k].params;
+	}
+	const int Nt = cfg.output_timestep;
+	const double dTout = cfg.t_final / Nt;
+	double dt_cap = cfg.dt;
+	int dt_member = -1;
+	if (!(dt_cap > 0))
+		for (int k = 0; k < B; k++) {
+			const double c = cfg.dt_safety * crd_stable_dt(&mp[(size_t)k]);
+			if (dt_member < 0 || c < dt_cap) dt_cap = c, dt_member = k;
+		}
+	const int64_t steps_per_output = (int64_t)std::ceil(dTout / dt_cap - 1e-12);
+	const double dt = dTout / (double)steps_per_output;
+
+	crd_ensemble *ens = nullptr;
+	int rc = crd_ensemble_create(mp.data(), B, 0, &ens);
+	if (rc != CRD_OK) {
+		std::cerr << "\nCRD_ERROR: crd_ensemble_create failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(nullptr) << "\n\n";
+		return 1;
+	}
+	crd_grid g;
+	crd_ensemble_info(ens, nullptr, &g);
+	if (!o.quiet) {
+		std::cout << "\nEnsemble of " << B << " members on one GPU (" << (mp[0].model == CRD_MODEL_FHN ? "FHN" : "Goldbeter") << ", "
+		          << (mp[0].surface == CRD_SURFACE_TORUS ? "torus" : "flat surface") << ", nx = " << g.nx << ", ny = " << g.ny << "):\n";
+		for (int k = 0; k < B; k++) {
+			std::cout << "   member " << k << ":";
+			for (const auto &kv : o.ensemble) std::cout << " " << kv.first << " = " << kv.second[(size_t)k];
+			std::cout << "  -> " << o.outdir << "/member_" << k << "\n";
+		}
+		std::cout << "   Tfinal = " << cfg.t_final << ", output timesteps = " << Nt << "\n";
+		std::cout << "   integrator = classical RK4 on GPU, dt = " << dt << " (" << steps_per_output << " steps per output; "
+		          << (dt_member < 0 ? std::string("from [Solver] dt / --dt") : "the smallest member's dtSafety x stable dt: member " + std::to_string(dt_member)) << ")\n";
+	}
+
+	std::vector<crd_writer *> wr((size_t)B, nullptr);
+	std::vector<double> buf((size_t)(2 * g.nx * g.ny));
+	auto cleanup = [&]() {
+		for (auto *w : wr) crd_writer_close(w);
+		crd_ensemble_destroy(ens);
+	};
+	for (int k = 0; k < B; k++) {
+		const std::string dir = o.outdir + "/member_" + std::to_string(k);
+		std::error_code ec;
+		std::filesystem::create_directories(dir, ec);
+		if ((rc = crd_initial_conditions(&mc[(size_t)k], 0, g.ny - 1, buf.data())) != CRD_OK) {
+			die("crd_initial_conditions", rc, nullptr);
+			cleanup();
+			return 1;
+		}
+		if ((rc = crd_writer_open(&mc[(size_t)k], dir.c_str(), 0, 1, &wr[(size_t)k])) != CRD_OK || (rc = crd_writer_write_row(wr[(size_t)k], buf.data())) != CRD_OK) {
+			die("crd_writer", rc, nullptr);
+			cleanup();
+			return 1;
+		}
+		if ((rc = crd_ensemble_upload(ens, k, buf.data(), 1)) != CRD_OK) {
+			std::cerr << "\nCRD_ERROR: crd_ensemble_upload failed: " << crd_ensemble_last_error(ens) << "\n\n";
+			cleanup();
+			return 1;
+		}
+	}
+
+	std::vector<int> blown_at((size_t)B, 0);  // output (1-based) at which a member went non-finite; 0: never
+	std::vector<double> peak((size_t)B);
+	double stepping_s = 0.0;
+	for (int iout = 0; iout < Nt; iout++) {
+		const double t = iout * dTout;
+		const auto step_t0 = std::chrono::steady_clock::now();
+		rc = crd_ensemble_step_rk4(ens, t, dt, steps_per_output);
+		if (rc == CRD_OK) rc = crd_ensemble_synchronize(ens);
+		stepping_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - step_t0).count();
+		if (rc == CRD_OK) rc = crd_ensemble_max_abs(ens, peak.data());
+		for (int k = 0; k < B && rc == CRD_OK; k++) {
+			if (blown_at[(size_t)k]) continue;
+			if (!std::isfinite(peak[(size_t)k])) {
+				blown_at[(size_t)k] = iout + 1;
+				std::cerr << "\nSolver failure, stopping integration of member " << k << " (non-finite state at output " << iout + 1 << ")\n";  // src/FHNmodel_torus.cpp:433
+				continue;
+			}
+			if ((rc = crd_ensemble_download(ens, k, buf.data(), 1)) == CRD_OK) rc = crd_writer_write_row(wr[(size_t)k], buf.data());
+		}
+		if (rc != CRD_OK) {
+			std::cerr << "\nCRD_ERROR: ensemble stepping / output failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(ens) << "\n\n";
+			cleanup();
+			return 1;
+		}
+		if (!o.quiet) {
+			std::printf("%s   %3d %%", iout > 0 ? "\r" : "", 100 * (iout + 1) / Nt);
+			std::fflush(stdout);
+		}
+	}
+	int status = 0;
+	for (int k = 0; k < B; k++)
+		if (blown_at[(size_t)k]) {
+			std::cerr << "member " << k << " blew up at output " << blown_at[(size_t)k] << " of " << Nt << "; its files stop there\n";
+			status = 1;
+		}
+	if (!o.quiet && stepping_s > 0.0) {
+		const double ps = (double)B * (double)g.nx * (double)g.ny * (double)steps_per_output * Nt / stepping_s;
+		std::printf("\n   rate: %d members x %lld steps in %.6f s of stepping = %.4g grid-point-steps/s\n", B, (long long)steps_per_output * Nt, stepping_s, ps);
+		std::cout << "   ----------------------\n";
+	}
+	cleanup();
+	return status;
+}
+
 // Rank and size an MPI launcher gave this process through its environment (no MPI library is linked).
 struct Launcher {
 	int rank = 0, size = 1;
@@ -183,6 +366,7 @@ int main(int argc, char *argv[])
 			else if (s == "--binary-only") o.binary = o.binary_only = true;
 			else if (s == "--ref-steady-state") o.ref_steady_state = true;
 			else if (s == "--block-contexts") o.block_contexts = true;
+			else if (s == "--ensemble") parse_ensemble(next(), &o);
 			else if (s == "--decomp") {
 				const std::string v = next();
 				if (v == "mpi") o.decomp_mpi = true;
@@ -199,6 +383,7 @@ int main(int argc, char *argv[])
 			else usage(argv[0], false);
 		}
 		if (o.model < 0 || o.surface < 0 || o.ini.empty() || o.precision == -2 || o.stepper == -2) usage(argv[0], false);
+		check_ensemble_options(o);
 	}
 
 	// Started by an MPI launcher the way the reference is (`mpirun -np N <exe> <ini>`, util/ShellScripts/run*.sh)?  This
@@ -227,6 +412,7 @@ int main(int argc, char *argv[])
 	if (o.precision >= 0) cfg.params.precision = o.precision;
 	if (o.adaptive >= 0) cfg.adaptive = o.adaptive;
 	if (o.ref_steady_state) cfg.steady_state_decimals = 8;  // numpy's print precision, util/GoldbeterModel/SolveGoldbeterODE.py:111
+	if (!o.ensemble.empty()) return run_ensemble(o, cfg);
 	time_t start_t = 0, end_t = 0;
 	double total_t = 0, eta = 0;
 	time(&start_t);

@@ -359,6 +359,92 @@ class Slab:
         self._check(lib().crd_halo_exchange(self._h, depth), "crd_halo_exchange")
 
 
+class Ensemble:
+    """B independent single-slab problems on one GPU, stepped by one launch per RK4 step (crd_ensemble).  params_list: one Params per
+    member; members share model, surface, nx, ny, surface length / width, precision and justDiffusion, and may differ in diffusion,
+    beta, betaMin, betaMax, varyBeta and tBoundary.  Each member's result is bit-identical to a Slab of the same params stepped alone."""
+
+    def __init__(self, params_list, device=0):
+        self._h = C.c_void_p()
+        self.params = list(params_list)
+        arr = (Params * max(len(self.params), 1))(*self.params)
+        rc = lib().crd_ensemble_create(arr, len(self.params), device, C.byref(self._h))
+        if rc != capi.OK:
+            self._h = None
+            raise CrdError(rc, "crd_ensemble_create", lib().crd_ensemble_last_error(None).decode())
+        n, g = C.c_int(), Grid()
+        self._check(lib().crd_ensemble_info(self._h, C.byref(n), C.byref(g)), "crd_ensemble_info")
+        self.n_members, self.grid = n.value, g
+        self.nx, self.ny = g.nx, g.ny
+        self.dtype = np.float64 if self.params[0].precision == PRECISION_F64 else np.float32
+
+    def __len__(self):
+        return self.n_members
+
+    # -- lifecycle ---------------------------------------------------------------------------------------------
+    def close(self):
+        if self._h:
+            lib().crd_ensemble_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _check(self, rc, where):
+        if rc != capi.OK:
+            raise CrdError(rc, where, lib().crd_ensemble_last_error(self._h).decode())
+
+    # -- state -------------------------------------------------------------------------------------------------
+    def upload(self, member, y):
+        y = np.ascontiguousarray(y)
+        assert y.shape == (self.ny, self.nx, 2), (y.shape, (self.ny, self.nx, 2))
+        if y.dtype == np.float64:
+            self._check(lib().crd_ensemble_upload(self._h, member, y.ctypes.data, 1), "crd_ensemble_upload")
+        elif y.dtype == np.float32 and self.dtype == np.float32:
+            self._check(lib().crd_ensemble_upload(self._h, member, y.ctypes.data, 0), "crd_ensemble_upload")
+        else:
+            raise TypeError("state must be float64, or float32 for an f32 ensemble")
+
+    def download(self, member, dtype=np.float64):
+        y = np.empty((self.ny, self.nx, 2), dtype=dtype)
+        self._check(lib().crd_ensemble_download(self._h, member, y.ctypes.data, 1 if y.dtype == np.float64 else 0), "crd_ensemble_download")
+        return y
+
+    # -- time stepping -----------------------------------------------------------------------------------------
+    def step_rk4(self, t0, dt, nsteps, sync=True):
+        self._check(lib().crd_ensemble_step_rk4(self._h, t0, dt, nsteps), "crd_ensemble_step_rk4")
+        if sync:
+            self.synchronize()
+
+    def step_rk4_timed(self, t0, dt, nsteps):
+        """Device time of the batch in ms (blocks until done)."""
+        ms = C.c_double()
+        self._check(lib().crd_ensemble_step_rk4_timed(self._h, t0, dt, nsteps, C.byref(ms)), "crd_ensemble_step_rk4_timed")
+        return ms.value
+
+    def synchronize(self):
+        self._check(lib().crd_ensemble_synchronize(self._h), "crd_ensemble_synchronize")
+
+    def max_abs(self):
+        """max |var0| per member (a list; non-finite for a member that blew up)."""
+        v = (C.c_double * self.n_members)()
+        self._check(lib().crd_ensemble_max_abs(self._h, v), "crd_ensemble_max_abs")
+        return list(v)
+
+
 class PinnedArray:
     """A numpy array over page-locked host memory from crd_host_alloc (freed with the object)."""
 

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define CRD_ABI_VERSION 6
+#define CRD_ABI_VERSION 7
 
 typedef enum crd_status {
 	CRD_OK = 0,
@@ -511,6 +511,41 @@ void crd_trace_range_pop(void);
 
 /* max |var0| over the slab (blow-up guard; synchronises). */
 int crd_state_max_abs(crd_ctx *ctx, double *out);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Ensembles: B independent single-slab problems stepped together, one launch per RK4 step for all of them -- what a parameter
+ * scan of the reference does with B separate runs (`mpirun ... FHNmodel_torus <ini>` once per value, src/FHNmodel_torus.cpp:148-497),
+ * each with its own ARKode stepping loop.  On the reference's own small grids (data/FHNmodelArgs.ini: 400 x 1600) one problem's step
+ * is bound by the launch, not by the device; B members share that launch.  Members must agree on model, surface, nx, the derived ny,
+ * surface length and width, precision and justDiffusion; they may differ in diffusion, beta, betaMin, betaMax, varyBeta and
+ * tBoundary.  Fixed-step classical RK4 only, on one device; every member's result is bit-identical to a context (crd_create) of the
+ * same parameters stepped alone with crd_step_rk4 and the one-launch stepper.  Not thread-safe; calls on one ensemble must be
+ * serialised.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct crd_ensemble crd_ensemble;
+/* members[0 .. n_members): the members' parameters.  Refusals come before any HIP call: CRD_EINVAL for n_members < 1, invalid
+ * parameters or members that disagree where they must agree (crd_ensemble_last_error(NULL) names the first such member and field);
+ * CRD_EHIP without a device.  Each member owns two state buffers of its own (no ghost rows, none of a context's other planes); the
+ * state starts at zero.  Replaces InitUserData + SetupDecomp of B single-rank runs (src/FHNmodel_torus.cpp:708-772). */
+int crd_ensemble_create(const crd_params *members, int n_members, int device, crd_ensemble **out);
+void crd_ensemble_destroy(crd_ensemble *e);
+const char *crd_ensemble_last_error(const crd_ensemble *e); /* never NULL; e may be NULL (creation errors) */
+/* Member count and the members' common grid.  Either pointer may be NULL. */
+int crd_ensemble_info(const crd_ensemble *e, int *n_members, crd_grid *g);
+/* State of ONE member in the boundary layout (AoS, ny * nx pairs; host_is_f64 as crd_state_upload).  Synchronous; other members'
+ * states are not touched.  Stands in for the initial-condition upload of that member's run (src/FHNmodel_torus.cpp:285-354). */
+int crd_ensemble_upload(crd_ensemble *e, int member, const void *y_aos_host, int host_is_f64);
+int crd_ensemble_download(crd_ensemble *e, int member, void *y_aos_host, int host_is_f64);
+/* nsteps classical RK4 steps of size dt on EVERY member, stage k of step n at t0 + n dt + c_k dt (the same times crd_step_rk4 forms);
+ * each member's absorbing rows follow its own tBoundary.  One launch per step.  Asynchronous on the ensemble's own stream
+ * (crd_ensemble_synchronize waits).  Replaces the members' ARKode(...) calls (src/FHNmodel_torus.cpp:423), one per member. */
+int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps);
+/* ... bracketed by events on the ensemble's stream; blocks until done; ms_total: device time of the batch. */
+int crd_ensemble_step_rk4_timed(crd_ensemble *e, double t0, double dt, int64_t nsteps, double *ms_total);
+int crd_ensemble_synchronize(crd_ensemble *e);
+/* max |var0| of every member, per_member[0 .. n_members) (non-finite for a member that blew up; synchronises).  The blow-up guard of
+ * each member's run (its ARKode call's failure, src/FHNmodel_torus.cpp:424-435). */
+int crd_ensemble_max_abs(crd_ensemble *e, double *per_member);
 
 #ifdef __cplusplus
 }

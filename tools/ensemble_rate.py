@@ -1,0 +1,125 @@
+"""Aggregate rate of an ensemble against the same members stepped one after another as single contexts ("Ensembles").
+
+The shipped FHN 400 x 1600 and Goldbeter 100 x 400 grids in fp64, B in {1, 4, 16, 64} members that differ in beta: (a) one Ensemble,
+one launch per step for all members; (b) B Slabs, each with its measured launch plan, stepped one after another (each call
+asynchronous, one synchronisation at the end).  Both device-synchronised, warmed up, with enough steps for a window of at least
+--window seconds.  Reports grid-point-steps/s and the fraction of the 8 TB/s roof at 32 B per grid-point-step (one read and one write
+of the fp64 state); `in_infinity_cache` says whether the members' two state buffers (2 x 16 B per point each) fit the 256 MiB cache.
+
+    python tools/ensemble_rate.py [--members 1,4,16,64] [--window 1.0] [--json OUT]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import crdmodel_amd as crd  # noqa: E402
+
+INI = os.path.join(ROOT, "tests", "golden", "ini")
+ROOF_BYTES_PER_S = 8.0e12
+INFINITY_CACHE = 256 * 2**20
+
+
+def members_of(case, n):
+    model = "fhn" if case == "fhn" else "goldbeter"
+    p = crd.load_ini(os.path.join(INI, "%s_shipped.ini" % case), model, "torus").params
+    lo, hi = (0.9, 1.3) if case == "fhn" else (0.3, 0.75)
+    out = []
+    for b in np.linspace(lo, hi, n):
+        q = crd._capi.Params.from_buffer_copy(p)
+        q.beta, q.t_boundary = float(b), 0.0
+        out.append(q)
+    return out
+
+
+def timed(fn, steps):
+    fn(steps)  # (the caller synchronises inside fn)
+    t = time.perf_counter()
+    fn(steps)
+    return time.perf_counter() - t
+
+
+def calibrate(fn, window):
+    steps = 16
+    while True:
+        s = timed(fn, steps)
+        if s >= window or steps >= 1 << 22:
+            return steps, s
+        steps = int(steps * max(2.0, 1.2 * window / max(s, 1e-6)))
+
+
+def measure(case, n, window, dt):
+    members = members_of(case, n)
+    g = crd.grid_of(members[0])
+    points = g.nx * g.ny
+    y0 = [crd.initial_conditions(crd.run_config(m)) for m in members]
+
+    with crd.Ensemble(members) as e:
+        for k, y in enumerate(y0):
+            e.upload(k, y)
+
+        def ens(steps):
+            e.step_rk4(0.0, dt, steps, sync=True)
+
+        ens(8)  # warm-up
+        steps_e, s_e = calibrate(ens, window)
+
+    slabs = [crd.Slab(m) for m in members]
+    try:
+        for s, y in zip(slabs, y0):
+            s.set_stepper("fused")
+            s.upload(y)
+            s.plan_launches()
+
+        def seq(steps):
+            for s in slabs:
+                s.step_rk4(0.0, dt, steps, sync=False)
+            for s in slabs:
+                s.synchronize()
+
+        seq(8)
+        steps_s, s_s = calibrate(seq, window)
+        plan = slabs[0].launch_plan()
+    finally:
+        for s in slabs:
+            s.close()
+    rate_e = n * points * steps_e / s_e
+    rate_s = n * points * steps_s / s_s
+    return {
+        "case": case, "grid": [g.nx, g.ny], "members": n, "ensemble_gpss": rate_e, "sequential_gpss": rate_s, "speedup": rate_e / rate_s,
+        "ensemble_us_per_step": 1e6 * s_e / steps_e, "sequential_us_per_member_step": 1e6 * s_s / steps_s / n,
+        "ensemble_roof_frac": rate_e * 32.0 / ROOF_BYTES_PER_S, "sequential_roof_frac": rate_s * 32.0 / ROOF_BYTES_PER_S,
+        "in_infinity_cache": n * 2 * 16 * points <= INFINITY_CACHE, "window_s": [s_e, s_s], "steps": [steps_e, steps_s],
+        "single_plan": {k: plan[k] for k in ("one_round", "xcd_mapping", "columns_per_lane", "nontemporal_stores", "steps_per_launch")},
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--members", default="1,4,16,64")
+    ap.add_argument("--cases", default="fhn,goldbeter")
+    ap.add_argument("--window", type=float, default=1.0)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    rows = []
+    for case in a.cases.split(","):
+        dt = 0.004 if case == "fhn" else 0.002  # (under both grids' RK4 stability bounds: 0.0052, 0.0069)
+        for n in [int(x) for x in a.members.split(",")]:
+            r = measure(case, n, a.window, dt)
+            rows.append(r)
+            print("%-9s %4dx%-4d B=%2d  ensemble %.3e gpss (%.1f us/step, %.3f of roof)  sequential %.3e gpss (%.1f us/member-step)  x%.2f  %s" % (
+                case, r["grid"][0], r["grid"][1], n, r["ensemble_gpss"], r["ensemble_us_per_step"], r["ensemble_roof_frac"], r["sequential_gpss"],
+                r["sequential_us_per_member_step"], r["speedup"], "in Infinity Cache" if r["in_infinity_cache"] else "beyond Infinity Cache"), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump({"device": "MI355X", "rows": rows}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
