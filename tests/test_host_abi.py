@@ -577,3 +577,42 @@ def test_multi_step_kernels_issue_their_stores_whatever_the_execution_mask():
     copied.insert(14, "\tv_mov_b64_e32 v[60:61], v[48:49]")  # a copy of a register with a read in flight, in front of the back edge
     hazards = kernel_regs.async_lds_read_hazards(copied)
     assert len(hazards) == 1 and hazards[0][1] in (48, 49)
+
+
+def test_kernel_lint_failure_leaves_no_table(tmp_path):
+    """tools/kernel_regs.py stops a build whose multi-step kernel breaks the vmcnt contract (see above) -- and it must do so before it
+    writes the kernel table: make links whatever .inc it finds, so a table left behind by a failed lint would put the violating kernel
+    into the next build without a word (the Makefile also deletes the target of a failed recipe: .DELETE_ON_ERROR)."""
+    import shutil
+    import subprocess
+    import sys
+
+    if not shutil.which("c++filt"):
+        pytest.skip("c++filt not installed (kernel_regs.py demangles with it)")
+    # a three-step FHN fp64 step kernel, as the assembler prints one, whose stores sit behind an execution-mask branch
+    name = "_ZN3crd12_GLOBAL__N_125crd_rk4_fused_step_kernelIdLi0ELb0ELi0ELi1ELb1ELi3EEEvNS_3dev4SlabIT_EENS0_9FusedArgsIS4_EE"
+    asm = tmp_path / "violating.s"
+    asm.write_text("\n".join([
+        name + ":",
+        ".LBB0_1:                                ; =>This Inner Loop Header: Depth=1",
+        "\tv_fma_f64 v[20:21], v[10:11], v[30:31], v[40:41]",
+        "\ts_and_saveexec_b64 s[6:7], vcc",
+        "\ts_cbranch_execz .LBB0_2",
+        "\tbuffer_store_dwordx2 v[0:1], v2, s[8:11], 0 offen nt",
+        ".LBB0_2:",
+        "\ts_or_b64 exec, exec, s[6:7]",
+        "\ts_waitcnt vmcnt(20)",
+        "\tds_read_b64 v[0:1], v3",
+        "\ts_cbranch_scc1 .LBB0_1",
+        "\ts_endpgm",
+        "\t; NumVgprs: 244",
+        "\t; NumSgprs: 106",
+        "\t; ScratchSize: 0",
+        "\t; Occupancy: 2",
+        "\t; LDSByteSize: 0",
+        ""]))
+    table, js = tmp_path / "crd_kernel_table.inc", tmp_path / "kernel_table.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), "--asm", str(asm), "--table", str(table), "--json", str(js)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "skipped on the execution mask" in r.stderr, (r.returncode, r.stderr)
+    assert not table.exists() and not js.exists()

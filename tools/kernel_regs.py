@@ -238,12 +238,6 @@ def main():
         kernels += parse(compile_to_asm(a.source, extra))
     for path in a.asm:
         kernels += parse(open(path).read())
-    print("%-64s %5s %5s %7s %4s %6s | loop: %5s %5s %5s %4s %6s | %s" % ("kernel", "VGPR", "SGPR", "scratch", "occ", "LDS", "VALU", "SALU", "VMEM", "LDS", "total",
-                                                                         "exec-skipped VMEM"))
-    for k in kernels:
-        lp = k["loop"]
-        print("%-64s %5d %5d %7d %4d %6d | %11d %5d %5d %4d %6d | %d" % (k["name"][:64], k["vgprs"], k["sgprs"], k["scratch"], k["occupancy"], k["lds"], lp["valu"], lp["salu"],
-                                                                          lp["vmem"], lp["lds"], lp["total"], k["exec_skipped_vmem"]) + (" | async LDS read hazards: %d" % k["async_lds_read_hazards"] if k["async_lds_read_hazards"] else ""))
     rows = []
     for k in kernels:
         m = STEP_KERNEL.search(k["name"])
@@ -253,6 +247,27 @@ def main():
                          "nt": int(nt == "true"), "steps": int(steps), "vgprs": k["vgprs"], "sgprs": k["sgprs"], "lds_bytes": k["lds"], "scratch_bytes": k["scratch"],
                          "wavefronts_per_simd": k["occupancy"], "loop": k["loop"], "exec_skipped_vmem": k["exec_skipped_vmem"],
                          "async_lds_read_hazards": k["async_lds_read_hazards"]})
+    # The vmcnt contract of the multi-step pipelines (exec_skipped_vmem above) and the edge reads' registers (async_lds_read_hazards): a build
+    # that breaks either does not go on -- checked before anything is written, so that no table of a violating build is left for the next
+    # `make` to link.
+    for r in rows:
+        if r["async_lds_read_hazards"]:
+            sys.stderr.write("kernel_regs.py: %s model %d absorb %d cols %d nt %d steps %d: %d register(s) with LDS reads in flight touched before the asm block that waits "
+                             "for them\n" % (r["precision"], r["model"], r["absorb"], r["cols"], r["nt"], r["steps"], r["async_lds_read_hazards"]))
+    if any(r["async_lds_read_hazards"] for r in rows):
+        sys.exit(4)
+    broken = [r for r in rows if r["steps"] >= 2 and r["exec_skipped_vmem"]]
+    for r in broken:
+        sys.stderr.write("kernel_regs.py: %s model %d absorb %d cols %d nt %d steps %d: %d vector-memory region(s) skipped on the execution mask -- the hand-counted "
+                         "s_waitcnt vmcnt of its ring reads no longer holds\n" % (r["precision"], r["model"], r["absorb"], r["cols"], r["nt"], r["steps"], r["exec_skipped_vmem"]))
+    if broken:
+        sys.exit(3)
+    print("%-64s %5s %5s %7s %4s %6s | loop: %5s %5s %5s %4s %6s | %s" % ("kernel", "VGPR", "SGPR", "scratch", "occ", "LDS", "VALU", "SALU", "VMEM", "LDS", "total",
+                                                                         "exec-skipped VMEM"))
+    for k in kernels:
+        lp = k["loop"]
+        print("%-64s %5d %5d %7d %4d %6d | %11d %5d %5d %4d %6d | %d" % (k["name"][:64], k["vgprs"], k["sgprs"], k["scratch"], k["occupancy"], k["lds"], lp["valu"], lp["salu"],
+                                                                          lp["vmem"], lp["lds"], lp["total"], k["exec_skipped_vmem"]) + (" | async LDS read hazards: %d" % k["async_lds_read_hazards"] if k["async_lds_read_hazards"] else ""))
     if a.table:
         with open(a.table, "w") as f:
             f.write("// generated by tools/kernel_regs.py from the assembly of this build's step kernels -- do not edit\n")
@@ -266,21 +281,6 @@ def main():
     if a.json:
         json.dump({"digest": table_digest(rows), "_comment": "step kernels of this build: registers, occupancy and the static instruction mix of the steady-state loop (one trip = the unrolled "
                                "pipeline iterations), from the code object's assembly (tools/kernel_regs.py)", "kernels": rows}, open(a.json, "w"), indent=1)
-
-
-    # The vmcnt contract of the multi-step pipelines (exec_skipped_vmem above): a build that breaks it does not go on.
-    for r in rows:
-        if r["async_lds_read_hazards"]:
-            sys.stderr.write("kernel_regs.py: %s model %d absorb %d cols %d nt %d steps %d: %d register(s) with LDS reads in flight touched before the asm block that waits "
-                             "for them\n" % (r["precision"], r["model"], r["absorb"], r["cols"], r["nt"], r["steps"], r["async_lds_read_hazards"]))
-    if any(r["async_lds_read_hazards"] for r in rows):
-        sys.exit(4)
-    broken = [r for r in rows if r["steps"] >= 2 and r["exec_skipped_vmem"]]
-    for r in broken:
-        sys.stderr.write("kernel_regs.py: %s model %d absorb %d cols %d nt %d steps %d: %d vector-memory region(s) skipped on the execution mask -- the hand-counted "
-                         "s_waitcnt vmcnt of its ring reads no longer holds\n" % (r["precision"], r["model"], r["absorb"], r["cols"], r["nt"], r["steps"], r["exec_skipped_vmem"]))
-    if broken:
-        sys.exit(3)
 
 
 if __name__ == "__main__":
