@@ -12,7 +12,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # CRD_LIBRARY points the binding at another build of the same ABI (tuning builds under tools/); default is the in-tree library.
 LIB_PATH = os.environ.get("CRD_LIBRARY") or os.path.join(_PKG, "libcrd.so")
 
-ABI_VERSION = 7  # CRD_ABI_VERSION of include/crd.h (tests/test_host_abi.py keeps the two in step)
+ABI_VERSION = 8  # CRD_ABI_VERSION of include/crd.h (tests/test_host_abi.py keeps the two in step)
 OK, EINVAL, ENOMEM, EHIP, ERCCL, EIO, EPARSE, ESTATE = 0, -1, -2, -3, -4, -5, -6, -7
 MODEL_FHN, MODEL_GOLDBETER = 0, 1
 SURFACE_TORUS, SURFACE_FLAT = 0, 1
@@ -199,6 +199,8 @@ _SIGNATURES = {
     "crd_ensemble_step_rk4_timed": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_double)]),
     "crd_ensemble_synchronize": (C.c_int, [_vp]),
     "crd_ensemble_max_abs": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "crd_ensemble_integrate_adaptive": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(AdaptiveOptions), C.POINTER(AdaptiveStats),
+                                                  C.POINTER(C.c_int32)]),
 }
 
 _lib = None

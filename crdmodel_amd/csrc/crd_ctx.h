@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "crd_arkode.h"
 #include "crd_internal.h"
 #include "crd_kernels.h"
 
@@ -148,15 +149,8 @@ struct crd_ctx {
 		double t_out = 0.0, t_n = 0.0, t_np1 = 0.0;
 	} dense;
 
-	// Memory of the ARKode-style controller (CRD_ADAPT_ARKODE) between calls, as ARKodeMem keeps it between ARKode() calls: valid
-	// while the resident state is the one the integrator left (`live`), dropped by whatever replaces that state.
-	struct {
-		bool live = false;
-		int64_t nst = 0;         // steps taken since the state was new
-		double tn = 0.0;         // time the integrator has reached
-		double h = 0.0, hprime = 0.0, eta = 1.0, etamax = 0.0;
-		double ehist[3] = {1.0, 1.0, 1.0};
-	} ark;
+	// Memory of the ARKode-style controller (CRD_ADAPT_ARKODE) between calls (crd_arkode.h).
+	crd::arkode::Memory ark;
 
 	// Multi-slab fused stepping: position in the deep-halo exchange cycle the resident state is at (steps taken since the ghost
 	// rows were last exchanged, 0 = just exchanged), or -1 when the ghost rows cannot be trusted (new state, another stepper,

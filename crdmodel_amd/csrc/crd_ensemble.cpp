@@ -1,12 +1,14 @@
 // crd_ensemble.cpp -- ensembles behind the C ABI (include/crd.h, crd_ensemble_*): B independent single-slab problems of one geometry,
 // stepped by one launch per RK4 step (crd_ensemble.hip).  Host code only.  A member owns its tables and two state buffers; the
 // members' descriptors sit in a device table the step kernel reads.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "crd_arkode.h"
 #include "crd_ctx.h"
 #include "crd_device.h"
 #include "crd_ensemble.h"
@@ -29,6 +31,25 @@ struct crd_ensemble {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	std::string err;
+
+	// Error-controlled integration (crd_ensemble_integrate_adaptive): allocated at the first such call, empty before.
+	struct Adaptive {
+		void *buf[5];             // the member's five state buffers: its two (EnsembleMember::u) and three for the dense output
+		void *role[5];            // buffer of each role Y, SA, SB, ACC, OUT, as a context's planes (crd_ctx); role[Y] is the state handed back
+		arkode::Memory ark;       // the controller's memory between calls (crd_ctx::ark)
+		struct {
+			bool pending = false;
+			double t_out = 0.0, t_n = 0.0, t_np1 = 0.0;
+		} dense;                  // crd_ctx::dense
+	};
+	std::vector<Adaptive> adapt;
+	EnsemblePlan aplan;                        // the attempt kernel's plan: fixed at the first adaptive call
+	double *partials = nullptr;                // n x member_items error partials
+	double *ydd_partials = nullptr;            // n x kEnsembleNormBlocks
+	double *sums_dev = nullptr, *sums_host = nullptr;  // n doubles each; sums_host page-locked
+	EnsembleAttempt *att_dev = nullptr, *att_host = nullptr;  // n entries each; att_host page-locked
+	EnsembleOp *ops_dev = nullptr, *ops_host = nullptr;  // kOpSets x n entries each; ops_host page-locked
+	static constexpr int kOpSets = 3;          // batched launches enqueued between two waits, each with an operand set of its own
 };
 
 namespace {
@@ -180,6 +201,8 @@ void crd_ensemble_destroy(crd_ensemble *e)
 	for (void *q : e->allocs) (void)hipFree(q);
 	if (e->table) (void)hipFree(e->table);
 	if (e->max_host) (void)hipHostFree(e->max_host);
+	for (void *q : {(void *)e->sums_host, (void *)e->att_host, (void *)e->ops_host})
+		if (q) (void)hipHostFree(q);
 	for (hipEvent_t ev : {e->ev0, e->ev1})
 		if (ev) (void)hipEventDestroy(ev);
 	if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -207,6 +230,7 @@ int crd_ensemble_upload(crd_ensemble *e, int member, const void *y, int host_is_
 	const size_t points = (size_t)e->nx * (size_t)e->ny;
 	const EnsembleMember &m = e->members[(size_t)member];
 	ENS_TRY(e, hipMemcpyAsync(e->stage, y, 2 * points * (host_is_f64 ? 8 : 4), hipMemcpyHostToDevice, e->stream));
+	if (!e->adapt.empty()) e->adapt[(size_t)member].dense.pending = e->adapt[(size_t)member].ark.live = false;  // this member starts afresh
 	ENS_TRY(e, launch_ensemble_aos_to_planes(e->precision, host_is_f64, e->stage, m.u[e->cur], m.v[e->cur], points, e->stream));
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	return CRD_OK;
@@ -232,6 +256,7 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 	if (!e) return CRD_EINVAL;
 	if (nsteps < 0 || !(dt > 0.0) || !std::isfinite(t0)) return efail(e, CRD_EINVAL, "bad t0 / dt / nsteps");
 	TraceRange range("crd_ensemble_step_rk4");
+	for (auto &a : e->adapt) a.dense.pending = a.ark.live = false;  // stepping on from the states handed back (run_steps)
 	ENS_TRY(e, hipSetDevice(e->device));
 	EnsembleStep st{};
 	// the step's constants as launch_fused_t forms them
@@ -296,6 +321,401 @@ int crd_ensemble_max_abs(crd_ensemble *e, double *per_member)
 	ENS_TRY(e, hipMemcpyAsync(e->max_host, e->max_dev, (size_t)e->n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	for (int k = 0; k < e->n; k++) per_member[k] = e->max_host[k];
+	return CRD_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+enum { kY = 0, kSA = 1, kSB = 2, kACC = 3, kOUT = 4 };  // a context's plane roles (crd_ctx)
+
+// The first adaptive call's allocations: three more state buffers per member, the error partials, the per-member scalars and the
+// attempt / operand tables.  An ensemble that only takes fixed steps never makes them.
+int ensure_adaptive(crd_ensemble *e)
+{
+	if (!e->adapt.empty()) return CRD_OK;
+	const size_t B = (size_t)e->n, plane = (size_t)e->nx * (size_t)e->ny * e->real_size;
+	EnsemblePlan plan;
+	ENS_TRY(e, ensemble_attempt_plan(e->precision, e->model, e->nx, e->ny, e->n, &plan));
+	const long member_blocks = (long)plan.nsb * plan.nchunks;
+	if (member_blocks * e->n > INT32_MAX) return efail(e, CRD_EINVAL, "too many work items for one attempt launch");
+	const size_t member_items = (size_t)plan.nstrips * (size_t)plan.nchunks;
+	std::vector<crd_ensemble::Adaptive> adapt(B);
+	std::vector<void *> fresh;  // (freed again if a later allocation fails)
+	auto dev_alloc = [&](size_t bytes, void **q) {
+		*q = nullptr;
+		const hipError_t r = hipMalloc(q, bytes);
+		if (r == hipSuccess) fresh.push_back(*q);
+		return r;
+	};
+	auto undo = [&](int rc, const std::string &what) {
+		for (void *q : fresh) (void)hipFree(q);
+		if (e->sums_host) (void)hipHostFree(e->sums_host);
+		if (e->att_host) (void)hipHostFree(e->att_host);
+		if (e->ops_host) (void)hipHostFree(e->ops_host);
+		e->sums_host = nullptr;
+		e->att_host = nullptr;
+		e->ops_host = nullptr;
+		return efail(e, rc, what);
+	};
+	void *q = nullptr;
+	for (size_t k = 0; k < B; k++) {
+		const EnsembleMember &m = e->members[k];
+		adapt[k].buf[0] = m.u[e->cur];
+		adapt[k].buf[1] = m.u[1 - e->cur];
+		for (int b = 2; b < 5; b++) {
+			if (hipError_t r = dev_alloc(2 * plane, &q); r != hipSuccess) return undo(CRD_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(r));
+			adapt[k].buf[b] = q;
+		}
+	}
+	void *p[5] = {};
+	const size_t sizes[5] = {B * member_items * sizeof(double), B * kEnsembleNormBlocks * sizeof(double), B * sizeof(double), B * sizeof(EnsembleAttempt),
+	                         crd_ensemble::kOpSets * B * sizeof(EnsembleOp)};
+	for (int i = 0; i < 5; i++)
+		if (hipError_t r = dev_alloc(sizes[i], &p[i]); r != hipSuccess) return undo(CRD_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(r));
+	if (hipHostMalloc((void **)&e->sums_host, B * sizeof(double), hipHostMallocPortable) != hipSuccess ||
+	    hipHostMalloc((void **)&e->att_host, B * sizeof(EnsembleAttempt), hipHostMallocPortable) != hipSuccess ||
+	    hipHostMalloc((void **)&e->ops_host, crd_ensemble::kOpSets * B * sizeof(EnsembleOp), hipHostMallocPortable) != hipSuccess)
+		return undo(CRD_ENOMEM, "hipHostMalloc failed");
+	e->partials = static_cast<double *>(p[0]);
+	e->ydd_partials = static_cast<double *>(p[1]);
+	e->sums_dev = static_cast<double *>(p[2]);
+	e->att_dev = static_cast<EnsembleAttempt *>(p[3]);
+	e->ops_dev = static_cast<EnsembleOp *>(p[4]);
+	e->allocs.insert(e->allocs.end(), fresh.begin(), fresh.end());
+	e->aplan = plan;
+	e->adapt = std::move(adapt);
+	return CRD_OK;
+}
+
+// What one member does during one call (integrate_adaptive_impl's locals, per member).
+struct MemberRun {
+	crd_adaptive_stats st{};
+	double t = 0.0, t_prev = 0.0, h_cap = 0.0, t_boundary = 0.0;
+	int cur = kY, spare = kSA, third = kOUT, prev = -1;
+	int nef = 0, dst = -1;
+	int64_t steps = 0;
+	bool new_step = true, reinterpolate = false, failed = false;
+	arkode::Hin hin;
+	std::string why;
+};
+
+// Operand set `set` (0 .. kOpSets) of the batched element-wise launches: host entries, then one copy to the device.
+EnsembleOp *op_set(crd_ensemble *e, int set) { return e->ops_host + (size_t)set * (size_t)e->n; }
+hipError_t upload_ops(crd_ensemble *e, int set, int count)
+{
+	if (count <= 0) return hipSuccess;
+	return hipMemcpyAsync(e->ops_dev + (size_t)set * (size_t)e->n, op_set(e, set), (size_t)count * sizeof(EnsembleOp), hipMemcpyHostToDevice, e->stream);
+}
+EnsembleOp make_op(int member, const void *x0, const void *x1, const void *x2, const void *x3, void *out)
+{
+	EnsembleOp o{};
+	o.x[0] = x0;
+	o.x[1] = x1;
+	o.x[2] = x2;
+	o.x[3] = x3;
+	o.out = out;
+	o.member = member;
+	return o;
+}
+// the scalars of `count` members, written to sums_dev by work already enqueued, into sums_host (one wait)
+hipError_t fetch_sums(crd_ensemble *e, int count)
+{
+	if (hipError_t r = hipMemcpyAsync(e->sums_host, e->sums_dev, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, e->stream); r != hipSuccess) return r;
+	return hipStreamSynchronize(e->stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats, int32_t *status)
+{
+	if (!e) return CRD_EINVAL;
+	crd_adaptive_options o;
+	crd_adaptive_defaults(&o);
+	if (opt) o = *opt;
+	if (!arkode::options_valid(o, t0, tout)) return efail(e, CRD_EINVAL, "bad adaptive options / time interval");
+	if (o.method != CRD_ADAPT_ARKODE) return efail(e, CRD_EINVAL, "an ensemble integrates with CRD_ADAPT_ARKODE only");
+	const int B = e->n;
+	// Which members resume (a context's rule, per member: t0 is the output time its previous call handed back, and nothing has replaced
+	// its state since), and -- before any device work -- whether a fresh member's first-step estimate can be made at all.
+	std::vector<char> resume((size_t)B, 0);
+	bool estimate = false;
+	for (int k = 0; k < B; k++) {
+		if (!e->adapt.empty()) {
+			const auto &a = e->adapt[(size_t)k];
+			resume[(size_t)k] = a.dense.pending && a.ark.live && t0 == a.dense.t_out;
+		}
+		estimate = estimate || (!resume[(size_t)k] && !(o.h0 > 0.0) && tout > t0);
+	}
+	arkode::Hin probe;
+	if (estimate && !arkode::hin_start(probe, t0, tout)) return efail(e, CRD_EINVAL, arkode::kHinTooClose);
+	TraceRange range("crd_ensemble_integrate_adaptive");
+	ENS_TRY(e, hipSetDevice(e->device));
+	if (int rc = ensure_adaptive(e)) return rc;
+	const size_t points = (size_t)e->nx * (size_t)e->ny, plane = points * e->real_size;
+	const double n_components = 2.0 * (double)e->nx * (double)e->ny;  // WRMS norm over the whole grid
+	const double ka4 = std::pow(kGbKa, 4.0);
+
+	std::vector<MemberRun> run((size_t)B);
+	std::vector<int> hin, active;  // members that estimate their first step / that take steps
+	for (int k = 0; k < B; k++) {
+		MemberRun &r = run[(size_t)k];
+		auto &a = e->adapt[(size_t)k];
+		const crd_params &p = e->p[(size_t)k];
+		r.h_cap = o.h_max > 0.0 ? o.h_max : (o.h_max == 0.0 ? crd_stable_dt(&p) : INFINITY);  // the member's own stability bound
+		r.t_boundary = p.t_boundary;
+		r.t = r.t_prev = t0;
+		if (!resume[(size_t)k]) {
+			// the member's state is in its descriptor's current buffer; its other four buffers are free
+			void *y = e->members[(size_t)k].u[e->cur];
+			a.role[kY] = y;
+			int next = kSA;
+			for (void *b : a.buf)
+				if (b != y) a.role[next++] = b;
+			a.dense.pending = false;
+			arkode::init(a.ark, t0, o.h0);
+			if (arkode::needs_estimate(a.ark, t0, tout)) {
+				arkode::hin_start(r.hin, t0, tout);
+				hin.push_back(k);
+			}
+			continue;
+		}
+		r.st.t_internal = a.dense.t_np1;
+		if (tout <= a.dense.t_np1) {  // still inside the step already taken: interpolate again
+			r.reinterpolate = true;
+			r.prev = kOUT;
+			r.cur = kSA;
+			continue;
+		}
+		r.t = a.dense.t_np1;
+		r.cur = kSA;
+		r.spare = kOUT;
+		r.third = kY;
+	}
+
+	// arkHin of the fresh members, batched: f0 -> SB, the trial state -> SA, f(trial) -> ACC
+	if (!hin.empty()) {
+		const int nh = (int)hin.size();
+		for (int i = 0; i < nh; i++) {
+			const int k = hin[(size_t)i];
+			auto &a = e->adapt[(size_t)k];
+			op_set(e, 0)[i] = make_op(k, a.role[kY], nullptr, nullptr, nullptr, a.role[kSB]);
+			op_set(e, 0)[i].absorb = t0 < run[(size_t)k].t_boundary ? 1 : 0;
+			op_set(e, 1)[i] = make_op(k, a.role[kY], a.role[kSB], nullptr, nullptr, nullptr);
+		}
+		ENS_TRY(e, upload_ops(e, 0, nh));
+		ENS_TRY(e, upload_ops(e, 1, nh));
+		ENS_TRY(e, launch_ensemble_rhs(e->precision, e->model, e->table, e->ops_dev, nh, e->nx, e->ny, ka4, e->stream));
+		ENS_TRY(e, launch_ensemble_hin_bound(e->precision, e->ops_dev + B, nh, points, o.rtol, o.atol, e->sums_dev, e->stream));
+		ENS_TRY(e, fetch_sums(e, nh));
+		std::vector<int> open;
+		for (int i = 0; i < nh; i++) {
+			arkode::hin_bound(run[(size_t)hin[(size_t)i]].hin, e->sums_host[i]);
+			if (!run[(size_t)hin[(size_t)i]].hin.done) open.push_back(hin[(size_t)i]);
+		}
+		while (!open.empty()) {
+			const int no = (int)open.size();
+			for (int i = 0; i < no; i++) {
+				const int k = open[(size_t)i];
+				auto &a = e->adapt[(size_t)k];
+				const double hg = run[(size_t)k].hin.hg;
+				EnsembleOp &ax = op_set(e, 0)[i];
+				ax = make_op(k, a.role[kY], a.role[kSB], nullptr, nullptr, a.role[kSA]);
+				ax.c[0] = hg;
+				ax.cf[0] = (float)hg;
+				op_set(e, 1)[i] = make_op(k, a.role[kSA], nullptr, nullptr, nullptr, a.role[kACC]);
+				op_set(e, 1)[i].absorb = t0 + hg < run[(size_t)k].t_boundary ? 1 : 0;
+				op_set(e, 2)[i] = make_op(k, a.role[kY], a.role[kSB], a.role[kACC], nullptr, nullptr);
+				op_set(e, 2)[i].c[0] = 1.0 / hg;
+			}
+			for (int set = 0; set < 3; set++) ENS_TRY(e, upload_ops(e, set, no));
+			ENS_TRY(e, launch_ensemble_axpy(e->precision, e->ops_dev, no, points, e->stream));
+			ENS_TRY(e, launch_ensemble_rhs(e->precision, e->model, e->table, e->ops_dev + B, no, e->nx, e->ny, ka4, e->stream));
+			ENS_TRY(e, launch_ensemble_ydd_sumsq(e->precision, e->ops_dev + 2 * B, no, points, o.rtol, o.atol, e->ydd_partials, e->sums_dev, e->stream));
+			ENS_TRY(e, fetch_sums(e, no));
+			std::vector<int> still;
+			for (int i = 0; i < no; i++) {
+				arkode::Hin &H = run[(size_t)open[(size_t)i]].hin;
+				arkode::hin_ydd(H, std::sqrt(e->sums_host[i] / n_components));
+				if (!H.done) still.push_back(open[(size_t)i]);
+			}
+			open.swap(still);
+		}
+		for (int k : hin) e->adapt[(size_t)k].ark.h = run[(size_t)k].hin.h0;
+	}
+	for (int k = 0; k < B; k++) {
+		MemberRun &r = run[(size_t)k];
+		if (r.reinterpolate) continue;
+		auto &A = e->adapt[(size_t)k].ark;
+		if (!resume[(size_t)k]) arkode::first_step(A, r.h_cap);
+		r.st.h_first = arkode::first_attempt(A);
+		if (r.t < tout) active.push_back(k);
+	}
+
+	// Rounds: one attempt of every active member in one launch, the per-member sums, one wait, then each member's controller.
+	const EnsemblePlan &pl = e->aplan;
+	EnsembleAttemptLaunch l{};
+	l.rtol = o.rtol;
+	l.atol = o.atol;
+	l.ka4 = ka4;
+	l.partials = e->partials;
+	l.nx = e->nx;
+	l.ny = e->ny;
+	l.nstrips = pl.nstrips;
+	l.sw = pl.sw;
+	l.nsb = pl.nsb;
+	l.chunk = pl.chunk;
+	l.nchunks = pl.nchunks;
+	l.member_blocks = pl.nsb * pl.nchunks;
+	l.member_items = pl.nstrips * pl.nchunks;
+	const double cs[5] = {0.0, 0.5, 0.5, 1.0, 0.75};  // stage times: make_fused_call's four, then Zonneveld's fifth (launch_attempt)
+	std::vector<int> slot_member;
+	while (!active.empty()) {
+		slot_member.clear();
+		bool absorb = false;
+		for (int k : active) {
+			MemberRun &r = run[(size_t)k];
+			auto &a = e->adapt[(size_t)k];
+			if (r.new_step) {
+				if (const char *why = arkode::begin_step(a.ark, r.t, r.steps, o.max_steps)) {
+					r.failed = true;
+					r.why = why;
+					continue;
+				}
+				r.new_step = false;
+				r.nef = 0;
+				r.dst = r.spare;
+			}
+			const double h = a.ark.h;
+			EnsembleAttempt &at = e->att_host[slot_member.size()];
+			at = EnsembleAttempt{};
+			at.in = a.role[r.cur];
+			at.out = a.role[r.dst];
+			at.h[0] = h;  // as launch_fused_t forms them
+			at.h[1] = 0.5 * h;
+			at.h[2] = h / 3.0;
+			at.h[3] = h / 6.0;
+			for (int q = 0; q < 4; q++) at.hf[q] = (float)at.h[q];
+			at.member = k;
+			for (int q = 0; q < 5; q++) {
+				at.absorb[q] = r.t + cs[q] * h < r.t_boundary ? 1 : 0;  // strict <, absorbing() (crd_ctx.h)
+				absorb = absorb || at.absorb[q];
+			}
+			slot_member.push_back(k);
+		}
+		const int count = (int)slot_member.size();
+		if (count > 0) {
+			l.nblocks = l.member_blocks * count;
+			ENS_TRY(e, hipMemcpyAsync(e->att_dev, e->att_host, (size_t)count * sizeof(EnsembleAttempt), hipMemcpyHostToDevice, e->stream));
+			ENS_TRY(e, launch_ensemble_attempts(e->precision, e->model, absorb && e->model != dev::kModelDiffusionOnly, e->table, e->att_dev, count, l, e->sums_dev, e->stream));
+			ENS_TRY(e, fetch_sums(e, count));
+		}
+		for (int i = 0; i < count; i++) {
+			const int k = slot_member[(size_t)i];
+			MemberRun &r = run[(size_t)k];
+			auto &A = e->adapt[(size_t)k].ark;
+			const double dsm = std::sqrt(e->sums_host[i] / n_components);
+			r.st.err_last = dsm;
+			if (dsm <= 1.0) {  // (a NaN fails the test)
+				r.t_prev = r.t;
+				arkode::accept(A, dsm, o, r.h_cap, r.t, r.st);
+				r.steps++;
+				// rotate: the old state becomes y_n (kept for the interpolant), the old y_n / scratch becomes the next target
+				const int old_cur = r.cur;
+				r.cur = r.dst;
+				r.spare = (r.prev >= 0) ? r.prev : r.third;
+				if (r.prev < 0) r.third = -1;
+				r.prev = old_cur;
+				r.new_step = true;
+			} else if (!arkode::reject(A, dsm, &r.nef, o, r.h_cap, r.st)) {
+				r.failed = true;
+				r.why = arkode::kErrFailure;
+			}
+		}
+		std::vector<int> still;
+		for (int k : active)
+			if (!run[(size_t)k].failed && run[(size_t)k].t < tout) still.push_back(k);
+		active.swap(still);
+	}
+
+	// ARK_NORMAL output: f at both ends of each finished member's last step, then the cubic Hermite interpolant at tout (members that
+	// interpolate again inside a step already taken need the interpolant only).  Three batched launches; the buffers are re-labelled.
+	int nd = 0, nhm = 0;
+	for (int k = 0; k < B; k++) {
+		MemberRun &r = run[(size_t)k];
+		auto &a = e->adapt[(size_t)k];
+		if (r.reinterpolate || r.failed || r.prev < 0 || r.t < tout) continue;
+		op_set(e, 0)[nd] = make_op(k, a.role[r.prev], nullptr, nullptr, nullptr, a.role[kSB]);
+		op_set(e, 0)[nd].absorb = r.t_prev < r.t_boundary ? 1 : 0;
+		op_set(e, 1)[nd] = make_op(k, a.role[r.cur], nullptr, nullptr, nullptr, a.role[kACC]);
+		op_set(e, 1)[nd].absorb = r.t < r.t_boundary ? 1 : 0;
+		nd++;
+	}
+	for (int k = 0; k < B; k++) {
+		MemberRun &r = run[(size_t)k];
+		auto &a = e->adapt[(size_t)k];
+		const bool fresh_output = !r.reinterpolate && !r.failed && r.prev >= 0 && r.t >= tout;
+		if (!r.reinterpolate && !fresh_output) continue;
+		const double t_n = r.reinterpolate ? a.dense.t_n : r.t_prev, t_np1 = r.reinterpolate ? a.dense.t_np1 : r.t, hstep = t_np1 - t_n;
+		const int out = kY + kSA + kOUT - r.prev - r.cur;
+		EnsembleOp &op = op_set(e, 2)[nhm++];
+		op = make_op(k, a.role[r.prev], a.role[r.cur], a.role[kSB], a.role[kACC], a.role[out]);
+		ensemble_hermite_coefficients((tout - t_n) / hstep, hstep, op.c, op.cf);
+	}
+	for (int set = 0; set < 3; set++) ENS_TRY(e, upload_ops(e, set, set < 2 ? nd : nhm));
+	ENS_TRY(e, launch_ensemble_rhs(e->precision, e->model, e->table, e->ops_dev, nd, e->nx, e->ny, ka4, e->stream));
+	ENS_TRY(e, launch_ensemble_rhs(e->precision, e->model, e->table, e->ops_dev + B, nd, e->nx, e->ny, ka4, e->stream));
+	ENS_TRY(e, launch_ensemble_hermite(e->precision, e->ops_dev + 2 * B, nhm, points, e->stream));
+
+	int rc = CRD_OK;
+	std::string failures;
+	for (int k = 0; k < B; k++) {
+		MemberRun &r = run[(size_t)k];
+		auto &a = e->adapt[(size_t)k];
+		const bool output = r.reinterpolate || (!r.failed && r.prev >= 0 && r.t >= tout);
+		if (output) {
+			// roles now: prev = y_n, cur = y_{n+1}, SB = f_n, ACC = f_{n+1}; the interpolant is in the remaining state buffer
+			const int out = kY + kSA + kOUT - r.prev - r.cur;
+			void *b_out = a.role[out], *b_n = a.role[r.prev], *b_np1 = a.role[r.cur];
+			a.role[kY] = b_out;
+			a.role[kSA] = b_np1;
+			a.role[kOUT] = b_n;
+			if (!r.reinterpolate) {
+				a.dense.pending = true;
+				a.dense.t_n = r.t_prev;
+				a.dense.t_np1 = r.t;
+				r.st.t_internal = r.t;
+			}
+			a.dense.t_out = tout;
+			r.st.t = tout;
+		} else {  // no output (a zero-length interval, or a failure): hand back the state reached
+			if (r.cur != kY) std::swap(a.role[kY], a.role[r.cur]);
+			a.dense.pending = false;
+			r.st.t_internal = r.t;
+			r.st.t = r.t;
+		}
+		if (!r.reinterpolate) a.ark.live = !r.failed && a.dense.pending;
+		r.st.h_next = a.ark.hprime;
+		if (r.failed) {
+			rc = CRD_ESTATE;
+			failures += (failures.empty() ? "" : "; ") + std::string("member ") + std::to_string(k) + ": " + r.why;
+		}
+		if (stats) stats[k] = r.st;
+		if (status) status[k] = r.failed ? CRD_ESTATE : CRD_OK;
+		// the descriptor: the state handed back is the current buffer; the other one (overwritten only by a fixed step, which ends the
+		// carry-over) the integrator's own state
+		EnsembleMember &m = e->members[(size_t)k];
+		m.u[e->cur] = a.role[kY];
+		m.v[e->cur] = static_cast<char *>(a.role[kY]) + plane;
+		m.u[1 - e->cur] = a.role[kSA];
+		m.v[1 - e->cur] = static_cast<char *>(a.role[kSA]) + plane;
+	}
+	ENS_TRY(e, hipMemcpyAsync(e->table, e->members.data(), (size_t)B * sizeof(EnsembleMember), hipMemcpyHostToDevice, e->stream));
+	ENS_TRY(e, hipStreamSynchronize(e->stream));
+	if (rc != CRD_OK) return efail(e, rc, "adaptive integration failed for " + failures);
 	return CRD_OK;
 }
 

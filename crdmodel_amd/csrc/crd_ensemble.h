@@ -51,4 +51,63 @@ hipError_t launch_ensemble_planes_to_aos(int precision, int dst_is_f64, const vo
 // max |u| of buffer `src` of every member into out_dev[0 .. members) (NaN propagates: a blown-up member reads non-finite).
 hipError_t launch_ensemble_max_abs(int precision, const EnsembleMember *table, int members, int src, size_t n, double *out_dev, hipStream_t s);
 
+
+// ---- error-controlled integration (crd_ensemble_adaptive.hip; crd_ensemble.cpp: crd_ensemble_integrate_adaptive) ----
+
+// One member's attempt of a round: an entry of a table in device memory, written by the host before each round's launch and read
+// through the constant address space.  Members take their own step sizes, so what a context's attempt gets as kernel arguments is here.
+struct EnsembleAttempt {
+	const void *in;         // y_n: a state buffer (u plane, then v plane), row 0 first, no ghost rows
+	void *out;              // the attempt's y_{n+1}
+	double h[4];            // h, h/2, h/3, h/6 formed in double as launch_fused_t forms them (fp64 kernels)
+	float hf[4];            // ... rounded to fp32 on the host (fp32 kernels: a conversion in the kernel would cost registers)
+	int member;             // index into the member table and into the error partials' segments
+	int absorb[5];          // t_stage < tBoundary at t + (0, 1/2, 1/2, 1, 3/4) h: the four stages and Zonneveld's fifth
+};
+
+// What one attempt launch shares over its members.
+struct EnsembleAttemptLaunch {
+	double rtol, atol, ka4;
+	double *partials;       // member k's error partials: [k * member_items, (k + 1) * member_items)
+	int nx, ny;
+	int nstrips, sw, nsb, chunk, nchunks;  // the attempt plan (fixed at the first adaptive call)
+	int member_blocks;      // nsb * nchunks
+	int member_items;       // nstrips * nchunks: the partials of one member's attempt
+	int nblocks;            // member_blocks * attempts
+};
+
+// One member's operands of a batched element-wise operation (arkHin's, the dense output's): buffer base pointers as in
+// EnsembleAttempt, a scalar set in double and in fp32 (rounded on the host), and the member's absorbing flag at the operation's time.
+struct EnsembleOp {
+	const void *x[4];
+	void *out;
+	double c[4];
+	float cf[4];
+	int member;
+	int absorb;
+};
+
+// The attempt kernel's plan: one column per lane, the embedded apron (54 valid columns per wavefront), the ensemble's chunk rule.
+hipError_t ensemble_attempt_plan(int precision, int model, int nx, int ny, int members, EnsemblePlan *plan);
+// One Zonneveld 5(3)4 attempt of each of `count` members (attempts[0 .. count)), and the fixed-order sum of each one's partials into
+// sums_dev[slot].  absorb: some entry has an absorbing flag set.
+hipError_t launch_ensemble_attempts(int precision, int model, bool absorb, const EnsembleMember *table, const EnsembleAttempt *attempts, int count,
+                                    const EnsembleAttemptLaunch &l, double *sums_dev, hipStream_t s);
+// Batched over ops[0 .. count), n = nx * ny points per field, out_dev[slot] where a scalar comes out:
+//   rhs        out = f(t, x0) with the member's tables and absorb flag (the bare RHS of rhs_on_planes: the same bits)
+//   hin_bound  out_dev = max_i |x1_i| / (0.1 |x0_i| + rtol |x0_i| + atol)
+//   axpy       out = x0 + c0 x1
+//   ydd_sumsq  out_dev = sum_i (((x2_i - x1_i) c0) / (rtol |x0_i| + atol))^2 in launch_ydd_sumsq's order (c0 = 1 / h)
+//   hermite    out = c0 x0 + c1 x2 + c2 x1 + c3 x3 (yn, yp, fn, fp: launch_hermite's coefficients)
+hipError_t launch_ensemble_rhs(int precision, int model, const EnsembleMember *table, const EnsembleOp *ops, int count, int nx, int ny, double ka4, hipStream_t s);
+hipError_t launch_ensemble_hin_bound(int precision, const EnsembleOp *ops, int count, size_t n, double rtol, double atol, double *out_dev, hipStream_t s);
+hipError_t launch_ensemble_axpy(int precision, const EnsembleOp *ops, int count, size_t n, hipStream_t s);
+hipError_t launch_ensemble_ydd_sumsq(int precision, const EnsembleOp *ops, int count, size_t n, double rtol, double atol, double *partials_dev, double *out_dev,
+                                     hipStream_t s);
+hipError_t launch_ensemble_hermite(int precision, const EnsembleOp *ops, int count, size_t n, hipStream_t s);
+constexpr int kEnsembleNormBlocks = 256;
+// launch_hermite's coefficients h00, h10, h01, h11 of the interpolant at t_n + theta h, formed as it forms them, in double and rounded to
+// fp32 (in the kernels' unit, under its floating-point contraction setting).
+void ensemble_hermite_coefficients(double theta, double h, double c[4], float cf[4]);  // blocks per member of the ydd norm (crd_kernels.hip: kNormBlocks); partials_dev: count x that
+
 }  // namespace crd

@@ -52,7 +52,8 @@ struct Options {
 		          << " --model fhn|goldbeter --surface torus|flat [--gpus G] [--devices D] [--dt DT] [--stepper auto|staged|fused]\n"
 		             "       [--precision 64|32] [--adaptive|--adaptive-rk43|--fixed] [--binary|--binary-only] [--ref-steady-state] [--decomp D0xD1|mpi [--block-contexts]]\n"
 		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary=V1,V2,... (repeatable)]\n"
-		             "       <Config file path>\n";
+		             "       <Config file path>\n"
+		             "  --ensemble: fixed-step RK4, or error-controlled (each member its own ARKode-style steps) when the ini asks for [Solver] adaptive = 1\n";
 	}
 	std::exit(EXIT_FAILURE);
 }
@@ -187,12 +188,16 @@ int die(const char *what, int rc, crd_ctx *ctx)
 
 // --ensemble: the run of the ini once per member, the members' parameters zipped from the lists, all stepped together on one GPU
 // (crd_ensemble_*).  Member k writes the reference's files of a single-rank run into <outdir>/member_<k>/, from its own initial
-// conditions; all members take one step size: the ini's / --dt's, else the smallest member's dtSafety x crd_stable_dt.  A member whose
-// state goes non-finite is written no further from that output on, as a lone run stops there; the others run to tFinal, and the run
-// then exits 1 naming it.
+// conditions.  Fixed steps: all members take one step size, the ini's / --dt's, else the smallest member's dtSafety x crd_stable_dt.
+// [Solver] adaptive = 1 in the ini: error-controlled, one crd_ensemble_integrate_adaptive call per output (a lone adaptive run's
+// crd_group_integrate_adaptive call), each member with its own step sequence.  A member whose state goes non-finite, or whose
+// integrator fails, is written no further from that output on, as a lone run stops there; the others run to tFinal, and the run then
+// exits 1 naming it.
 int run_ensemble(const Options &o, crd_run_config cfg)
 {
-	if (cfg.adaptive) usage_error("--ensemble steps fixed-step RK4 only: the ini asks for [Solver] adaptive (pass --fixed)");
+	if (cfg.adaptive == 2)
+		usage_error("--ensemble integrates error-controlled with ARKode's pair only: the ini asks for [Solver] adaptive = 2 (RK4(3); pass --fixed, or set adaptive = 1)");
+	const bool adaptive = cfg.adaptive == 1;
 	if (cfg.n_gpus > 1) usage_error("--ensemble runs on one GPU: the ini asks for [Solver] gpus = " + std::to_string(cfg.n_gpus) + " (pass --gpus 1)");
 	const int B = (int)o.ensemble[0].second.size();
 	std::vector<crd_run_config> mc((size_t)B, cfg);
@@ -230,8 +235,12 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 			std::cout << "  -> " << o.outdir << "/member_" << k << "\n";
 		}
 		std::cout << "   Tfinal = " << cfg.t_final << ", output timesteps = " << Nt << "\n";
-		std::cout << "   integrator = classical RK4 on GPU, dt = " << dt << " (" << steps_per_output << " steps per output; "
-		          << (dt_member < 0 ? std::string("from [Solver] dt / --dt") : "the smallest member's dtSafety x stable dt: member " + std::to_string(dt_member)) << ")\n";
+		if (adaptive)
+			std::cout << "   integrator = ARKode-style ERK on GPU (Zonneveld 5(3)4, PID controller), each member its own steps\n   rtol = " << cfg.rtol
+			          << "\n   atol = " << cfg.atol << "\n";
+		else
+			std::cout << "   integrator = classical RK4 on GPU, dt = " << dt << " (" << steps_per_output << " steps per output; "
+			          << (dt_member < 0 ? std::string("from [Solver] dt / --dt") : "the smallest member's dtSafety x stable dt: member " + std::to_string(dt_member)) << ")\n";
 	}
 
 	std::vector<crd_writer *> wr((size_t)B, nullptr);
@@ -262,17 +271,44 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 	}
 
 	std::vector<int> blown_at((size_t)B, 0);  // output (1-based) at which a member went non-finite; 0: never
+	std::vector<int> failed_at((size_t)B, 0);  // ... at which its error-controlled integration failed
 	std::vector<double> peak((size_t)B);
+	std::vector<crd_adaptive_stats> as((size_t)B);
+	std::vector<int32_t> member_status((size_t)B);
+	std::vector<long long> accepted((size_t)B, 0), rejected((size_t)B, 0);
+	crd_adaptive_options ao;
+	crd_adaptive_defaults(&ao);
+	ao.rtol = cfg.rtol;
+	ao.atol = cfg.atol;
+	ao.method = CRD_ADAPT_ARKODE;
+	ao.h0 = 0.0;          // first step: arkHin; the controller's memory carries over in the ensemble
+	ao.dense_output = 1;  // ARK_NORMAL: output times do not shorten steps, the row written is the interpolant at tout
 	double stepping_s = 0.0;
 	for (int iout = 0; iout < Nt; iout++) {
 		const double t = iout * dTout;
 		const auto step_t0 = std::chrono::steady_clock::now();
-		rc = crd_ensemble_step_rk4(ens, t, dt, steps_per_output);
+		if (adaptive) {
+			// one ARKode(...) call per output interval for every member, src/FHNmodel_torus.cpp:423 (a failed member still takes part in
+			// later calls, from the state it was left at, but is written no further)
+			rc = crd_ensemble_integrate_adaptive(ens, t, (iout + 1 == Nt) ? cfg.t_final : (iout + 1) * dTout, &ao, as.data(), member_status.data());
+			if (rc == CRD_ESTATE) {
+				for (int k = 0; k < B; k++)
+					if (member_status[(size_t)k] != CRD_OK && !failed_at[(size_t)k] && !blown_at[(size_t)k]) {
+						failed_at[(size_t)k] = iout + 1;
+						std::cerr << "\nSolver failure, stopping integration of member " << k << " (" << crd_ensemble_last_error(ens) << ")\n";  // src/FHNmodel_torus.cpp:433
+					}
+				rc = CRD_OK;
+			}
+			for (int k = 0; k < B && rc == CRD_OK; k++)
+				if (!failed_at[(size_t)k] && !blown_at[(size_t)k]) accepted[(size_t)k] += as[(size_t)k].accepted, rejected[(size_t)k] += as[(size_t)k].rejected;
+		} else {
+			rc = crd_ensemble_step_rk4(ens, t, dt, steps_per_output);
+		}
 		if (rc == CRD_OK) rc = crd_ensemble_synchronize(ens);
 		stepping_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - step_t0).count();
 		if (rc == CRD_OK) rc = crd_ensemble_max_abs(ens, peak.data());
 		for (int k = 0; k < B && rc == CRD_OK; k++) {
-			if (blown_at[(size_t)k]) continue;
+			if (blown_at[(size_t)k] || failed_at[(size_t)k]) continue;
 			if (!std::isfinite(peak[(size_t)k])) {
 				blown_at[(size_t)k] = iout + 1;
 				std::cerr << "\nSolver failure, stopping integration of member " << k << " (non-finite state at output " << iout + 1 << ")\n";  // src/FHNmodel_torus.cpp:433
@@ -295,8 +331,20 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		if (blown_at[(size_t)k]) {
 			std::cerr << "member " << k << " blew up at output " << blown_at[(size_t)k] << " of " << Nt << "; its files stop there\n";
 			status = 1;
+		} else if (failed_at[(size_t)k]) {
+			std::cerr << "member " << k << " failed its error-controlled integration at output " << failed_at[(size_t)k] << " of " << Nt << "; its files stop there\n";
+			status = 1;
 		}
-	if (!o.quiet && stepping_s > 0.0) {
+	if (!o.quiet && adaptive) {
+		std::cout << "\n";
+		for (int k = 0; k < B; k++) std::cout << "   member " << k << ": steps = " << accepted[(size_t)k] << " (+" << rejected[(size_t)k] << " rejected)\n";
+	}
+	if (!o.quiet && adaptive && stepping_s > 0.0) {
+		long long attempts = 0;
+		for (int k = 0; k < B; k++) attempts += accepted[(size_t)k] + rejected[(size_t)k];
+		std::printf("   rate: %d members, %lld attempts in %.6f s of stepping = %.1f attempts/s\n", B, attempts, stepping_s, (double)attempts / stepping_s);
+		std::cout << "   ----------------------\n";
+	} else if (!o.quiet && stepping_s > 0.0) {
 		const double ps = (double)B * (double)g.nx * (double)g.ny * (double)steps_per_output * Nt / stepping_s;
 		std::printf("\n   rate: %d members x %lld steps in %.6f s of stepping = %.4g grid-point-steps/s\n", B, (long long)steps_per_output * Nt, stepping_s, ps);
 		std::cout << "   ----------------------\n";

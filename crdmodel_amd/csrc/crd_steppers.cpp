@@ -645,43 +645,15 @@ static int collect_scalar(crd_ctx *const *cs, int n, bool take_max, double *out)
 	return CRD_OK;
 }
 
-// ARKode's step-size controller (CRD_ADAPT_ARKODE), restated from its documentation; oracle/arkode_erk.py has the same rules
-// with the same names, and the tests compare the two attempt by attempt.
-namespace arkode {
-constexpr double kK1 = 0.58, kK2 = 0.21, kK3 = 0.1;  // ARK_ADAPT_PID gains
-constexpr int kEmbeddingOrder = 3;                   // Zonneveld 5(3)4; "pq = 0": the embedding's order enters the exponents
-constexpr double kEtamx1 = 10000.0, kEtamxf = 0.3;   // growth bound of the very first step; bound from the second failure of a step on
-constexpr int kSmallNef = 2, kMaxNef = 7;
-constexpr double kLbound = 1.0, kUbound = 1.5, kOnePsm = 1.000001, kOneMsm = 0.999999;  // no change of h for lbound <= eta <= ubound
-constexpr double kTiny = 1.0e-10, kUround = 2.220446049250313e-16;
-constexpr double kH0LbFactor = 100.0, kH0UbFactor = 0.1, kH0Bias = 0.5;
-constexpr int kH0Iters = 4;
-
-// arkAdapt with the PID method and no explicit-stability function: eta = h_new / h.  e = (this step's biased error, the previous
-// accepted step's, the one before that).
-double pid_eta(double h, const double e[3], double etamax, double safety, double etamin, double h_cap)
-{
-	const double e1 = std::fmax(e[0], kTiny), e2 = std::fmax(e[1], kTiny), e3 = std::fmax(e[2], kTiny);
-	double h_acc = h * std::pow(e1, -kK1 / kEmbeddingOrder) * std::pow(e2, kK2 / kEmbeddingOrder) * std::pow(e3, -kK3 / kEmbeddingOrder);
-	h_acc *= safety;
-	h_acc = std::fmin(std::fabs(h_acc), std::fabs(etamax * h));
-	h_acc = std::fmax(std::fabs(h_acc), std::fabs(etamin * h));
-	if (std::fabs(h_acc) > std::fabs(h * kLbound * kOneMsm) && std::fabs(h_acc) < std::fabs(h * kUbound * kOnePsm)) h_acc = h;
-	double eta = h_acc / h;
-	if (std::isfinite(h_cap)) eta /= std::fmax(1.0, std::fabs(h) * eta / h_cap);  // hmax_inv
-	return eta;
-}
-}  // namespace arkode
+// ARKode's step-size controller (CRD_ADAPT_ARKODE) and its bookkeeping: crd_arkode.h (shared with the ensemble's integrator).
 
 // arkHin: ARKode's estimate of the first step from y'' along a forward Euler trial step, on the planes: f0 -> SB, trial state ->
 // SA, f(trial) -> ACC (all three are scratch on a fresh state).
 static int arkode_initial_step(crd_ctx *const *cs, int n, double t0, double tout, int cur, const crd_adaptive_options &o, double n_components, double *h0)
 {
-	using namespace arkode;
 	crd_ctx *lead = cs[0];
-	const double tdist = std::fabs(tout - t0), tround = kUround * std::fmax(std::fabs(t0), std::fabs(tout));
-	if (tdist < 2.0 * tround) return fail(lead, CRD_EINVAL, "adaptive integration: tout too close to t0 to estimate a first step");
-	const double hlb = kH0LbFactor * tround;
+	arkode::Hin H;
+	if (!arkode::hin_start(H, t0, tout)) return fail(lead, CRD_EINVAL, arkode::kHinTooClose);
 	if (int rc = rhs_on_planes(cs, n, t0, cur, crd_ctx::SB)) return rc;
 	for (int k = 0; k < n; k++) {
 		crd_ctx *c = cs[k];
@@ -690,16 +662,9 @@ static int arkode_initial_step(crd_ctx *const *cs, int n, double t0, double tout
 	}
 	double hub_inv = 0.0;
 	if (int rc = collect_scalar(cs, n, true, &hub_inv)) return rc;
-	double hub = kH0UbFactor * tdist;
-	if (hub * hub_inv > 1.0) hub = 1.0 / hub_inv;
-	double hg = std::sqrt(hlb * hub);
-	if (hub < hlb) {
-		*h0 = hg;
-		return CRD_OK;
-	}
-	bool hnew_ok = false;
-	double hnew = hg;
-	for (int count = 1; count <= kH0Iters; count++) {
+	arkode::hin_bound(H, hub_inv);
+	while (!H.done) {
+		const double hg = H.hg;
 		for (int k = 0; k < n; k++) {
 			crd_ctx *c = cs[k];
 			if (int rc = set_device(c)) return rc;
@@ -714,21 +679,9 @@ static int arkode_initial_step(crd_ctx *const *cs, int n, double t0, double tout
 		}
 		double sum = 0.0;
 		if (int rc = collect_scalar(cs, n, false, &sum)) return rc;
-		const double yddnrm = std::sqrt(sum / n_components);
-		if (hnew_ok || count == kH0Iters) {
-			hnew = hg;
-			break;
-		}
-		hnew = (yddnrm * hub * hub > 2.0) ? std::sqrt(2.0 / yddnrm) : std::sqrt(hg * hub);
-		const double hrat = hnew / hg;
-		if (hrat > 0.5 && hrat < 2.0) hnew_ok = true;
-		if (count > 1 && hrat > 2.0) {
-			hnew = hg;
-			hnew_ok = true;
-		}
-		hg = hnew;
+		arkode::hin_ydd(H, std::sqrt(sum / n_components));
 	}
-	*h0 = std::fmin(std::fmax(kH0Bias * hnew, hlb), hub);
+	*h0 = H.h0;
 	return CRD_OK;
 }
 
@@ -740,9 +693,7 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 	crd_adaptive_options o;
 	crd_adaptive_defaults(&o);
 	if (opt_in) o = *opt_in;
-	if (!(o.rtol >= 0.0) || !(o.atol >= 0.0) || !(o.rtol + o.atol > 0.0) || !(o.safety > 0.0) || !(o.bias > 0.0) || !(o.growth >= 1.0) ||
-	    !(o.shrink > 0.0 && o.shrink < 1.0) || o.max_steps < 1 || !(o.h0 >= 0.0) || std::isnan(o.h_max) || !std::isfinite(t0) || !std::isfinite(tout) || tout < t0 ||
-	    (o.method != CRD_ADAPT_RK43 && o.method != CRD_ADAPT_ARKODE))
+	if (!arkode::options_valid(o, t0, tout))
 		return fail(lead, CRD_EINVAL, "bad adaptive options / time interval");
 	if (lead->d0 > 1) return fail(lead, CRD_EINVAL, "the error-controlled integrators need phi-slabs (theta-blocks step with the staged RK4 only)");
 	const bool multi = lead->halo != CRD_HALO_SELF;
@@ -832,23 +783,16 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 	}
 	if (arkode_method) {
 		if (!resume) {  // a fresh state: ARKodeInit
-			A.live = false;
-			A.nst = 0;
-			A.tn = t0;
-			A.eta = 1.0;
-			A.etamax = arkode::kEtamx1;
-			A.ehist[0] = A.ehist[1] = A.ehist[2] = 1.0;
-			A.h = o.h0;
-			if (!(A.h > 0.0) && tout > t0)
+			arkode::init(A, t0, o.h0);
+			if (arkode::needs_estimate(A, t0, tout))
 				if (int rc = arkode_initial_step(cs, n, t0, tout, cur, o, n_components, &A.h)) return rc;
-			A.h = std::fmin(A.h, h_cap);
-			A.hprime = A.h;
+			arkode::first_step(A, h_cap);
 		}
 		h = A.h;
 	} else {
 		h = std::fmin(o.h0 > 0.0 ? o.h0 : 0.8 * crd_stable_dt(&lead->p), h_cap);
 	}
-	st.h_first = (arkode_method && A.nst > 0 && A.hprime != A.h) ? A.h * A.eta : h;
+	st.h_first = arkode_method ? arkode::first_attempt(A) : h;
 
 	// Ghost rows of each plane's present content that are still valid (multi-slab; a single slab wraps in the kernel).  The
 	// integrator exchanges kAdaptGhost rows of the state it is about to step from when fewer than the attempt's five are left, and
@@ -980,13 +924,8 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 	int next_slot = 0;
 	while (t < tout && rc == CRD_OK && arkode_method) {
 		// ---- CRD_ADAPT_ARKODE: one step = attempts until the error test passes (arkStep), then arkPrepareNextStep / arkCompleteStep ----
-		if (steps_this_call >= o.max_steps) {
-			rc = fail(lead, CRD_ESTATE, "adaptive integration: max_steps steps taken before reaching tout (ARK_TOO_MUCH_WORK)");
-			break;
-		}
-		if (A.nst > 0 && A.hprime != A.h) A.h *= A.eta;
-		if (!(A.h > 1e-14 * std::fmax(std::fabs(t), 1e-300)) && !(t == 0.0 && A.h > 0.0)) {
-			rc = fail(lead, CRD_ESTATE, "adaptive integration: step size underflow");
+		if (const char *why = arkode::begin_step(A, t, steps_this_call, o.max_steps)) {
+			rc = fail(lead, CRD_ESTATE, why);
 			break;
 		}
 		const int dst = spare;
@@ -1024,40 +963,16 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 #endif
 			if (dsm <= 1.0) break;  // (a NaN fails the test)
 			ahead.live = false;     // a failed step: what was launched ahead of it is void
-			nef++;
-			st.rejected++;
-			if (nef == arkode::kMaxNef) {
-				rc = fail(lead, CRD_ESTATE, "adaptive integration: the error test failed 7 times on one step (ARK_ERR_FAILURE)");
+			if (!arkode::reject(A, dsm, &nef, o, h_cap, st)) {
+				rc = fail(lead, CRD_ESTATE, arkode::kErrFailure);
 				break;
 			}
-			A.etamax = 1.0;  // no growth for the rest of this step, and none after it
-			const double e[3] = {std::isfinite(dsm) ? dsm * o.bias : 1e300, A.ehist[0], A.ehist[1]};
-			double eta = arkode::pid_eta(A.h, e, A.etamax, o.safety, o.shrink, h_cap);
-			if (nef >= arkode::kSmallNef) eta = std::fmin(eta, arkode::kEtamxf);
-			A.h *= eta;
 		}
 		if (rc != CRD_OK) break;
-		A.ehist[2] = A.ehist[1];
-		A.ehist[1] = A.ehist[0];
-		A.ehist[0] = dsm * o.bias;
-		if (A.etamax == 1.0) {  // the step failed its test at least once: keep its size for the next one
-			A.hprime = A.h;
-			A.eta = 1.0;
-		} else {
-			A.eta = arkode::pid_eta(A.h, A.ehist, A.etamax, o.safety, o.shrink, h_cap);
-			A.hprime = A.h * A.eta;
-		}
-		A.etamax = o.growth;
 		t_prev = t;
-		t += A.h;
-		A.tn = t;
-		A.nst++;
+		arkode::accept(A, dsm, o, h_cap, t, st);
 		steps_this_call++;
 		accept_planes(dst);
-		st.accepted++;
-		st.h_last = A.h;
-		st.h_min = (st.h_min == 0.0) ? A.h : std::fmin(st.h_min, A.h);
-		st.h_max = std::fmax(st.h_max, A.h);
 	}
 	while (t < tout && rc == CRD_OK && !arkode_method) {
 		// ---- CRD_ADAPT_RK43: the embedded pair and I-controller of rounds 1-2 ----

@@ -444,6 +444,27 @@ class Ensemble:
         self._check(lib().crd_ensemble_max_abs(self._h, v), "crd_ensemble_max_abs")
         return list(v)
 
+    def integrate_adaptive(self, t0, tout, **options):
+        """Error-controlled integration of every member from t0 to tout (crd_ensemble_integrate_adaptive): each member steps as a Slab of
+        its params would with Slab.integrate_adaptive and the same options (CRD_ADAPT_ARKODE only).  Returns one stats dict per member,
+        each with a `status` entry (OK, or ESTATE for a member that failed alone -- the others still reach tout); raises CrdError only for
+        failures of the call itself."""
+        opt = _adaptive_options(options)
+        st = (capi.AdaptiveStats * self.n_members)()
+        status = (C.c_int32 * self.n_members)()
+        rc = lib().crd_ensemble_integrate_adaptive(self._h, t0, tout, C.byref(opt), st, status)
+        if rc not in (capi.OK, capi.ESTATE):
+            raise CrdError(rc, "crd_ensemble_integrate_adaptive", lib().crd_ensemble_last_error(self._h).decode())
+        out = []
+        for k in range(self.n_members):
+            d = {f: getattr(st[k], f) for f, _ in st[k]._fields_}
+            d["status"] = status[k]
+            out.append(d)
+        return out
+
+    def last_error(self):
+        return lib().crd_ensemble_last_error(self._h).decode()
+
 
 class PinnedArray:
     """A numpy array over page-locked host memory from crd_host_alloc (freed with the object)."""

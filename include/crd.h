@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define CRD_ABI_VERSION 7
+#define CRD_ABI_VERSION 8
 
 typedef enum crd_status {
 	CRD_OK = 0,
@@ -518,9 +518,10 @@ int crd_state_max_abs(crd_ctx *ctx, double *out);
  * each with its own ARKode stepping loop.  On the reference's own small grids (data/FHNmodelArgs.ini: 400 x 1600) one problem's step
  * is bound by the launch, not by the device; B members share that launch.  Members must agree on model, surface, nx, the derived ny,
  * surface length and width, precision and justDiffusion; they may differ in diffusion, beta, betaMin, betaMax, varyBeta and
- * tBoundary.  Fixed-step classical RK4 only, on one device; every member's result is bit-identical to a context (crd_create) of the
- * same parameters stepped alone with crd_step_rk4 and the one-launch stepper.  Not thread-safe; calls on one ensemble must be
- * serialised.
+ * tBoundary.  One device.  Fixed-step classical RK4 (crd_ensemble_step_rk4): every member's result is bit-identical to a context
+ * (crd_create) of the same parameters stepped alone with crd_step_rk4 and the one-launch stepper.  Error-controlled integration
+ * (crd_ensemble_integrate_adaptive): every member takes its own step sequence, as a context of its parameters integrated alone with
+ * crd_integrate_adaptive would.  Not thread-safe; calls on one ensemble must be serialised.
  * --------------------------------------------------------------------------------------------------------- */
 typedef struct crd_ensemble crd_ensemble;
 /* members[0 .. n_members): the members' parameters.  Refusals come before any HIP call: CRD_EINVAL for n_members < 1, invalid
@@ -546,6 +547,25 @@ int crd_ensemble_synchronize(crd_ensemble *e);
 /* max |var0| of every member, per_member[0 .. n_members) (non-finite for a member that blew up; synchronises).  The blow-up guard of
  * each member's run (its ARKode call's failure, src/FHNmodel_torus.cpp:424-435). */
 int crd_ensemble_max_abs(crd_ensemble *e, double *per_member);
+/* Error-controlled integration of EVERY member from t0 to tout: member k integrates exactly as crd_integrate_adaptive would on a lone
+ * single-slab context of member k's parameters and state -- CRD_ADAPT_ARKODE with ARK_NORMAL dense output, arkHin on a fresh state,
+ * the PID controller and its safeguards, the 7-failure limit, max_steps and the step-size underflow check -- with its own step size,
+ * accept / reject sequence, controller memory and stats.  With h_max = 0 each member is capped at its own crd_stable_dt.  Replaces
+ * the members' ARKode(..., tout, ..., ARK_NORMAL) calls (src/FHNmodel_torus.cpp:423), one per member.
+ *   Rounds: one launch runs one attempt of every member still short of tout, one wait brings back all their error norms, and each
+ *   member's controller decides on its own.  A member's error norm is summed over the ensemble's fixed partition of work items (planned
+ *   at the first call from the member count), not a context's: its step sizes agree with a lone context's to rounding (~1e-15), and a
+ *   member's result does not depend on the other members or on when they finish.  Repeated calls are bit-identical.
+ *   Resume: member k continues from its internal state when t0 is the tout its previous call handed back and nothing has replaced its
+ *   state since; crd_ensemble_upload(e, k, ...) ends member k's carry-over only, crd_ensemble_step_rk4 every member's.
+ *   Failures stay per member: a member that fails the error test 7 times on one step, takes max_steps steps or underflows its step
+ *   size stops alone (status[k] = CRD_ESTATE; its state is left where crd_integrate_adaptive leaves a context), the others reach tout,
+ *   and the call returns CRD_ESTATE with crd_ensemble_last_error naming the failed members.
+ * stats and status: n_members entries each, or NULL.  CRD_EINVAL, before any device work, for CRD_ADAPT_RK43 and every option or
+ * interval crd_integrate_adaptive refuses.  The first call allocates three more state buffers per member (the dense output's y_n,
+ * y_{n+1} / f_n, f_{n+1} / interpolant), kept for later calls; an ensemble that only takes fixed steps never does.  Synchronous. */
+int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, const crd_adaptive_options *opt,
+                                    crd_adaptive_stats *stats, int32_t *status);
 
 #ifdef __cplusplus
 }
