@@ -112,6 +112,16 @@ class StepTiming(C.Structure):
                 ("agreement_restarts", C.c_int64)]
 
 
+OBSERVE_MAX_PROBES = 16  # CRD_OBSERVE_MAX_PROBES
+
+
+class ObserveOptions(C.Structure):
+    """crd_observe_options"""
+
+    _fields_ = [("stride", C.c_int64), ("n_probes", C.c_int32), ("maps", C.c_int32), ("probe_i", C.c_int32 * OBSERVE_MAX_PROBES),
+                ("probe_j", C.c_int32 * OBSERVE_MAX_PROBES), ("threshold", C.c_double)]
+
+
 # name -> (restype, argtypes); the test suite checks this table against include/crd.h symbol by symbol.
 _vp = C.c_void_p
 _SIGNATURES = {
@@ -201,6 +211,13 @@ _SIGNATURES = {
     "crd_ensemble_max_abs": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "crd_ensemble_integrate_adaptive": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(AdaptiveOptions), C.POINTER(AdaptiveStats),
                                                   C.POINTER(C.c_int32)]),
+    "crd_ensemble_observe_begin": (C.c_int, [_vp, C.POINTER(ObserveOptions), C.c_int64]),
+    "crd_ensemble_observe_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "crd_ensemble_observe_read": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "crd_ensemble_observe_maps": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "crd_ensemble_observe_info": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(ObserveOptions), C.POINTER(C.c_int64)]),
+    "crd_ensemble_observe_end": (C.c_int, [_vp]),
+    "crd_state_observe": (C.c_int, [_vp, C.POINTER(C.c_double)]),
 }
 
 _lib = None

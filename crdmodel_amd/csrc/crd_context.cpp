@@ -9,6 +9,7 @@
 #include <new>
 
 #include "crd_ctx.h"
+#include "crd_ensemble.h"
 #include "crd_tuning.h"
 
 namespace crd {
@@ -807,6 +808,33 @@ int crd_state_max_abs(crd_ctx *c, double *out)
 	if (sink != c->scalar_host) HIP_TRY(c, hipMemcpyAsync(c->scalar_host, sink, sizeof(double), hipMemcpyDeviceToHost, c->compute));
 	HIP_TRY(c, hipStreamSynchronize(c->compute));
 	*out = c->scalar_host[0];
+	return CRD_OK;
+}
+
+int crd_state_observe(crd_ctx *c, double stats[8])
+{
+	if (!c || !stats) return CRD_EINVAL;
+	if (c->n_slabs != 1) return fail(c, CRD_EINVAL, "crd_state_observe takes a single-slab context: this one is slab " + std::to_string(c->slab) + " of " + std::to_string(c->n_slabs));
+	if (int rc = set_device(c)) return rc;
+	// a one-entry descriptor over the owned rows (as launch_max_abs addresses them), the partial records and the row, in one block
+	const size_t n = (size_t)c->nx * (size_t)c->nyl;
+	const int blocks = observe_blocks(n);
+	EnsembleMember m{};
+	const size_t first_row = (size_t)kGhost * (size_t)c->nx * c->real_size;  // bytes from a plane's base to its row 0
+	m.u[0] = static_cast<char *>(c->plane[crd_ctx::Y][0]) + first_row;
+	m.v[0] = static_cast<char *>(c->plane[crd_ctx::Y][1]) + first_row;
+	static_assert(sizeof(EnsembleMember) % sizeof(double) == 0, "the doubles behind the descriptor are aligned");
+	char *block = nullptr;
+	HIP_TRY(c, hipMalloc((void **)&block, sizeof m + ((size_t)blocks * 8 + 8) * sizeof(double)));
+	double *const partials = reinterpret_cast<double *>(block + sizeof m), *const row = partials + (size_t)blocks * 8;
+	ObserveProbes none{};
+	hipError_t r = hipMemcpyAsync(block, &m, sizeof m, hipMemcpyHostToDevice, c->compute);
+	if (r == hipSuccess) r = launch_observe_sample(c->p.precision, reinterpret_cast<EnsembleMember *>(block), 1, 0, n, partials, nullptr, 0, 0.0, 0.0, c->compute);
+	if (r == hipSuccess) r = launch_observe_finish(c->p.precision, reinterpret_cast<EnsembleMember *>(block), 1, 0, n, partials, none, c->nx, row, 8, c->compute);
+	if (r == hipSuccess) r = hipMemcpyAsync(stats, row, 8 * sizeof(double), hipMemcpyDeviceToHost, c->compute);
+	if (r == hipSuccess) r = hipStreamSynchronize(c->compute);
+	(void)hipFree(block);
+	if (r != hipSuccess) return fail(c, CRD_EHIP, std::string("crd_state_observe: ") + hipGetErrorString(r));
 	return CRD_OK;
 }
 

@@ -50,6 +50,21 @@ struct crd_ensemble {
 	EnsembleAttempt *att_dev = nullptr, *att_host = nullptr;  // n entries each; att_host page-locked
 	EnsembleOp *ops_dev = nullptr, *ops_host = nullptr;  // kOpSets x n entries each; ops_host page-locked
 	static constexpr int kOpSets = 3;          // batched launches enqueued between two waits, each with an operand set of its own
+
+	// Observer (crd_ensemble_observe_*): empty unless one is open.
+	struct Observer {
+		bool open = false;
+		crd_observe_options opt{};
+		ObserveProbes probes{};
+		int64_t capacity = 0, count = 0;       // samples: room, recorded (enqueued)
+		int64_t steps = 0;                     // fixed steps taken since begin (the stride's count, carried over calls)
+		int blocks = 0, row_doubles = 0;       // sampling blocks per member; doubles per member and sample: 8 + 2 n_probes
+		size_t map_plane = 0;                  // doubles per map plane (nx * ny, rounded up to an even count: 16-byte planes)
+		double *records = nullptr;             // capacity x n x row_doubles
+		double *partials = nullptr;            // n x blocks x 8
+		double *maps = nullptr;                // n x 3 x map_plane (minimum, maximum, activation time), or null
+		std::vector<double> t;                 // the samples' times
+	} obs;
 };
 
 namespace {
@@ -87,6 +102,27 @@ const char *disagreement(const crd_params &a, const crd_grid &ga, const crd_para
 int check_member(crd_ensemble *e, int member)
 {
 	if (member < 0 || member >= e->n) return efail(e, CRD_EINVAL, "member index out of range");
+	return CRD_OK;
+}
+
+void observer_release(crd_ensemble *e)
+{
+	for (void *q : {(void *)e->obs.records, (void *)e->obs.partials, (void *)e->obs.maps})
+		if (q) (void)hipFree(q);
+	e->obs = crd_ensemble::Observer{};
+}
+
+// One sample of every member's current state at time t, behind whatever the stream holds: the sampling pass, then the finishing
+// launch into the sample's rows.  The caller has checked that there is room.
+int observer_sample(crd_ensemble *e, double t)
+{
+	crd_ensemble::Observer &ob = e->obs;
+	const size_t n = (size_t)e->nx * (size_t)e->ny;
+	double *const row = ob.records + (size_t)ob.count * (size_t)e->n * (size_t)ob.row_doubles;
+	ENS_TRY(e, launch_observe_sample(e->precision, e->table, e->n, e->cur, n, ob.partials, ob.maps, ob.map_plane, ob.opt.threshold, t, e->stream));
+	ENS_TRY(e, launch_observe_finish(e->precision, e->table, e->n, e->cur, n, ob.partials, ob.probes, e->nx, row, ob.row_doubles, e->stream));
+	ob.t.push_back(t);
+	ob.count++;
 	return CRD_OK;
 }
 
@@ -198,6 +234,7 @@ void crd_ensemble_destroy(crd_ensemble *e)
 	if (!e) return;
 	(void)hipSetDevice(e->device);
 	if (e->stream) (void)hipStreamSynchronize(e->stream);
+	observer_release(e);
 	for (void *q : e->allocs) (void)hipFree(q);
 	if (e->table) (void)hipFree(e->table);
 	if (e->max_host) (void)hipHostFree(e->max_host);
@@ -255,6 +292,12 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 {
 	if (!e) return CRD_EINVAL;
 	if (nsteps < 0 || !(dt > 0.0) || !std::isfinite(t0)) return efail(e, CRD_EINVAL, "bad t0 / dt / nsteps");
+	crd_ensemble::Observer &ob = e->obs;
+	if (ob.open) {  // a call that would overrun the record buffer is refused whole
+		const int64_t stride = ob.opt.stride, samples = (ob.steps + nsteps) / stride - ob.steps / stride;
+		if (samples > ob.capacity - ob.count)
+			return efail(e, CRD_EINVAL, "the observer has room for " + std::to_string(ob.capacity - ob.count) + " more samples; this call would record " + std::to_string(samples));
+	}
 	TraceRange range("crd_ensemble_step_rk4");
 	for (auto &a : e->adapt) a.dense.pending = a.ark.live = false;  // stepping on from the states handed back (run_steps)
 	ENS_TRY(e, hipSetDevice(e->device));
@@ -287,6 +330,8 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 		st.src = e->cur;
 		ENS_TRY(e, launch_ensemble_step(e->precision, e->model, e->plan.cols, absorb && e->model != dev::kModelDiffusionOnly, e->table, st, e->stream));
 		e->cur = 1 - e->cur;
+		if (ob.open && ++ob.steps % ob.opt.stride == 0)
+			if (int rc = observer_sample(e, t0 + (double)(s + 1) * dt)) return rc;  // the time as the next step's t is formed
 	}
 	return CRD_OK;
 }
@@ -438,6 +483,7 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 	if (opt) o = *opt;
 	if (!arkode::options_valid(o, t0, tout)) return efail(e, CRD_EINVAL, "bad adaptive options / time interval");
 	if (o.method != CRD_ADAPT_ARKODE) return efail(e, CRD_EINVAL, "an ensemble integrates with CRD_ADAPT_ARKODE only");
+	if (e->obs.open && e->obs.count >= e->obs.capacity) return efail(e, CRD_EINVAL, "the observer has no room for this call's sample");
 	const int B = e->n;
 	// Which members resume (a context's rule, per member: t0 is the output time its previous call handed back, and nothing has replaced
 	// its state since), and -- before any device work -- whether a fresh member's first-step estimate can be made at all.
@@ -714,8 +760,134 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 		m.v[1 - e->cur] = static_cast<char *>(a.role[kSA]) + plane;
 	}
 	ENS_TRY(e, hipMemcpyAsync(e->table, e->members.data(), (size_t)B * sizeof(EnsembleMember), hipMemcpyHostToDevice, e->stream));
+	if (e->obs.open) {
+		// one sample per call, of the states handed back; a member that failed gets a row of NaNs (every byte 0xff is one)
+		double *const row = e->obs.records + (size_t)e->obs.count * (size_t)B * (size_t)e->obs.row_doubles;
+		if (int orc = observer_sample(e, tout)) return orc;
+		for (int k = 0; k < B; k++)
+			if (run[(size_t)k].failed)
+				ENS_TRY(e, hipMemsetAsync(row + (size_t)k * (size_t)e->obs.row_doubles, 0xff, (size_t)e->obs.row_doubles * sizeof(double), e->stream));
+	}
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	if (rc != CRD_OK) return efail(e, rc, "adaptive integration failed for " + failures);
+	return CRD_OK;
+}
+
+}  // extern "C"
+
+// ---- observers ----
+
+extern "C" {
+
+int crd_ensemble_observe_begin(crd_ensemble *e, const crd_observe_options *opt, int64_t capacity)
+{
+	if (!e) return CRD_EINVAL;
+	if (!opt) return efail(e, CRD_EINVAL, "null observer options");
+	if (e->obs.open) return efail(e, CRD_EINVAL, "an observer is already open (crd_ensemble_observe_end closes it)");
+	if (opt->stride < 1) return efail(e, CRD_EINVAL, "observer stride must be at least 1 (got " + std::to_string(opt->stride) + ")");
+	if (capacity < 1) return efail(e, CRD_EINVAL, "observer capacity must be at least 1 sample (got " + std::to_string(capacity) + ")");
+	if (opt->n_probes < 0 || opt->n_probes > CRD_OBSERVE_MAX_PROBES)
+		return efail(e, CRD_EINVAL, "an observer takes 0 .. " + std::to_string(CRD_OBSERVE_MAX_PROBES) + " probes (got " + std::to_string(opt->n_probes) + ")");
+	for (int q = 0; q < opt->n_probes; q++)
+		if (opt->probe_i[q] < 0 || opt->probe_i[q] >= e->nx || opt->probe_j[q] < 0 || opt->probe_j[q] >= e->ny)
+			return efail(e, CRD_EINVAL, "probe " + std::to_string(q) + " (i = " + std::to_string(opt->probe_i[q]) + ", j = " + std::to_string(opt->probe_j[q]) +
+			                                ") is outside the " + std::to_string(e->nx) + " x " + std::to_string(e->ny) + " grid");
+	if (opt->maps != 0 && opt->maps != 1) return efail(e, CRD_EINVAL, "observer maps is 0 or 1");
+	if (opt->maps && !std::isfinite(opt->threshold)) return efail(e, CRD_EINVAL, "observer maps need a finite threshold");
+	static_assert(CRD_OBSERVE_MAX_PROBES == kObserveMaxProbes, "the header's probe limit is the kernels'");
+	const size_t n = (size_t)e->nx * (size_t)e->ny, B = (size_t)e->n;
+	crd_ensemble::Observer ob;
+	ob.opt = *opt;
+	ob.probes.n = opt->n_probes;
+	for (int q = 0; q < opt->n_probes; q++) {
+		ob.probes.i[q] = opt->probe_i[q];
+		ob.probes.j[q] = opt->probe_j[q];
+	}
+	ob.capacity = capacity;
+	ob.blocks = observe_blocks(n);
+	ob.row_doubles = 8 + 2 * opt->n_probes;
+	ob.map_plane = (n + 1) & ~(size_t)1;
+	if ((double)capacity * (double)B * (double)ob.row_doubles * 8.0 > 0x1p46) return efail(e, CRD_EINVAL, "observer capacity too large");
+	TraceRange range("crd_ensemble_observe_begin");
+	ENS_TRY(e, hipSetDevice(e->device));
+	e->obs = ob;  // (observer_release frees whatever a failed allocation leaves behind)
+	auto fail = [&](hipError_t r, const char *what) {
+		observer_release(e);
+		return efail(e, r == hipErrorOutOfMemory ? CRD_ENOMEM : CRD_EHIP, std::string(what) + ": " + hipGetErrorString(r));
+	};
+	if (hipError_t r = hipMalloc((void **)&e->obs.records, (size_t)capacity * B * (size_t)ob.row_doubles * sizeof(double)); r != hipSuccess) return fail(r, "hipMalloc(records)");
+	if (hipError_t r = hipMalloc((void **)&e->obs.partials, B * (size_t)ob.blocks * 8 * sizeof(double)); r != hipSuccess) return fail(r, "hipMalloc(partials)");
+	if (opt->maps) {
+		if (hipError_t r = hipMalloc((void **)&e->obs.maps, B * 3 * ob.map_plane * sizeof(double)); r != hipSuccess) return fail(r, "hipMalloc(maps)");
+		for (size_t k = 0; k < B; k++) {
+			const double init[3] = {INFINITY, -INFINITY, NAN};
+			for (int q = 0; q < 3; q++)
+				if (hipError_t r = launch_observe_fill(e->obs.maps + (k * 3 + (size_t)q) * ob.map_plane, ob.map_plane, init[q], e->stream); r != hipSuccess)
+					return fail(r, "map initialisation");
+		}
+	}
+	e->obs.open = true;
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_count(const crd_ensemble *e, int64_t *n_samples)
+{
+	if (!e || !n_samples || !e->obs.open) return CRD_EINVAL;
+	*n_samples = e->obs.count;
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_info(const crd_ensemble *e, int32_t *blocks_per_member, int64_t *values_per_field, crd_observe_options *opt, int64_t *capacity)
+{
+	if (!e || !e->obs.open) return CRD_EINVAL;
+	if (blocks_per_member) *blocks_per_member = e->obs.blocks;
+	if (values_per_field) *values_per_field = (int64_t)e->nx * (int64_t)e->ny;
+	if (opt) *opt = e->obs.opt;
+	if (capacity) *capacity = e->obs.capacity;
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_read(crd_ensemble *e, int64_t first, int64_t count, double *t, double *stats, double *probes)
+{
+	if (!e) return CRD_EINVAL;
+	const crd_ensemble::Observer &ob = e->obs;
+	if (!ob.open) return efail(e, CRD_EINVAL, "no observer is open");
+	if (first < 0 || count < 0 || first > ob.count || count > ob.count - first) return efail(e, CRD_EINVAL, "sample range outside the " + std::to_string(ob.count) + " recorded");
+	TraceRange range("crd_ensemble_observe_read");
+	ENS_TRY(e, hipSetDevice(e->device));
+	const size_t B = (size_t)e->n, R = (size_t)ob.row_doubles, P = (size_t)ob.probes.n, rows = (size_t)count * B;
+	std::vector<double> host(rows * R);
+	if (rows) ENS_TRY(e, hipMemcpyAsync(host.data(), ob.records + (size_t)first * B * R, rows * R * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	ENS_TRY(e, hipStreamSynchronize(e->stream));
+	for (size_t r = 0; r < rows; r++) {
+		if (stats) std::copy(host.begin() + (ptrdiff_t)(r * R), host.begin() + (ptrdiff_t)(r * R + 8), stats + r * 8);
+		if (probes) std::copy(host.begin() + (ptrdiff_t)(r * R + 8), host.begin() + (ptrdiff_t)(r * R + R), probes + r * 2 * P);
+	}
+	if (t) std::copy(ob.t.begin() + (ptrdiff_t)first, ob.t.begin() + (ptrdiff_t)(first + count), t);
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_maps(crd_ensemble *e, int member, double *min_u, double *max_u, double *t_act)
+{
+	if (!e) return CRD_EINVAL;
+	if (!e->obs.open || !e->obs.maps) return efail(e, CRD_EINVAL, "no observer with maps is open");
+	if (int rc = check_member(e, member)) return rc;
+	ENS_TRY(e, hipSetDevice(e->device));
+	const size_t n = (size_t)e->nx * (size_t)e->ny;
+	double *const out[3] = {min_u, max_u, t_act};
+	for (int q = 0; q < 3; q++)
+		if (out[q]) ENS_TRY(e, hipMemcpyAsync(out[q], e->obs.maps + ((size_t)member * 3 + (size_t)q) * e->obs.map_plane, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	ENS_TRY(e, hipStreamSynchronize(e->stream));
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_end(crd_ensemble *e)
+{
+	if (!e) return CRD_EINVAL;
+	if (!e->obs.open) return efail(e, CRD_EINVAL, "no observer is open");
+	ENS_TRY(e, hipSetDevice(e->device));
+	ENS_TRY(e, hipStreamSynchronize(e->stream));
+	observer_release(e);
 	return CRD_OK;
 }
 

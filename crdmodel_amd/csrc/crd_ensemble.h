@@ -110,4 +110,29 @@ constexpr int kEnsembleNormBlocks = 256;
 // fp32 (in the kernels' unit, under its floating-point contraction setting).
 void ensemble_hermite_coefficients(double theta, double h, double c[4], float cf[4]);  // blocks per member of the ydd norm (crd_kernels.hip: kNormBlocks); partials_dev: count x that
 
+
+// ---- observers (crd_observe.hip; crd_ensemble.cpp: crd_ensemble_observe_*, crd_context.cpp: crd_state_observe) ----
+
+constexpr int kObserveMaxProbes = 16;           // CRD_OBSERVE_MAX_PROBES
+constexpr int kObserveMaxBlocks = 256;          // sampling blocks per member, at most
+constexpr size_t kObservePointsPerBlock = 4096; // ... one per this many points of a plane: 16 points per lane of 256
+// The probes' grid points, the same for every member: a kernel argument of the finishing launch.
+struct ObserveProbes {
+	int n;
+	int i[kObserveMaxProbes], j[kObserveMaxProbes];
+};
+// Sampling blocks per member, G: a function of the plane's size alone -- never of the member count -- so a member's partition, and
+// with it every bit of its row, is the same in any ensemble.
+int observe_blocks(size_t n);
+// Sampling: the partial records of buffer `src` of every member, n = nx * ny points per field, into partials_dev[members x G x 8]
+// (min, max, sum, sum of squares of u, then of v).  maps_dev non-null: also fold u into member k's three planes at
+// maps_dev + 3 k map_plane (running minimum, running maximum, time of the first sample with u >= threshold -- set to t where it is
+// still NaN), each of map_plane >= n doubles.
+hipError_t launch_observe_sample(int precision, const EnsembleMember *table, int members, int src, size_t n, double *partials_dev, double *maps_dev, size_t map_plane,
+                                 double threshold, double t, hipStream_t s);
+// Finishing: member k's G partials added in index order into row_dev[k * row_doubles .. + 8), the probes' (u, v) behind them.
+hipError_t launch_observe_finish(int precision, const EnsembleMember *table, int members, int src, size_t n, const double *partials_dev, const ObserveProbes &probes, int nx,
+                                 double *row_dev, int row_doubles, hipStream_t s);
+hipError_t launch_observe_fill(double *x, size_t n, double value, hipStream_t s);
+
 }  // namespace crd

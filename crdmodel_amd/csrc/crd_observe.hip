@@ -1,0 +1,229 @@
+// crd_observe.hip -- observers: per-member statistics, probes and maps of an ensemble's current state, recorded on the device
+// (crd_ensemble.cpp drives them; crd_state_observe runs the same sampling kernel on a single-slab context).  Two launches per sample:
+//   sampling   grid (G blocks per member, B members): a block strides over its member's two planes and writes ONE partial record
+//              (min, max, sum, sum of squares of each field, in fp64 whatever the state's precision); with maps on, the same pass
+//              folds the activator it has just read into the member's three map planes;
+//   finishing  one workgroup per member: adds the member's G partials in index order into the sample's row of the record buffer and
+//              gathers the probe values into the same row.
+// No floating-point atomics and no "last block" ticket: which lane takes which point, and the order of every addition, depend on
+// the plane's size alone -- not on the member count, not on the alignment of the planes (the 16-byte and the element-wise loads
+// serve the same points to the same lanes) -- so a row is the same bits from run to run, in an ensemble of 1 and of 64, and from
+// crd_state_observe.  Reads the state and nothing else of the stepping: the step kernels do not know observers exist.
+// DESIGN.md, "Ensembles" (observers).
+#include "crd_device.h"
+#include "crd_ensemble.h"
+
+namespace crd {
+
+using dev::clear_launch_status;
+using dev::launch_status;
+
+namespace {
+
+typedef const __attribute__((address_space(4))) EnsembleMember ConstMember;
+
+constexpr int kObserveThreads = 256;
+
+template <typename Real> struct Wide;
+template <> struct Wide<double> { using type = double2; static constexpr int n = 2; };
+template <> struct Wide<float> { using type = float4; static constexpr int n = 4; };
+
+// NaN propagates through both (the rule of crd_max_abs_kernel): once an operand is NaN the result is, whichever side it is on.
+__device__ __forceinline__ double nan_min(double m, double x) { return (x < m || x != x) ? x : m; }
+__device__ __forceinline__ double nan_max(double m, double x) { return (x > m || x != x) ? x : m; }
+
+// One field's statistics in a lane: V interleaved accumulators (element e of every 16-byte group goes to accumulator e), so that a
+// point passes through at most ceil(points / (V lanes G)) - 1 additions here and log2 V in fold().
+template <int V>
+struct FieldStats {
+	double mn, mx, s[V], q[V];
+	__device__ __forceinline__ void clear()
+	{
+		mn = INFINITY;
+		mx = -INFINITY;
+		for (int e = 0; e < V; e++) s[e] = q[e] = 0.0;
+	}
+	__device__ __forceinline__ void take(int e, double x)
+	{
+		mn = nan_min(mn, x);
+		mx = nan_max(mx, x);
+		s[e] += x;
+		q[e] = fma(x, x, q[e]);
+	}
+	__device__ __forceinline__ void fold()  // pairwise: (0 + 1) + (2 + 3)
+	{
+		for (int w = 1; w < V; w *= 2)
+			for (int e = 0; e + w < V; e += 2 * w) {
+				s[e] += s[e + w];
+				q[e] += q[e + w];
+			}
+	}
+};
+
+// Running minimum / maximum of the activator (np.minimum / np.maximum: NaN propagates) and the time of the first sample at which
+// it is >= threshold.  A plane entry is rewritten only when it changes.
+__device__ __forceinline__ void map_update(double *__restrict__ mmin, double *__restrict__ mmax, double *__restrict__ tact, size_t p, double x, double threshold,
+                                           double t)
+{
+	const double lo = mmin[p], hi = mmax[p], ta = tact[p];
+	if (x < lo || x != x) mmin[p] = x;
+	if (x > hi || x != x) mmax[p] = x;
+	if (ta != ta && x >= threshold) tact[p] = t;
+}
+
+// grid (G, members), kObserveThreads lanes.  Group c of V consecutive points belongs to lane (c mod 256) of block ((c / 256) mod G);
+// partial record of (member, block): min u, max u, sum u, sum u^2, then v's four.
+template <typename Real, bool MAPS>
+__global__ void __launch_bounds__(kObserveThreads) crd_observe_sample_kernel(const EnsembleMember *members, int src, size_t n, double *__restrict__ partials,
+                                                                             double *__restrict__ maps, size_t map_plane, double threshold, double t)
+{
+	constexpr int V = Wide<Real>::n;
+	using Vec = typename Wide<Real>::type;
+	__shared__ double part[kObserveThreads / 64][8];
+	const int member = blockIdx.y;
+	ConstMember *const mem = (ConstMember *)members + member;
+	const Real *__restrict__ const u = static_cast<const Real *>(mem->u[src]);
+	const Real *__restrict__ const v = static_cast<const Real *>(mem->v[src]);
+	double *const mmin = MAPS ? maps + (size_t)member * 3 * map_plane : nullptr;
+	double *const mmax = MAPS ? mmin + map_plane : nullptr;
+	double *const tact = MAPS ? mmax + map_plane : nullptr;
+	// 16 bytes per lane and load where both of this member's planes allow it (decided per block; the result does not depend on it)
+	const bool wide = (((uintptr_t)u | (uintptr_t)v) & 15) == 0;
+	const size_t groups = (n + V - 1) / V, stride = (size_t)gridDim.x * kObserveThreads;
+
+	FieldStats<V> a, b;
+	a.clear();
+	b.clear();
+	// a lane takes its groups in rising order whichever loop serves them
+	auto take_group = [&](size_t p0, const Real *xu, const Real *xv, int count) {
+		for (int e = 0; e < V; e++)
+			if (e < count) {
+				a.take(e, (double)xu[e]);
+				b.take(e, (double)xv[e]);
+				if constexpr (MAPS) map_update(mmin, mmax, tact, p0 + e, (double)xu[e], threshold, t);
+			}
+	};
+	size_t c = (size_t)blockIdx.x * kObserveThreads + threadIdx.x;
+	if (wide) {
+		const size_t full = n / V;  // groups that lie wholly inside the plane
+		constexpr int kAhead = 8 / V;  // 16-byte loads in flight per lane and field: 4 in fp64, 2 in fp32
+		for (; c + (kAhead - 1) * stride < full; c += kAhead * stride) {
+			Vec wu[kAhead], wv[kAhead];
+			for (int i = 0; i < kAhead; i++) {
+				wu[i] = *reinterpret_cast<const Vec *>(u + (c + i * stride) * V);
+				wv[i] = *reinterpret_cast<const Vec *>(v + (c + i * stride) * V);
+			}
+			for (int i = 0; i < kAhead; i++) take_group((c + i * stride) * V, reinterpret_cast<const Real *>(&wu[i]), reinterpret_cast<const Real *>(&wv[i]), V);
+		}
+		for (; c < full; c += stride) {
+			const Vec wu = *reinterpret_cast<const Vec *>(u + c * V), wv = *reinterpret_cast<const Vec *>(v + c * V);
+			take_group(c * V, reinterpret_cast<const Real *>(&wu), reinterpret_cast<const Real *>(&wv), V);
+		}
+	}
+	for (; c < groups; c += stride) {  // planes that do not sit on 16 bytes, and the last, short group of any plane
+		const size_t p0 = c * V;
+		const int count = p0 + V <= n ? V : (int)(n - p0);
+		Real xu[V] = {}, xv[V] = {};
+		for (int e = 0; e < V; e++)
+			if (e < count) {
+				xu[e] = u[p0 + e];
+				xv[e] = v[p0 + e];
+			}
+		take_group(p0, xu, xv, count);
+	}
+	a.fold();
+	b.fold();
+	double r[8] = {a.mn, a.mx, a.s[0], a.q[0], b.mn, b.mx, b.s[0], b.q[0]};
+	for (int off = 32; off > 0; off >>= 1)
+		for (int k = 0; k < 8; k++) {
+			const double o = __shfl_down(r[k], off, 64);
+			r[k] = (k & 3) == 0 ? nan_min(r[k], o) : (k & 3) == 1 ? nan_max(r[k], o) : r[k] + o;
+		}
+	if ((threadIdx.x & 63) == 0)
+		for (int k = 0; k < 8; k++) part[threadIdx.x >> 6][k] = r[k];
+	__syncthreads();
+	if (threadIdx.x < 8) {
+		const int k = threadIdx.x;
+		const double w0 = part[0][k], w1 = part[1][k], w2 = part[2][k], w3 = part[3][k];  // pairwise: (0 + 1) + (2 + 3)
+		const double out = (k & 3) == 0 ? nan_min(nan_min(w0, w1), nan_min(w2, w3)) : (k & 3) == 1 ? nan_max(nan_max(w0, w1), nan_max(w2, w3)) : (w0 + w1) + (w2 + w3);
+		partials[((size_t)member * gridDim.x + blockIdx.x) * 8 + k] = out;
+	}
+}
+
+// One workgroup per member.  row: the sample's rows, member k's at row + k * row_doubles: the eight statistics, then (u, v) of each probe.
+template <typename Real>
+__global__ void __launch_bounds__(64) crd_observe_finish_kernel(const EnsembleMember *members, int src, const double *__restrict__ partials, int blocks, ObserveProbes pr,
+                                                                int nx, double *__restrict__ row, int row_doubles)
+{
+	const int member = blockIdx.x, k = threadIdx.x;
+	double *const out = row + (size_t)member * row_doubles;
+	if (k < 8) {
+		const double *const p = partials + (size_t)member * blocks * 8 + k;
+		auto fold = [&](double r, double o) { return (k & 3) == 0 ? nan_min(r, o) : (k & 3) == 1 ? nan_max(r, o) : r + o; };
+		double r = p[0];
+		int g = 1;
+		for (; g + 8 <= blocks; g += 8) {  // index order; eight loads in flight, then their additions
+			double o[8];
+			for (int i = 0; i < 8; i++) o[i] = p[(size_t)(g + i) * 8];
+			for (int i = 0; i < 8; i++) r = fold(r, o[i]);
+		}
+		for (; g < blocks; g++) r = fold(r, p[(size_t)g * 8]);
+		out[k] = r;
+	} else if (k < 8 + 2 * pr.n) {
+		ConstMember *const mem = (ConstMember *)members + member;
+		const int q = (k - 8) >> 1;
+		const Real *const plane = static_cast<const Real *>((k & 1) ? mem->v[src] : mem->u[src]);
+		out[k] = (double)plane[(size_t)pr.j[q] * nx + pr.i[q]];
+	}
+}
+
+__global__ void __launch_bounds__(256) crd_observe_fill_kernel(double *__restrict__ x, size_t n, double value)
+{
+	for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) x[q] = value;
+}
+
+}  // namespace
+
+int observe_blocks(size_t n)
+{
+	const size_t g = (n + kObservePointsPerBlock - 1) / kObservePointsPerBlock;
+	return (int)(g < 1 ? 1 : g > (size_t)kObserveMaxBlocks ? (size_t)kObserveMaxBlocks : g);
+}
+
+hipError_t launch_observe_sample(int precision, const EnsembleMember *table, int members, int src, size_t n, double *partials_dev, double *maps_dev, size_t map_plane,
+                                 double threshold, double t, hipStream_t s)
+{
+	clear_launch_status();
+	if (members < 1 || n == 0) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)observe_blocks(n), (unsigned)members);
+	if (precision == CRD_PRECISION_F64) {
+		if (maps_dev) crd_observe_sample_kernel<double, true><<<grid, kObserveThreads, 0, s>>>(table, src, n, partials_dev, maps_dev, map_plane, threshold, t);
+		else crd_observe_sample_kernel<double, false><<<grid, kObserveThreads, 0, s>>>(table, src, n, partials_dev, nullptr, 0, threshold, t);
+	} else {
+		if (maps_dev) crd_observe_sample_kernel<float, true><<<grid, kObserveThreads, 0, s>>>(table, src, n, partials_dev, maps_dev, map_plane, threshold, t);
+		else crd_observe_sample_kernel<float, false><<<grid, kObserveThreads, 0, s>>>(table, src, n, partials_dev, nullptr, 0, threshold, t);
+	}
+	return launch_status();
+}
+
+hipError_t launch_observe_finish(int precision, const EnsembleMember *table, int members, int src, size_t n, const double *partials_dev, const ObserveProbes &probes, int nx,
+                                 double *row_dev, int row_doubles, hipStream_t s)
+{
+	clear_launch_status();
+	if (members < 1 || probes.n < 0 || probes.n > kObserveMaxProbes || row_doubles < 8 + 2 * probes.n) return hipErrorInvalidValue;
+	const int blocks = observe_blocks(n);
+	if (precision == CRD_PRECISION_F64) crd_observe_finish_kernel<double><<<members, 64, 0, s>>>(table, src, partials_dev, blocks, probes, nx, row_dev, row_doubles);
+	else crd_observe_finish_kernel<float><<<members, 64, 0, s>>>(table, src, partials_dev, blocks, probes, nx, row_dev, row_doubles);
+	return launch_status();
+}
+
+hipError_t launch_observe_fill(double *x, size_t n, double value, hipStream_t s)
+{
+	clear_launch_status();
+	if (n == 0) return hipSuccess;
+	const size_t g = (n + 255) / 256;
+	crd_observe_fill_kernel<<<(int)(g < 2048 ? g : 2048), 256, 0, s>>>(x, n, value);
+	return launch_status();
+}
+
+}  // namespace crd

@@ -41,6 +41,11 @@ struct Options {
 	bool decomp_mpi = false;
 	// --ensemble KEY=v1,v2,...: members that differ in one or more parameters, zipped over the lists (run_ensemble)
 	std::vector<std::pair<std::string, std::vector<double>>> ensemble;
+	// --observe STRIDE [--probe i,j]... [--observe-maps THRESHOLD]: the ensemble's observer (crd_ensemble_observe_*)
+	bool observe = false, observe_maps = false;
+	long long observe_stride = 0;
+	double observe_threshold = 0.0;
+	std::vector<std::pair<long long, long long>> probes;
 };
 
 [[noreturn]] void usage(const char *argv0, bool alias)
@@ -52,8 +57,12 @@ struct Options {
 		          << " --model fhn|goldbeter --surface torus|flat [--gpus G] [--devices D] [--dt DT] [--stepper auto|staged|fused]\n"
 		             "       [--precision 64|32] [--adaptive|--adaptive-rk43|--fixed] [--binary|--binary-only] [--ref-steady-state] [--decomp D0xD1|mpi [--block-contexts]]\n"
 		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary=V1,V2,... (repeatable)]\n"
+		             "       [--observe STRIDE [--probe I,J (repeatable)] [--observe-maps THRESHOLD]]\n"
 		             "       <Config file path>\n"
-		             "  --ensemble: fixed-step RK4, or error-controlled (each member its own ARKode-style steps) when the ini asks for [Solver] adaptive = 1\n";
+		             "  --ensemble: fixed-step RK4, or error-controlled (each member its own ARKode-style steps) when the ini asks for [Solver] adaptive = 1\n"
+		             "  --observe: with --ensemble, member_<k>/observables.txt -- time, min / max / sum / sum of squares of both fields and the probes' values\n"
+		             "             after every STRIDE-th step (error-controlled: at every output), recorded on the GPU; --observe-maps: also\n"
+		             "             amplitude_map.npy and activation_time.npy (first sample with var0 >= THRESHOLD)\n";
 	}
 	std::exit(EXIT_FAILURE);
 }
@@ -111,7 +120,16 @@ void parse_ensemble(const std::string &arg, Options *o)
 // What --ensemble cannot be combined with, and lists of unequal length: refused before the ini is read or any device touched.
 void check_ensemble_options(const Options &o)
 {
-	if (o.ensemble.empty()) return;
+	if (o.ensemble.empty()) {
+		if (o.observe) usage_error("--observe records an ensemble's members: it needs --ensemble");
+		if (!o.probes.empty()) usage_error("--probe belongs to --observe, which needs --ensemble");
+		if (o.observe_maps) usage_error("--observe-maps belongs to --observe, which needs --ensemble");
+		return;
+	}
+	if (!o.observe && !o.probes.empty()) usage_error("--probe belongs to --observe STRIDE");
+	if (!o.observe && o.observe_maps) usage_error("--observe-maps belongs to --observe STRIDE");
+	if (o.observe && o.observe_stride < 1) usage_error("--observe takes a stride of at least 1 (got " + std::to_string(o.observe_stride) + ")");
+	if ((int)o.probes.size() > CRD_OBSERVE_MAX_PROBES) usage_error("--probe: at most " + std::to_string(CRD_OBSERVE_MAX_PROBES) + " probes");
 	if (o.adaptive == 1 || o.adaptive == 2) usage_error("--ensemble steps fixed-step RK4 only: not with --adaptive / --adaptive-rk43");
 	if (o.gpus > 1) usage_error("--ensemble runs on one GPU: not with --gpus " + std::to_string(o.gpus));
 	if (o.d0 > 0 || o.decomp_mpi) usage_error("--ensemble members are single slabs: not with --decomp");
@@ -184,6 +202,53 @@ int die(const char *what, int rc, crd_ctx *ctx)
 	return 1;
 }
 
+// A [ny][nx] array of doubles as a NumPy .npy file (format 1.0).
+bool write_npy_2d(const std::string &path, const std::vector<double> &a, long long ny, long long nx)
+{
+	std::string head = "{'descr': '<f8', 'fortran_order': False, 'shape': (" + std::to_string(ny) + ", " + std::to_string(nx) + "), }";
+	while ((10 + head.size() + 1) % 64) head += ' ';
+	head += '\n';
+	FILE *f = std::fopen(path.c_str(), "wb");
+	if (!f) return false;
+	const unsigned char magic[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(head.size() & 0xff), (unsigned char)(head.size() >> 8)};
+	bool ok = std::fwrite(magic, 1, 10, f) == 10 && std::fwrite(head.data(), 1, head.size(), f) == head.size() && std::fwrite(a.data(), sizeof(double), a.size(), f) == a.size();
+	return std::fclose(f) == 0 && ok;
+}
+
+// What --observe leaves in <outdir>/member_<k>/: observables.txt, one line per sample in the state files' number format, and with
+// --observe-maps amplitude_map.npy (running maximum - running minimum of var0) and activation_time.npy.
+int write_observations(const Options &o, crd_ensemble *ens, int B, const crd_grid &g)
+{
+	int64_t n = 0;
+	int rc = crd_ensemble_observe_count(ens, &n);
+	const size_t P = o.probes.size();
+	std::vector<double> t((size_t)n), stats((size_t)n * (size_t)B * 8), pv((size_t)n * (size_t)B * P * 2);
+	if (rc == CRD_OK) rc = crd_ensemble_observe_read(ens, 0, n, t.data(), stats.data(), pv.data());
+	if (rc != CRD_OK) return rc;
+	const size_t points = (size_t)(g.nx * g.ny);
+	std::vector<double> lo(points), hi(points), ta(points);
+	for (int k = 0; k < B; k++) {
+		const std::string dir = o.outdir + "/member_" + std::to_string(k);
+		FILE *f = std::fopen((dir + "/observables.txt").c_str(), "w");
+		if (!f) return CRD_EIO;
+		std::fprintf(f, "# t min0 max0 sum0 sumsq0 min1 max1 sum1 sumsq1");
+		for (const auto &q : o.probes) std::fprintf(f, " var0(%lld,%lld) var1(%lld,%lld)", q.first, q.second, q.first, q.second);
+		std::fprintf(f, "\n");
+		for (size_t s = 0; s < (size_t)n; s++) {
+			std::fprintf(f, "%.16e", t[s]);
+			for (int c = 0; c < 8; c++) std::fprintf(f, " %.16e", stats[(s * (size_t)B + (size_t)k) * 8 + (size_t)c]);
+			for (size_t c = 0; c < 2 * P; c++) std::fprintf(f, " %.16e", pv[(s * (size_t)B + (size_t)k) * 2 * P + c]);
+			std::fprintf(f, "\n");
+		}
+		if (std::fclose(f) != 0) return CRD_EIO;
+		if (!o.observe_maps) continue;
+		if ((rc = crd_ensemble_observe_maps(ens, k, lo.data(), hi.data(), ta.data())) != CRD_OK) return rc;
+		for (size_t q = 0; q < points; q++) hi[q] -= lo[q];
+		if (!write_npy_2d(dir + "/amplitude_map.npy", hi, g.ny, g.nx) || !write_npy_2d(dir + "/activation_time.npy", ta, g.ny, g.nx)) return CRD_EIO;
+	}
+	return CRD_OK;
+}
+
 }  // namespace
 
 // --ensemble: the run of the ini once per member, the members' parameters zipped from the lists, all stepped together on one GPU
@@ -217,6 +282,14 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		}
 	const int64_t steps_per_output = (int64_t)std::ceil(dTout / dt_cap - 1e-12);
 	const double dt = dTout / (double)steps_per_output;
+
+	if (o.observe) {  // (refused before any device is asked for)
+		crd_grid pg;
+		if (crd_grid_from_params(&mp[0], &pg) != CRD_OK) usage_error("bad geometry");
+		for (const auto &q : o.probes)
+			if (q.first < 0 || q.first >= pg.nx || q.second < 0 || q.second >= pg.ny)
+				usage_error("--probe " + std::to_string(q.first) + "," + std::to_string(q.second) + " is outside the " + std::to_string(pg.nx) + " x " + std::to_string(pg.ny) + " grid");
+	}
 
 	crd_ensemble *ens = nullptr;
 	int rc = crd_ensemble_create(mp.data(), B, 0, &ens);
@@ -265,6 +338,26 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		}
 		if ((rc = crd_ensemble_upload(ens, k, buf.data(), 1)) != CRD_OK) {
 			std::cerr << "\nCRD_ERROR: crd_ensemble_upload failed: " << crd_ensemble_last_error(ens) << "\n\n";
+			cleanup();
+			return 1;
+		}
+	}
+
+	if (o.observe) {
+		crd_observe_options oo{};
+		oo.stride = o.observe_stride;
+		oo.n_probes = (int32_t)o.probes.size();
+		for (size_t q = 0; q < o.probes.size(); q++) {
+			oo.probe_i[q] = (int32_t)o.probes[q].first;
+			oo.probe_j[q] = (int32_t)o.probes[q].second;
+		}
+		oo.maps = o.observe_maps ? 1 : 0;
+		oo.threshold = o.observe_threshold;
+		// fixed steps: every stride-th step of the run -- floor(total steps / stride), the count the library itself reaches, since its
+		// step count carries over the calls; error-controlled: one sample per output
+		const int64_t capacity = adaptive ? Nt : std::max<int64_t>(1, steps_per_output * Nt / oo.stride);
+		if ((rc = crd_ensemble_observe_begin(ens, &oo, capacity)) != CRD_OK) {
+			std::cerr << "\nCRD_ERROR: crd_ensemble_observe_begin failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(ens) << "\n\n";
 			cleanup();
 			return 1;
 		}
@@ -325,6 +418,11 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 			std::printf("%s   %3d %%", iout > 0 ? "\r" : "", 100 * (iout + 1) / Nt);
 			std::fflush(stdout);
 		}
+	}
+	if (o.observe && (rc = write_observations(o, ens, B, g)) != CRD_OK) {
+		std::cerr << "\nCRD_ERROR: writing the observations failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(ens) << "\n\n";
+		cleanup();
+		return 1;
 	}
 	int status = 0;
 	for (int k = 0; k < B; k++)
@@ -415,6 +513,25 @@ int main(int argc, char *argv[])
 			else if (s == "--ref-steady-state") o.ref_steady_state = true;
 			else if (s == "--block-contexts") o.block_contexts = true;
 			else if (s == "--ensemble") parse_ensemble(next(), &o);
+			else if (s == "--observe") {
+				const std::string v = next();
+				char *end = nullptr;
+				o.observe = true;
+				o.observe_stride = std::strtoll(v.c_str(), &end, 10);
+				if (v.empty() || *end != '\0') usage_error("--observe takes a stride, a whole number of steps (got '" + v + "')");
+			} else if (s == "--probe") {
+				const std::string v = next();
+				long long i = 0, j = 0;
+				int used = 0;
+				if (std::sscanf(v.c_str(), "%lld,%lld%n", &i, &j, &used) != 2 || used != (int)v.size()) usage_error("--probe takes I,J, a grid point's theta and phi index (got '" + v + "')");
+				o.probes.emplace_back(i, j);
+			} else if (s == "--observe-maps") {
+				const std::string v = next();
+				char *end = nullptr;
+				o.observe_maps = true;
+				o.observe_threshold = std::strtod(v.c_str(), &end);
+				if (v.empty() || *end != '\0' || !std::isfinite(o.observe_threshold)) usage_error("--observe-maps takes a threshold, a number (got '" + v + "')");
+			}
 			else if (s == "--decomp") {
 				const std::string v = next();
 				if (v == "mpi") o.decomp_mpi = true;

@@ -242,6 +242,23 @@ def map_to_torus(run, surface_length, surface_width, out_dir=None, pvd=None, n_t
     return steps
 
 
+def oscillation_summary(t, series):
+    """Peak-to-peak amplitude and period of a sampled series (a probe's values from Ensemble.observations()): the amplitude is
+    max - min; the period is the mean spacing of the upward crossings of the series' mean, each placed by linear interpolation between
+    the two samples around it -- NaN with fewer than two crossings (a series that does not oscillate, or less than one period of one)."""
+    t = np.asarray(t, dtype=np.float64)
+    x = np.asarray(series, dtype=np.float64)
+    if t.shape != x.shape or t.ndim != 1 or t.size < 1:
+        raise ValueError("t and series are one-dimensional and equally long")
+    amplitude = float(np.max(x) - np.min(x))
+    d = x - np.mean(x)
+    up = np.nonzero((d[:-1] < 0.0) & (d[1:] >= 0.0))[0]
+    if up.size < 2:
+        return {"amplitude": amplitude, "period": float("nan"), "crossings": int(up.size)}
+    tc = t[up] + (t[up + 1] - t[up]) * (-d[up] / (d[up + 1] - d[up]))
+    return {"amplitude": amplitude, "period": float((tc[-1] - tc[0]) / (up.size - 1)), "crossings": int(up.size)}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("what", choices=["plot", "map"])

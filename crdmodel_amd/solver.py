@@ -343,6 +343,13 @@ class Slab:
         self._check(lib().crd_state_max_abs(self._h, C.byref(v)), "crd_state_max_abs")
         return v.value
 
+    def observe(self):
+        """min, max, sum and sum of squares of both fields of a single-slab context's state, [2, 4] (crd_state_observe): the row an
+        Ensemble of one holding this state records, bit for bit."""
+        v = np.empty((2, 4))
+        self._check(lib().crd_state_observe(self._h, v.ctypes.data_as(C.POINTER(C.c_double))), "crd_state_observe")
+        return v
+
     # -- RCCL wiring -------------------------------------------------------------------------------------------
     def init_rccl(self, unique_id):
         buf = C.create_string_buffer(bytes(unique_id), 128)
@@ -461,6 +468,62 @@ class Ensemble:
             d["status"] = status[k]
             out.append(d)
         return out
+
+    # -- observers ---------------------------------------------------------------------------------------------
+    def observe(self, stride=1, probes=(), maps=False, threshold=0.0, capacity=1024):
+        """Open the observer (crd_ensemble_observe_begin): from now on step_rk4 records a sample of every member after each stride-th
+        step and integrate_adaptive one per call -- field statistics, both fields at the `probes` (i, j) = (theta, phi index) and, with
+        maps, the running minimum / maximum of var0 and the activation time (first sample with var0 >= threshold) per grid point -- on
+        the device, without a synchronisation.  capacity: samples the record buffer holds.  Returns the observer's info: the sampling
+        blocks per member and the values per field, which state the sums' rounding bound."""
+        probes = list(probes)
+        opt = capi.ObserveOptions()
+        opt.stride, opt.n_probes, opt.maps, opt.threshold = int(stride), len(probes), 1 if maps else 0, float(threshold)
+        if len(probes) > capi.OBSERVE_MAX_PROBES:
+            raise ValueError("at most %d probes" % capi.OBSERVE_MAX_PROBES)
+        for q, (i, j) in enumerate(probes):
+            opt.probe_i[q], opt.probe_j[q] = int(i), int(j)
+        self._check(lib().crd_ensemble_observe_begin(self._h, C.byref(opt), int(capacity)), "crd_ensemble_observe_begin")
+        return self.observe_info()
+
+    def observe_info(self):
+        blocks, values, opt, cap = C.c_int32(), C.c_int64(), capi.ObserveOptions(), C.c_int64()
+        self._check(lib().crd_ensemble_observe_info(self._h, C.byref(blocks), C.byref(values), C.byref(opt), C.byref(cap)), "crd_ensemble_observe_info")
+        return {"blocks_per_member": blocks.value, "values_per_field": values.value, "stride": opt.stride, "maps": bool(opt.maps), "threshold": opt.threshold,
+                "probes": [(opt.probe_i[q], opt.probe_j[q]) for q in range(opt.n_probes)], "capacity": cap.value}
+
+    def observed_count(self):
+        n = C.c_int64()
+        self._check(lib().crd_ensemble_observe_count(self._h, C.byref(n)), "crd_ensemble_observe_count")
+        return n.value
+
+    def observations(self, first=0, count=None):
+        """The recorded samples first .. first + count - 1 (default: all): a dict of numpy arrays -- t [samples], stats [samples, members,
+        2 fields, 4: min, max, sum, sum of squares], probes [samples, members, probes, 2 fields] -- and, derived here, mean and variance
+        [samples, members, 2] (the population variance sum x^2 / n - mean^2, clipped at 0).  Synchronises; one copy."""
+        info = self.observe_info()
+        if count is None:
+            count = self.observed_count() - first
+        P = len(info["probes"])
+        t = np.empty(count)
+        stats = np.empty((count, self.n_members, 2, 4))
+        probes = np.empty((count, self.n_members, P, 2))
+        self._check(lib().crd_ensemble_observe_read(self._h, first, count, t.ctypes.data, stats.ctypes.data, probes.ctypes.data), "crd_ensemble_observe_read")
+        n = float(info["values_per_field"])
+        mean = stats[..., 2] / n
+        with np.errstate(invalid="ignore"):
+            variance = np.maximum(stats[..., 3] / n - mean * mean, 0.0)
+        variance[np.isnan(mean)] = np.nan
+        return {"t": t, "stats": stats, "probes": probes, "mean": mean, "variance": variance}
+
+    def observed_maps(self, member):
+        """Member `member`'s maps as they stand: (running minimum of var0, running maximum, activation time), [ny, nx] each."""
+        out = [np.empty((self.ny, self.nx)) for _ in range(3)]
+        self._check(lib().crd_ensemble_observe_maps(self._h, member, *[a.ctypes.data for a in out]), "crd_ensemble_observe_maps")
+        return tuple(out)
+
+    def end_observe(self):
+        self._check(lib().crd_ensemble_observe_end(self._h), "crd_ensemble_observe_end")
 
     def last_error(self):
         return lib().crd_ensemble_last_error(self._h).decode()

@@ -567,6 +567,62 @@ int crd_ensemble_max_abs(crd_ensemble *e, double *per_member);
 int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, const crd_adaptive_options *opt,
                                     crd_adaptive_stats *stats, int32_t *status);
 
+/* Observers: while an ensemble steps, record for every member -- on the device, without a host synchronisation -- the field
+ * statistics, the values at a few probe points and, optionally, per-point maps.  What a scan is read for (does member k oscillate,
+ * with what amplitude and period, where, and when does the wave arrive) without downloading every member's state at every output
+ * (the reference answers these from its output files, util/Plotting).  One sample is two small launches on the ensemble's stream
+ * behind the step it samples: a sampling pass over the state (blocks_per_member workgroups per member, each writing one partial
+ * record) and a finishing launch that adds a member's partials in index order.  No floating-point atomics: every addition has a
+ * fixed place, blocks_per_member depends on the grid size alone, so a member's row is bit-identical from run to run and in an
+ * ensemble of 1 and of 64.  Statistics accumulate in double whatever the ensemble's precision.  min and max are exact; a sum differs
+ * from the exact sum of the n = nx ny values by at most D u sum|x| (sums of squares: (D + 1) u sum x^2), u = 2^-53,
+ * D = ceil(n / (256 blocks_per_member)) + 8 + blocks_per_member: no value passes through more additions than that.  A field that
+ * holds a NaN reports NaN for its min, max and both sums.  No observers on multi-slab runs. */
+#define CRD_OBSERVE_MAX_PROBES 16
+typedef struct crd_observe_options {
+	int64_t stride;         /* >= 1: crd_ensemble_step_rk4 records a sample after every stride-th step since crd_ensemble_observe_begin */
+	int32_t n_probes;       /* 0 .. CRD_OBSERVE_MAX_PROBES grid points, the same for every member */
+	int32_t maps;           /* 1: also keep three planes per member, folded at every sample: running minimum and maximum of var0 (their
+	                         * difference is the peak-to-peak amplitude map) and the activation time */
+	int32_t probe_i[CRD_OBSERVE_MAX_PROBES]; /* theta index, 0 .. nx - 1 */
+	int32_t probe_j[CRD_OBSERVE_MAX_PROBES]; /* phi index (row), 0 .. ny - 1 */
+	double threshold;       /* maps: the activation time of a point is the time of the first sample at which var0 >= threshold */
+} crd_observe_options;
+/* Open the ensemble's observer with room for `capacity` samples: allocates the record buffer (capacity x n_members rows of
+ * 8 + 2 n_probes doubles), the partial records and, with maps, three planes of doubles per member.  CRD_EINVAL before any device work
+ * for a NULL opt, stride < 1, capacity < 1, n_probes outside 0 .. CRD_OBSERVE_MAX_PROBES, a probe outside the grid, a non-finite
+ * threshold with maps on, or an observer already open.  While it is open:
+ *   crd_ensemble_step_rk4 records a sample after every step whose count since this call is a multiple of stride (the count carries
+ *   over calls), at time t0 + (s + 1) dt for step s of the call; the call stays asynchronous.  A call that would record more
+ *   samples than there is room left is refused whole (CRD_EINVAL, nothing launched, state and sample count untouched);
+ *   crd_ensemble_integrate_adaptive records one sample per call, at tout, of the states it hands back; a member whose status is not
+ *   CRD_OK gets a row of NaNs (CRD_EINVAL, before any work, when no room is left) -- the sample is recorded and counted also when the call returns CRD_ESTATE -- and with maps on that
+ *   member's state, NaNs included, is still folded into its map planes (they follow np.minimum / np.maximum: a NaN stays);
+ *   crd_ensemble_upload does not disturb it.
+ * With no observer open an ensemble launches exactly what it launches without this interface. */
+int crd_ensemble_observe_begin(crd_ensemble *e, const crd_observe_options *opt, int64_t capacity);
+/* Samples recorded (enqueued) so far. */
+int crd_ensemble_observe_count(const crd_ensemble *e, int64_t *n_samples);
+/* Samples first .. first + count - 1: synchronises, ONE device-to-host copy.  Any of the three outputs may be NULL.
+ *   t[count]                                  sample times
+ *   stats[count][n_members][8]                min, max, sum, sum of squares of var0, then the same four of var1
+ *   probes[count][n_members][n_probes][2]     var0, var1 at each probe
+ * CRD_EINVAL for a range outside the recorded samples.  Reading does not consume: samples stay until crd_ensemble_observe_end. */
+int crd_ensemble_observe_read(crd_ensemble *e, int64_t first, int64_t count, double *t, double *stats, double *probes);
+/* One member's maps as they stand, ny * nx doubles each (row-major, theta fastest), any of them NULL: running minimum and maximum of
+ * var0 over the samples so far (+inf / -inf before the first) and the activation time (NaN where var0 was never >= threshold at a
+ * sample).  Synchronises.  CRD_EINVAL without maps. */
+int crd_ensemble_observe_maps(crd_ensemble *e, int member, double *min_u, double *max_u, double *t_act);
+/* What states the rounding bound above: sampling blocks per member, values per field (nx ny), and the observer's options and
+ * capacity.  Any pointer may be NULL.  CRD_EINVAL with no observer open. */
+int crd_ensemble_observe_info(const crd_ensemble *e, int32_t *blocks_per_member, int64_t *values_per_field, crd_observe_options *opt, int64_t *capacity);
+/* Close the observer and free what it holds (crd_ensemble_destroy does too).  CRD_EINVAL with no observer open. */
+int crd_ensemble_observe_end(crd_ensemble *e);
+/* The same eight statistics of a single-slab context's state, stats[8] as a row of crd_ensemble_observe_read: one synchronous call
+ * on the same sampling kernel, bit-identical to the row of an ensemble of one holding that state.  Generalises crd_state_max_abs.
+ * CRD_EINVAL for a context that is one of several slabs (no cross-rank reduction). */
+int crd_state_observe(crd_ctx *ctx, double stats[8]);
+
 #ifdef __cplusplus
 }
 #endif
