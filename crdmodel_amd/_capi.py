@@ -122,6 +122,18 @@ class ObserveOptions(C.Structure):
                 ("probe_j", C.c_int32 * OBSERVE_MAX_PROBES), ("threshold", C.c_double)]
 
 
+OBSERVE_MAX_SECTIONS = 8  # CRD_OBSERVE_MAX_SECTIONS
+SECTION_ROW, SECTION_COLUMN, SECTION_THETA_MEAN, SECTION_PHI_MEAN = 0, 1, 2, 3
+SECTION_KINDS = {"row": SECTION_ROW, "column": SECTION_COLUMN, "theta_mean": SECTION_THETA_MEAN, "phi_mean": SECTION_PHI_MEAN}
+
+
+class ObserveExtras(C.Structure):
+    """crd_observe_extras"""
+
+    _fields_ = [("n_sections", C.c_int32), ("cycles", C.c_int32), ("kind", C.c_int32 * OBSERVE_MAX_SECTIONS), ("index", C.c_int32 * OBSERVE_MAX_SECTIONS),
+                ("cycle_threshold", C.c_double)]
+
+
 # name -> (restype, argtypes); the test suite checks this table against include/crd.h symbol by symbol.
 _vp = C.c_void_p
 _SIGNATURES = {
@@ -218,6 +230,11 @@ _SIGNATURES = {
     "crd_ensemble_observe_info": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(ObserveOptions), C.POINTER(C.c_int64)]),
     "crd_ensemble_observe_end": (C.c_int, [_vp]),
     "crd_state_observe": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "crd_ensemble_observe_begin_with": (C.c_int, [_vp, C.POINTER(ObserveOptions), C.POINTER(ObserveExtras), C.c_int64]),
+    "crd_ensemble_observe_section_info": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "crd_ensemble_observe_read_section": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, _vp]),
+    "crd_ensemble_observe_cycles": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "crd_state_section": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
 }
 
 _lib = None

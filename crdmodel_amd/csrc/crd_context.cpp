@@ -838,4 +838,37 @@ int crd_state_observe(crd_ctx *c, double stats[8])
 	return CRD_OK;
 }
 
+int crd_state_section(crd_ctx *c, int kind, int index, double *values)
+{
+	if (!c || !values) return CRD_EINVAL;
+	ObserveSections sc{};
+	int blocks = 0;
+	if (!observe_section_shape(c->p.precision, kind, c->nx, c->nyl, &sc.length[0], &blocks, nullptr)) return fail(c, CRD_EINVAL, "crd_state_section: unknown kind " + std::to_string(kind));
+	if (c->n_slabs != 1) return fail(c, CRD_EINVAL, "crd_state_section takes a single-slab context: this one is slab " + std::to_string(c->slab) + " of " + std::to_string(c->n_slabs));
+	if ((kind == CRD_SECTION_ROW && (index < 0 || index >= c->nyl)) || (kind == CRD_SECTION_COLUMN && (index < 0 || index >= c->nx)))
+		return fail(c, CRD_EINVAL, std::string("crd_state_section: ") + (kind == CRD_SECTION_ROW ? "row " : "column ") + std::to_string(index) + " is outside the " + std::to_string(c->nx) + " x " + std::to_string(c->nyl) + " grid");
+	if (int rc = set_device(c)) return rc;
+	// a one-entry descriptor over the owned rows and the line, in one block (crd_state_observe)
+	EnsembleMember m{};
+	const size_t first_row = (size_t)kGhost * (size_t)c->nx * c->real_size;
+	m.u[0] = static_cast<char *>(c->plane[crd_ctx::Y][0]) + first_row;
+	m.v[0] = static_cast<char *>(c->plane[crd_ctx::Y][1]) + first_row;
+	static_assert(sizeof(EnsembleMember) % 16 == 0, "the line behind the descriptor sits on 16 bytes");
+	const size_t line = (size_t)sc.length[0] * 2 * sizeof(double);
+	char *block = nullptr;
+	HIP_TRY(c, hipMalloc((void **)&block, sizeof m + line));
+	sc.n = 1;
+	sc.kind[0] = kind;
+	sc.index[0] = (kind == CRD_SECTION_ROW || kind == CRD_SECTION_COLUMN) ? index : 0;
+	sc.first_block[1] = blocks;
+	sc.out[0] = reinterpret_cast<double *>(block + sizeof m);
+	hipError_t r = hipMemcpyAsync(block, &m, sizeof m, hipMemcpyHostToDevice, c->compute);
+	if (r == hipSuccess) r = launch_observe_sections(c->p.precision, reinterpret_cast<EnsembleMember *>(block), 1, 0, c->nx, c->nyl, sc, c->compute);
+	if (r == hipSuccess) r = hipMemcpyAsync(values, sc.out[0], line, hipMemcpyDeviceToHost, c->compute);
+	if (r == hipSuccess) r = hipStreamSynchronize(c->compute);
+	(void)hipFree(block);
+	if (r != hipSuccess) return fail(c, CRD_EHIP, std::string("crd_state_section: ") + hipGetErrorString(r));
+	return CRD_OK;
+}
+
 }  // extern "C"

@@ -64,6 +64,14 @@ struct crd_ensemble {
 		double *partials = nullptr;            // n x blocks x 8
 		double *maps = nullptr;                // n x 3 x map_plane (minimum, maximum, activation time), or null
 		std::vector<double> t;                 // the samples' times
+		// sections and cycle maps (crd_ensemble_observe_begin_with): none unless asked for
+		ObserveSections sections{};            // kinds, indices, lengths, blocks; out[] is set per sample
+		int64_t section_additions[kObserveMaxSections] = {};  // D of each section's bound
+		size_t section_base[kObserveMaxSections] = {};        // section s: section_records + section_base[s], capacity x n x length x 2
+		double *section_records = nullptr;
+		bool cycles = false;
+		double cycle_threshold = 0.0;
+		double *cycle_planes = nullptr;        // n x 4 x map_plane (previous var0, t_first, t_last, int32 count), or null
 	} obs;
 };
 
@@ -107,9 +115,15 @@ int check_member(crd_ensemble *e, int member)
 
 void observer_release(crd_ensemble *e)
 {
-	for (void *q : {(void *)e->obs.records, (void *)e->obs.partials, (void *)e->obs.maps})
+	for (void *q : {(void *)e->obs.records, (void *)e->obs.partials, (void *)e->obs.maps, (void *)e->obs.section_records, (void *)e->obs.cycle_planes})
 		if (q) (void)hipFree(q);
 	e->obs = crd_ensemble::Observer{};
+}
+
+// Sample `sample`'s lines of section s: n members x length x 2 doubles.
+double *section_lines(crd_ensemble *e, int s, int64_t sample)
+{
+	return e->obs.section_records + e->obs.section_base[s] + (size_t)sample * (size_t)e->n * (size_t)e->obs.sections.length[s] * 2;
 }
 
 // One sample of every member's current state at time t, behind whatever the stream holds: the sampling pass, then the finishing
@@ -119,8 +133,17 @@ int observer_sample(crd_ensemble *e, double t)
 	crd_ensemble::Observer &ob = e->obs;
 	const size_t n = (size_t)e->nx * (size_t)e->ny;
 	double *const row = ob.records + (size_t)ob.count * (size_t)e->n * (size_t)ob.row_doubles;
-	ENS_TRY(e, launch_observe_sample(e->precision, e->table, e->n, e->cur, n, ob.partials, ob.maps, ob.map_plane, ob.opt.threshold, t, e->stream));
+	if (ob.cycles) {
+		const ObserveCycles cy{ob.cycle_planes, ob.map_plane, ob.cycle_threshold, ob.t.empty() ? 0.0 : ob.t.back(), ob.t.empty() ? 1 : 0};
+		ENS_TRY(e, launch_observe_sample_cycles(e->precision, e->table, e->n, e->cur, n, ob.partials, ob.maps, ob.map_plane, ob.opt.threshold, t, cy, e->stream));
+	} else {
+		ENS_TRY(e, launch_observe_sample(e->precision, e->table, e->n, e->cur, n, ob.partials, ob.maps, ob.map_plane, ob.opt.threshold, t, e->stream));
+	}
 	ENS_TRY(e, launch_observe_finish(e->precision, e->table, e->n, e->cur, n, ob.partials, ob.probes, e->nx, row, ob.row_doubles, e->stream));
+	if (ob.sections.n > 0) {
+		for (int s = 0; s < ob.sections.n; s++) ob.sections.out[s] = section_lines(e, s, ob.count);
+		ENS_TRY(e, launch_observe_sections(e->precision, e->table, e->n, e->cur, e->nx, e->ny, ob.sections, e->stream));
+	}
 	ob.t.push_back(t);
 	ob.count++;
 	return CRD_OK;
@@ -762,11 +785,17 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 	ENS_TRY(e, hipMemcpyAsync(e->table, e->members.data(), (size_t)B * sizeof(EnsembleMember), hipMemcpyHostToDevice, e->stream));
 	if (e->obs.open) {
 		// one sample per call, of the states handed back; a member that failed gets a row of NaNs (every byte 0xff is one)
-		double *const row = e->obs.records + (size_t)e->obs.count * (size_t)B * (size_t)e->obs.row_doubles;
+		const int64_t sample = e->obs.count;
+		double *const row = e->obs.records + (size_t)sample * (size_t)B * (size_t)e->obs.row_doubles;
 		if (int orc = observer_sample(e, tout)) return orc;
 		for (int k = 0; k < B; k++)
-			if (run[(size_t)k].failed)
+			if (run[(size_t)k].failed) {
 				ENS_TRY(e, hipMemsetAsync(row + (size_t)k * (size_t)e->obs.row_doubles, 0xff, (size_t)e->obs.row_doubles * sizeof(double), e->stream));
+				for (int s = 0; s < e->obs.sections.n; s++) {  // ... and lines of NaNs
+					const size_t line = (size_t)e->obs.sections.length[s] * 2;
+					ENS_TRY(e, hipMemsetAsync(section_lines(e, s, sample) + (size_t)k * line, 0xff, line * sizeof(double), e->stream));
+				}
+			}
 	}
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	if (rc != CRD_OK) return efail(e, rc, "adaptive integration failed for " + failures);
@@ -779,7 +808,9 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 
 extern "C" {
 
-int crd_ensemble_observe_begin(crd_ensemble *e, const crd_observe_options *opt, int64_t capacity)
+int crd_ensemble_observe_begin(crd_ensemble *e, const crd_observe_options *opt, int64_t capacity) { return crd_ensemble_observe_begin_with(e, opt, nullptr, capacity); }
+
+int crd_ensemble_observe_begin_with(crd_ensemble *e, const crd_observe_options *opt, const crd_observe_extras *extras, int64_t capacity)
 {
 	if (!e) return CRD_EINVAL;
 	if (!opt) return efail(e, CRD_EINVAL, "null observer options");
@@ -795,8 +826,38 @@ int crd_ensemble_observe_begin(crd_ensemble *e, const crd_observe_options *opt, 
 	if (opt->maps != 0 && opt->maps != 1) return efail(e, CRD_EINVAL, "observer maps is 0 or 1");
 	if (opt->maps && !std::isfinite(opt->threshold)) return efail(e, CRD_EINVAL, "observer maps need a finite threshold");
 	static_assert(CRD_OBSERVE_MAX_PROBES == kObserveMaxProbes, "the header's probe limit is the kernels'");
+	static_assert(CRD_OBSERVE_MAX_SECTIONS == kObserveMaxSections, "the header's section limit is the kernels'");
 	const size_t n = (size_t)e->nx * (size_t)e->ny, B = (size_t)e->n;
 	crd_ensemble::Observer ob;
+	size_t section_doubles = 0;  // of the whole section buffer
+	if (extras) {
+		if (extras->n_sections < 0 || extras->n_sections > CRD_OBSERVE_MAX_SECTIONS)
+			return efail(e, CRD_EINVAL, "an observer takes 0 .. " + std::to_string(CRD_OBSERVE_MAX_SECTIONS) + " sections (got " + std::to_string(extras->n_sections) + ")");
+		if (extras->cycles != 0 && extras->cycles != 1) return efail(e, CRD_EINVAL, "observer cycles is 0 or 1");
+		if (extras->cycles && !std::isfinite(extras->cycle_threshold)) return efail(e, CRD_EINVAL, "cycle maps need a finite cycle_threshold");
+		ObserveSections &sc = ob.sections;
+		sc.n = extras->n_sections;
+		for (int s = 0; s < sc.n; s++) {
+			int blocks = 0;
+			if (!observe_section_shape(e->precision, extras->kind[s], e->nx, e->ny, &sc.length[s], &blocks, &ob.section_additions[s]))
+				return efail(e, CRD_EINVAL, "section " + std::to_string(s) + ": unknown kind " + std::to_string(extras->kind[s]));
+			sc.kind[s] = extras->kind[s];
+			sc.index[s] = 0;
+			if (sc.kind[s] == CRD_SECTION_ROW || sc.kind[s] == CRD_SECTION_COLUMN) {
+				const int limit = sc.kind[s] == CRD_SECTION_ROW ? e->ny : e->nx;
+				if (extras->index[s] < 0 || extras->index[s] >= limit)
+					return efail(e, CRD_EINVAL, "section " + std::to_string(s) + ": " + (sc.kind[s] == CRD_SECTION_ROW ? "row " : "column ") + std::to_string(extras->index[s]) +
+					                                " is outside the " + std::to_string(e->nx) + " x " + std::to_string(e->ny) + " grid");
+				sc.index[s] = extras->index[s];
+			}
+			sc.first_block[s + 1] = sc.first_block[s] + blocks;
+			if ((double)capacity * (double)B * (double)sc.length[s] * 16.0 > 0x1p46) return efail(e, CRD_EINVAL, "observer capacity too large");
+			ob.section_base[s] = section_doubles;
+			section_doubles += (size_t)(capacity > 0 ? capacity : 0) * B * (size_t)sc.length[s] * 2;
+		}
+		ob.cycles = extras->cycles == 1;
+		ob.cycle_threshold = extras->cycle_threshold;
+	}
 	ob.opt = *opt;
 	ob.probes.n = opt->n_probes;
 	for (int q = 0; q < opt->n_probes; q++) {
@@ -824,6 +885,17 @@ int crd_ensemble_observe_begin(crd_ensemble *e, const crd_observe_options *opt, 
 			for (int q = 0; q < 3; q++)
 				if (hipError_t r = launch_observe_fill(e->obs.maps + (k * 3 + (size_t)q) * ob.map_plane, ob.map_plane, init[q], e->stream); r != hipSuccess)
 					return fail(r, "map initialisation");
+		}
+	}
+	if (section_doubles)
+		if (hipError_t r = hipMalloc((void **)&e->obs.section_records, section_doubles * sizeof(double)); r != hipSuccess) return fail(r, "hipMalloc(section records)");
+	if (ob.cycles) {
+		if (hipError_t r = hipMalloc((void **)&e->obs.cycle_planes, B * 4 * ob.map_plane * sizeof(double)); r != hipSuccess) return fail(r, "hipMalloc(cycle planes)");
+		for (size_t k = 0; k < B; k++) {  // previous var0: anything (the first sample stores it); t_first, t_last: NaN; count: 0
+			double *const planes = e->obs.cycle_planes + k * 4 * ob.map_plane;
+			if (hipError_t r = launch_observe_fill(planes + ob.map_plane, 2 * ob.map_plane, NAN, e->stream); r != hipSuccess) return fail(r, "cycle map initialisation");
+			if (hipError_t r = hipMemsetAsync(planes, 0, ob.map_plane * sizeof(double), e->stream); r != hipSuccess) return fail(r, "cycle map initialisation");
+			if (hipError_t r = hipMemsetAsync(planes + 3 * ob.map_plane, 0, ob.map_plane * sizeof(double), e->stream); r != hipSuccess) return fail(r, "cycle map initialisation");
 		}
 	}
 	e->obs.open = true;
@@ -877,6 +949,47 @@ int crd_ensemble_observe_maps(crd_ensemble *e, int member, double *min_u, double
 	double *const out[3] = {min_u, max_u, t_act};
 	for (int q = 0; q < 3; q++)
 		if (out[q]) ENS_TRY(e, hipMemcpyAsync(out[q], e->obs.maps + ((size_t)member * 3 + (size_t)q) * e->obs.map_plane, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	ENS_TRY(e, hipStreamSynchronize(e->stream));
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_section_info(const crd_ensemble *e, int section, int32_t *kind, int32_t *index, int64_t *length, int64_t *additions)
+{
+	if (!e || !e->obs.open || section < 0 || section >= e->obs.sections.n) return CRD_EINVAL;
+	if (kind) *kind = e->obs.sections.kind[section];
+	if (index) *index = e->obs.sections.index[section];
+	if (length) *length = e->obs.sections.length[section];
+	if (additions) *additions = e->obs.section_additions[section];
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_read_section(crd_ensemble *e, int section, int64_t first, int64_t count, double *values)
+{
+	if (!e) return CRD_EINVAL;
+	const crd_ensemble::Observer &ob = e->obs;
+	if (!ob.open) return efail(e, CRD_EINVAL, "no observer is open");
+	if (section < 0 || section >= ob.sections.n) return efail(e, CRD_EINVAL, "section " + std::to_string(section) + " was not configured (the observer has " + std::to_string(ob.sections.n) + ")");
+	if (first < 0 || count < 0 || first > ob.count || count > ob.count - first) return efail(e, CRD_EINVAL, "sample range outside the " + std::to_string(ob.count) + " recorded");
+	if (count > 0 && !values) return efail(e, CRD_EINVAL, "null values");
+	TraceRange range("crd_ensemble_observe_read_section");
+	ENS_TRY(e, hipSetDevice(e->device));
+	const size_t doubles = (size_t)count * (size_t)e->n * (size_t)ob.sections.length[section] * 2;
+	if (doubles) ENS_TRY(e, hipMemcpyAsync(values, section_lines(e, section, first), doubles * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	ENS_TRY(e, hipStreamSynchronize(e->stream));
+	return CRD_OK;
+}
+
+int crd_ensemble_observe_cycles(crd_ensemble *e, int member, int32_t *count, double *t_first, double *t_last)
+{
+	if (!e) return CRD_EINVAL;
+	if (!e->obs.open || !e->obs.cycles) return efail(e, CRD_EINVAL, "no observer with cycle maps is open");
+	if (int rc = check_member(e, member)) return rc;
+	ENS_TRY(e, hipSetDevice(e->device));
+	const size_t n = (size_t)e->nx * (size_t)e->ny, plane = e->obs.map_plane;
+	const double *const planes = e->obs.cycle_planes + (size_t)member * 4 * plane;
+	if (t_first) ENS_TRY(e, hipMemcpyAsync(t_first, planes + plane, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	if (t_last) ENS_TRY(e, hipMemcpyAsync(t_last, planes + 2 * plane, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+	if (count) ENS_TRY(e, hipMemcpyAsync(count, planes + 3 * plane, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	return CRD_OK;
 }

@@ -135,4 +135,32 @@ hipError_t launch_observe_finish(int precision, const EnsembleMember *table, int
                                  double *row_dev, int row_doubles, hipStream_t s);
 hipError_t launch_observe_fill(double *x, size_t n, double value, hipStream_t s);
 
+// Cycle maps: what the sampling pass needs besides the sample's time.  Member k's four planes of `plane` >= n doubles each at
+// planes + 4 k plane: the previous sample's var0, the time of the first and of the last upward crossing of `threshold` (NaN where
+// there was none), and -- as int32, in the first half of its plane -- the count of crossings.
+struct ObserveCycles {
+	double *planes;
+	size_t plane;
+	double threshold;
+	double t_prev;          // the previous sample's time
+	int first;              // the first sample since begin: only stores var0
+};
+// launch_observe_sample with the cycle maps folded in the same pass over the state.
+hipError_t launch_observe_sample_cycles(int precision, const EnsembleMember *table, int members, int src, size_t n, double *partials_dev, double *maps_dev, size_t map_plane,
+                                        double threshold, double t, const ObserveCycles &cy, hipStream_t s);
+
+// Sections: lines of both fields along a row or a column, and the means over theta and over phi, the same for every member: a kernel
+// argument of the sections launch.
+constexpr int kObserveMaxSections = 8;          // CRD_OBSERVE_MAX_SECTIONS
+struct ObserveSections {
+	int n;
+	int kind[kObserveMaxSections], index[kObserveMaxSections], length[kObserveMaxSections];
+	int first_block[kObserveMaxSections + 1];   // blocks per member before section s; [n]: blocks per member
+	double *out[kObserveMaxSections];           // this sample's lines of section s: member k's at out[s] + 2 k length[s], (var0, var1) per point
+};
+// A section's values per field, its blocks per member and D, the additions a value of a mean passes through (+ 3: crd.h; 0 for the
+// exact kinds): functions of the kind, the precision (values per 16-byte load) and the grid alone.  false: unknown kind.
+bool observe_section_shape(int precision, int kind, int nx, int ny, int *length, int *blocks, int64_t *additions);
+hipError_t launch_observe_sections(int precision, const EnsembleMember *table, int members, int src, int nx, int ny, const ObserveSections &sc, hipStream_t s);
+
 }  // namespace crd

@@ -46,6 +46,10 @@ struct Options {
 	long long observe_stride = 0;
 	double observe_threshold = 0.0;
 	std::vector<std::pair<long long, long long>> probes;
+	// --section row:J|column:I|theta-mean|phi-mean (repeatable), --observe-cycles THRESHOLD: the observer's sections and cycle maps
+	std::vector<std::pair<int, long long>> sections;  // (CRD_SECTION_*, index)
+	bool observe_cycles = false;
+	double cycle_threshold = 0.0;
 };
 
 [[noreturn]] void usage(const char *argv0, bool alias)
@@ -57,12 +61,15 @@ struct Options {
 		          << " --model fhn|goldbeter --surface torus|flat [--gpus G] [--devices D] [--dt DT] [--stepper auto|staged|fused]\n"
 		             "       [--precision 64|32] [--adaptive|--adaptive-rk43|--fixed] [--binary|--binary-only] [--ref-steady-state] [--decomp D0xD1|mpi [--block-contexts]]\n"
 		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary=V1,V2,... (repeatable)]\n"
-		             "       [--observe STRIDE [--probe I,J (repeatable)] [--observe-maps THRESHOLD]]\n"
+		             "       [--observe STRIDE [--probe I,J (repeatable)] [--observe-maps THRESHOLD]\n"
+		             "                         [--section row:J|column:I|theta-mean|phi-mean (repeatable)] [--observe-cycles THRESHOLD]]\n"
 		             "       <Config file path>\n"
 		             "  --ensemble: fixed-step RK4, or error-controlled (each member its own ARKode-style steps) when the ini asks for [Solver] adaptive = 1\n"
 		             "  --observe: with --ensemble, member_<k>/observables.txt -- time, min / max / sum / sum of squares of both fields and the probes' values\n"
 		             "             after every STRIDE-th step (error-controlled: at every output), recorded on the GPU; --observe-maps: also\n"
-		             "             amplitude_map.npy and activation_time.npy (first sample with var0 >= THRESHOLD)\n";
+		             "             amplitude_map.npy and activation_time.npy (first sample with var0 >= THRESHOLD); --section: also\n"
+		             "             section_<n>.npy, [sample, length, 2]: both fields along a row or a column, or their mean over theta / over phi;\n"
+		             "             --observe-cycles: also activation_count.npy (upward crossings of THRESHOLD by var0) and period_map.npy\n";
 	}
 	std::exit(EXIT_FAILURE);
 }
@@ -124,8 +131,13 @@ void check_ensemble_options(const Options &o)
 		if (o.observe) usage_error("--observe records an ensemble's members: it needs --ensemble");
 		if (!o.probes.empty()) usage_error("--probe belongs to --observe, which needs --ensemble");
 		if (o.observe_maps) usage_error("--observe-maps belongs to --observe, which needs --ensemble");
+		if (!o.sections.empty()) usage_error("--section belongs to --observe, which needs --ensemble");
+		if (o.observe_cycles) usage_error("--observe-cycles belongs to --observe, which needs --ensemble");
 		return;
 	}
+	if (!o.observe && !o.sections.empty()) usage_error("--section belongs to --observe STRIDE");
+	if (!o.observe && o.observe_cycles) usage_error("--observe-cycles belongs to --observe STRIDE");
+	if ((int)o.sections.size() > CRD_OBSERVE_MAX_SECTIONS) usage_error("--section: at most " + std::to_string(CRD_OBSERVE_MAX_SECTIONS) + " sections");
 	if (!o.observe && !o.probes.empty()) usage_error("--probe belongs to --observe STRIDE");
 	if (!o.observe && o.observe_maps) usage_error("--observe-maps belongs to --observe STRIDE");
 	if (o.observe && o.observe_stride < 1) usage_error("--observe takes a stride of at least 1 (got " + std::to_string(o.observe_stride) + ")");
@@ -202,6 +214,37 @@ int die(const char *what, int rc, crd_ctx *ctx)
 	return 1;
 }
 
+const char *section_name(int kind)
+{
+	return kind == CRD_SECTION_ROW ? "row" : kind == CRD_SECTION_COLUMN ? "column" : kind == CRD_SECTION_THETA_MEAN ? "theta-mean" : "phi-mean";
+}
+
+// --section's argument: row:J, column:I, theta-mean or phi-mean.
+void parse_section(const std::string &v, Options *o)
+{
+	if (v == "theta-mean") return (void)o->sections.emplace_back(CRD_SECTION_THETA_MEAN, 0);
+	if (v == "phi-mean") return (void)o->sections.emplace_back(CRD_SECTION_PHI_MEAN, 0);
+	const size_t colon = v.find(':');
+	const std::string name = v.substr(0, colon), at = colon == std::string::npos ? "" : v.substr(colon + 1);
+	char *end = nullptr;
+	const long long index = std::strtoll(at.c_str(), &end, 10);
+	if ((name != "row" && name != "column") || at.empty() || *end != '\0') usage_error("--section takes row:J, column:I, theta-mean or phi-mean (got '" + v + "')");
+	o->sections.emplace_back(name == "row" ? CRD_SECTION_ROW : CRD_SECTION_COLUMN, index);
+}
+
+// An array of doubles or int32 of the given shape as a NumPy .npy file (format 1.0).
+bool write_npy(const std::string &path, const void *data, size_t bytes, const char *descr, const std::string &shape)
+{
+	std::string head = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" + shape + "), }";
+	while ((10 + head.size() + 1) % 64) head += ' ';
+	head += '\n';
+	FILE *f = std::fopen(path.c_str(), "wb");
+	if (!f) return false;
+	const unsigned char magic[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(head.size() & 0xff), (unsigned char)(head.size() >> 8)};
+	bool ok = std::fwrite(magic, 1, 10, f) == 10 && std::fwrite(head.data(), 1, head.size(), f) == head.size() && std::fwrite(data, 1, bytes, f) == bytes;
+	return std::fclose(f) == 0 && ok;
+}
+
 // A [ny][nx] array of doubles as a NumPy .npy file (format 1.0).
 bool write_npy_2d(const std::string &path, const std::vector<double> &a, long long ny, long long nx)
 {
@@ -227,6 +270,7 @@ int write_observations(const Options &o, crd_ensemble *ens, int B, const crd_gri
 	if (rc != CRD_OK) return rc;
 	const size_t points = (size_t)(g.nx * g.ny);
 	std::vector<double> lo(points), hi(points), ta(points);
+	std::vector<std::vector<double>> section_values(o.sections.size());
 	for (int k = 0; k < B; k++) {
 		const std::string dir = o.outdir + "/member_" + std::to_string(k);
 		FILE *f = std::fopen((dir + "/observables.txt").c_str(), "w");
@@ -234,6 +278,16 @@ int write_observations(const Options &o, crd_ensemble *ens, int B, const crd_gri
 		std::fprintf(f, "# t min0 max0 sum0 sumsq0 min1 max1 sum1 sumsq1");
 		for (const auto &q : o.probes) std::fprintf(f, " var0(%lld,%lld) var1(%lld,%lld)", q.first, q.second, q.first, q.second);
 		std::fprintf(f, "\n");
+		for (size_t q = 0; q < o.sections.size(); q++) {  // (further comment lines: numpy.loadtxt skips them)
+			std::fprintf(f, "# section_%zu.npy: %s", q, section_name(o.sections[q].first));
+			if (o.sections[q].first == CRD_SECTION_ROW || o.sections[q].first == CRD_SECTION_COLUMN) std::fprintf(f, " %lld", o.sections[q].second);
+			std::fprintf(f, ", [sample, length, 2]; sample s at the time t of line s below\n");
+		}
+		if (!o.sections.empty()) {
+			std::fprintf(f, "# sample times:");
+			for (size_t s = 0; s < (size_t)n; s++) std::fprintf(f, " %.16e", t[s]);
+			std::fprintf(f, "\n");
+		}
 		for (size_t s = 0; s < (size_t)n; s++) {
 			std::fprintf(f, "%.16e", t[s]);
 			for (int c = 0; c < 8; c++) std::fprintf(f, " %.16e", stats[(s * (size_t)B + (size_t)k) * 8 + (size_t)c]);
@@ -241,6 +295,28 @@ int write_observations(const Options &o, crd_ensemble *ens, int B, const crd_gri
 			std::fprintf(f, "\n");
 		}
 		if (std::fclose(f) != 0) return CRD_EIO;
+		for (size_t q = 0; q < o.sections.size(); q++) {  // the member's lines out of the section's [sample][member][length][2]
+			int64_t length = 0;
+			if ((rc = crd_ensemble_observe_section_info(ens, (int)q, nullptr, nullptr, &length, nullptr)) != CRD_OK) return rc;
+			const size_t line = (size_t)length * 2;
+			if (k == 0) {
+				section_values[q].resize((size_t)n * (size_t)B * line);
+				if ((rc = crd_ensemble_observe_read_section(ens, (int)q, 0, n, section_values[q].data())) != CRD_OK) return rc;
+			}
+			std::vector<double> mine((size_t)n * line);
+			for (size_t s = 0; s < (size_t)n; s++)
+				std::copy(section_values[q].begin() + (ptrdiff_t)((s * (size_t)B + (size_t)k) * line), section_values[q].begin() + (ptrdiff_t)((s * (size_t)B + (size_t)k + 1) * line), mine.begin() + (ptrdiff_t)(s * line));
+			if (!write_npy(dir + "/section_" + std::to_string(q) + ".npy", mine.data(), mine.size() * sizeof(double), "<f8", std::to_string(n) + ", " + std::to_string(length) + ", 2")) return CRD_EIO;
+		}
+		if (o.observe_cycles) {
+			std::vector<int32_t> count(points);
+			std::vector<double> tf(points), tl(points), period(points, std::nan(""));
+			if ((rc = crd_ensemble_observe_cycles(ens, k, count.data(), tf.data(), tl.data())) != CRD_OK) return rc;
+			for (size_t q = 0; q < points; q++)
+				if (count[q] >= 2) period[q] = (tl[q] - tf[q]) / (double)(count[q] - 1);
+			const std::string shape = std::to_string(g.ny) + ", " + std::to_string(g.nx);
+			if (!write_npy(dir + "/activation_count.npy", count.data(), points * sizeof(int32_t), "<i4", shape) || !write_npy_2d(dir + "/period_map.npy", period, g.ny, g.nx)) return CRD_EIO;
+		}
 		if (!o.observe_maps) continue;
 		if ((rc = crd_ensemble_observe_maps(ens, k, lo.data(), hi.data(), ta.data())) != CRD_OK) return rc;
 		for (size_t q = 0; q < points; q++) hi[q] -= lo[q];
@@ -289,6 +365,9 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		for (const auto &q : o.probes)
 			if (q.first < 0 || q.first >= pg.nx || q.second < 0 || q.second >= pg.ny)
 				usage_error("--probe " + std::to_string(q.first) + "," + std::to_string(q.second) + " is outside the " + std::to_string(pg.nx) + " x " + std::to_string(pg.ny) + " grid");
+		for (const auto &q : o.sections)
+			if ((q.first == CRD_SECTION_ROW && (q.second < 0 || q.second >= pg.ny)) || (q.first == CRD_SECTION_COLUMN && (q.second < 0 || q.second >= pg.nx)))
+				usage_error(std::string("--section ") + section_name(q.first) + ":" + std::to_string(q.second) + " is outside the " + std::to_string(pg.nx) + " x " + std::to_string(pg.ny) + " grid");
 	}
 
 	crd_ensemble *ens = nullptr;
@@ -356,7 +435,16 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		// fixed steps: every stride-th step of the run -- floor(total steps / stride), the count the library itself reaches, since its
 		// step count carries over the calls; error-controlled: one sample per output
 		const int64_t capacity = adaptive ? Nt : std::max<int64_t>(1, steps_per_output * Nt / oo.stride);
-		if ((rc = crd_ensemble_observe_begin(ens, &oo, capacity)) != CRD_OK) {
+		crd_observe_extras ex{};
+		ex.n_sections = (int32_t)o.sections.size();
+		for (size_t q = 0; q < o.sections.size(); q++) {
+			ex.kind[q] = o.sections[q].first;
+			ex.index[q] = (int32_t)o.sections[q].second;
+		}
+		ex.cycles = o.observe_cycles ? 1 : 0;
+		ex.cycle_threshold = o.cycle_threshold;
+		const bool extras = ex.n_sections > 0 || ex.cycles;
+		if ((rc = extras ? crd_ensemble_observe_begin_with(ens, &oo, &ex, capacity) : crd_ensemble_observe_begin(ens, &oo, capacity)) != CRD_OK) {
 			std::cerr << "\nCRD_ERROR: crd_ensemble_observe_begin failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(ens) << "\n\n";
 			cleanup();
 			return 1;
@@ -531,6 +619,14 @@ int main(int argc, char *argv[])
 				o.observe_maps = true;
 				o.observe_threshold = std::strtod(v.c_str(), &end);
 				if (v.empty() || *end != '\0' || !std::isfinite(o.observe_threshold)) usage_error("--observe-maps takes a threshold, a number (got '" + v + "')");
+			} else if (s == "--section") {
+				parse_section(next(), &o);
+			} else if (s == "--observe-cycles") {
+				const std::string v = next();
+				char *end = nullptr;
+				o.observe_cycles = true;
+				o.cycle_threshold = std::strtod(v.c_str(), &end);
+				if (v.empty() || *end != '\0' || !std::isfinite(o.cycle_threshold)) usage_error("--observe-cycles takes a threshold, a number (got '" + v + "')");
 			}
 			else if (s == "--decomp") {
 				const std::string v = next();

@@ -259,6 +259,43 @@ def oscillation_summary(t, series):
     return {"amplitude": amplitude, "period": float((tc[-1] - tc[0]) / (up.size - 1)), "crossings": int(up.size)}
 
 
+def period_map(count, t_first, t_last):
+    """The period per grid point from an observer's cycle maps (Ensemble.observed_cycles): (t_last - t_first) / (count - 1) where a
+    point had at least two upward crossings, NaN elsewhere."""
+    count = np.asarray(count)
+    t_first, t_last = np.asarray(t_first, dtype=np.float64), np.asarray(t_last, dtype=np.float64)
+    if not (count.shape == t_first.shape == t_last.shape):
+        raise ValueError("count, t_first and t_last have one shape")
+    out = np.full(count.shape, np.nan)
+    two = count >= 2
+    out[two] = (t_last[two] - t_first[two]) / (count[two] - 1)
+    return out
+
+
+def plot_kymograph(section, t, var=0, path=None, extent=None, dpi=150):
+    """A space-time image of one member's section: section is [sample, length, 2] (Ensemble.observed_section(s)[:, member], or a
+    driver's section_<n>.npy), t the samples' times; position runs along x, time upwards.  Returns the figure, saved to `path` if given."""
+    import matplotlib
+    matplotlib.use("Agg")
+    import matplotlib.pyplot as plt
+
+    section = np.asarray(section, dtype=np.float64)
+    t = np.asarray(t, dtype=np.float64)
+    if section.ndim != 3 or section.shape[2] != 2 or t.shape != (section.shape[0],):
+        raise ValueError("section is [sample, length, 2] and t holds one time per sample")
+    x0, x1 = extent if extent is not None else (0.0, float(section.shape[1]))
+    t1 = float(t[-1]) if t.size > 1 and t[-1] > t[0] else float(t[0]) + 1.0
+    fig, ax = plt.subplots()
+    img = ax.imshow(section[:, :, var], extent=[x0, x1, float(t[0]), t1], cmap="jet", aspect="auto", origin="lower", interpolation="nearest")
+    ax.set_xlabel("position along the section")
+    ax.set_ylabel("t")
+    fig.colorbar(img)
+    if path is not None:
+        fig.savefig(path, dpi=dpi)
+        plt.close(fig)
+    return fig
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("what", choices=["plot", "map"])

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi as capi
+from .post import period_map
 from ._capi import (MODELS, SURFACES, STEPPERS, PRECISION_F32, PRECISION_F64, CrdError, Grid, Params,  # noqa: F401
                     RunConfig, check, lib)
 
@@ -350,6 +351,17 @@ class Slab:
         self._check(lib().crd_state_observe(self._h, v.ctypes.data_as(C.POINTER(C.c_double))), "crd_state_observe")
         return v
 
+    def section(self, kind, index=0):
+        """One section of a single-slab context's state, [length, 2] (crd_state_section): kind "row" (along theta at row `index`),
+        "column" (along phi at column `index`), "theta_mean" (the axial profile) or "phi_mean" (the profile around the tube) -- the
+        line an Ensemble of one holding this state records, bit for bit."""
+        kind = _section_kind(kind)
+        g = self.grid
+        length = g.nx if kind in (capi.SECTION_ROW, capi.SECTION_PHI_MEAN) else g.ny
+        v = np.empty((length, 2))
+        self._check(lib().crd_state_section(self._h, kind, int(index), v.ctypes.data), "crd_state_section")
+        return v
+
     # -- RCCL wiring -------------------------------------------------------------------------------------------
     def init_rccl(self, unique_id):
         buf = C.create_string_buffer(bytes(unique_id), 128)
@@ -364,6 +376,15 @@ class Slab:
     def halo_exchange(self, depth=32):
         """One exchange of `depth` ghost rows of both fields with the ring neighbours, outside any step; waits for it."""
         self._check(lib().crd_halo_exchange(self._h, depth), "crd_halo_exchange")
+
+
+def _section_kind(kind):
+    if isinstance(kind, str):
+        name = kind.replace("-", "_")
+        if name not in capi.SECTION_KINDS:
+            raise ValueError("a section is one of %s (got %r)" % (", ".join(sorted(capi.SECTION_KINDS)), kind))
+        return capi.SECTION_KINDS[name]
+    return int(kind)
 
 
 class Ensemble:
@@ -470,12 +491,15 @@ class Ensemble:
         return out
 
     # -- observers ---------------------------------------------------------------------------------------------
-    def observe(self, stride=1, probes=(), maps=False, threshold=0.0, capacity=1024):
+    def observe(self, stride=1, probes=(), maps=False, threshold=0.0, capacity=1024, sections=(), cycles=False, cycle_threshold=0.0):
         """Open the observer (crd_ensemble_observe_begin): from now on step_rk4 records a sample of every member after each stride-th
         step and integrate_adaptive one per call -- field statistics, both fields at the `probes` (i, j) = (theta, phi index) and, with
         maps, the running minimum / maximum of var0 and the activation time (first sample with var0 >= threshold) per grid point -- on
         the device, without a synchronisation.  capacity: samples the record buffer holds.  Returns the observer's info: the sampling
-        blocks per member and the values per field, which state the sums' rounding bound."""
+        blocks per member and the values per field, which state the sums' rounding bound.
+        sections: up to 8 of ("row", j), ("column", i), ("theta_mean",), ("phi_mean",) -- a line of both fields per sample and member
+        (observed_section).  cycles: also count, per grid point, the upward crossings of cycle_threshold by var0 between consecutive
+        samples and keep the times of the first and the last (observed_cycles).  Without either this is crd_ensemble_observe_begin."""
         probes = list(probes)
         opt = capi.ObserveOptions()
         opt.stride, opt.n_probes, opt.maps, opt.threshold = int(stride), len(probes), 1 if maps else 0, float(threshold)
@@ -483,8 +507,43 @@ class Ensemble:
             raise ValueError("at most %d probes" % capi.OBSERVE_MAX_PROBES)
         for q, (i, j) in enumerate(probes):
             opt.probe_i[q], opt.probe_j[q] = int(i), int(j)
-        self._check(lib().crd_ensemble_observe_begin(self._h, C.byref(opt), int(capacity)), "crd_ensemble_observe_begin")
+        sections = [tuple(s) if isinstance(s, (tuple, list)) else (s,) for s in sections]
+        if not sections and not cycles:
+            self._check(lib().crd_ensemble_observe_begin(self._h, C.byref(opt), int(capacity)), "crd_ensemble_observe_begin")
+            return self.observe_info()
+        if len(sections) > capi.OBSERVE_MAX_SECTIONS:
+            raise ValueError("at most %d sections" % capi.OBSERVE_MAX_SECTIONS)
+        ex = capi.ObserveExtras()
+        ex.n_sections, ex.cycles, ex.cycle_threshold = len(sections), 1 if cycles else 0, float(cycle_threshold)
+        for q, sec in enumerate(sections):
+            ex.kind[q], ex.index[q] = _section_kind(sec[0]), int(sec[1]) if len(sec) > 1 else 0
+        self._check(lib().crd_ensemble_observe_begin_with(self._h, C.byref(opt), C.byref(ex), int(capacity)), "crd_ensemble_observe_begin_with")
         return self.observe_info()
+
+    def observed_section_info(self, section):
+        """Section `section` of the open observer: kind, index, length and D -- a mean of n values x lies within D 2^-53 sum|x| / n of
+        the exact mean (0 for the exact kinds)."""
+        kind, index, length, additions = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._check(lib().crd_ensemble_observe_section_info(self._h, int(section), C.byref(kind), C.byref(index), C.byref(length), C.byref(additions)),
+                    "crd_ensemble_observe_section_info")
+        return {"kind": kind.value, "index": index.value, "length": length.value, "additions": additions.value}
+
+    def observed_section(self, section, first=0, count=None):
+        """The recorded lines of section `section`, [sample, member, length, 2] (default: every sample).  Synchronises; one copy."""
+        length = self.observed_section_info(section)["length"]
+        if count is None:
+            count = self.observed_count() - first
+        v = np.empty((count, self.n_members, length, 2))
+        self._check(lib().crd_ensemble_observe_read_section(self._h, int(section), first, count, v.ctypes.data), "crd_ensemble_observe_read_section")
+        return v
+
+    def observed_cycles(self, member):
+        """Member `member`'s cycle maps as they stand, [ny, nx] each: (count of upward crossings, time of the first, time of the last,
+        period map = (t_last - t_first) / (count - 1) where count >= 2, NaN elsewhere)."""
+        count = np.empty((self.ny, self.nx), dtype=np.int32)
+        t_first, t_last = np.empty((self.ny, self.nx)), np.empty((self.ny, self.nx))
+        self._check(lib().crd_ensemble_observe_cycles(self._h, member, count.ctypes.data, t_first.ctypes.data, t_last.ctypes.data), "crd_ensemble_observe_cycles")
+        return count, t_first, t_last, period_map(count, t_first, t_last)
 
     def observe_info(self):
         blocks, values, opt, cap = C.c_int32(), C.c_int64(), capi.ObserveOptions(), C.c_int64()

@@ -623,6 +623,68 @@ int crd_ensemble_observe_end(crd_ensemble *e);
  * CRD_EINVAL for a context that is one of several slabs (no cross-rank reduction). */
 int crd_state_observe(crd_ctx *ctx, double stats[8]);
 
+/* Sections and cycle maps: what a scan's space-time plots and period maps are read from, recorded by the same observer.
+ * A section is one line of values per sample and member, (var0, var1) per point, stored as doubles: recorded on the device by one
+ * more launch per sample (only when sections are configured), on the ensemble's stream behind the finishing launch, with no host wait.
+ *   CRD_SECTION_ROW, index j      nx values: both fields along theta at row j -- exact: the state's value widened to double
+ *   CRD_SECTION_COLUMN, index i   ny values: both fields along phi at column i -- exact
+ *   CRD_SECTION_THETA_MEAN        ny values: the mean over theta of each row (the axial profile)
+ *   CRD_SECTION_PHI_MEAN          nx values: the mean over phi of each column (around the tube: inner against outer equator)
+ * The means accumulate in double whatever the ensemble's precision, without atomics: which lane takes which point and the order of every
+ * addition depend on nx, ny and the precision alone, so a line is bit-identical from run to run, in an ensemble of 1 and of 64 and from
+ * crd_state_section.  theta-mean: a wavefront per row; group c of V consecutive columns (V = 2 in fp64, 4 in fp32: a 16-byte load)
+ * belongs to lane c mod 64, element e of a lane's groups is added in rising order into its accumulator e, the V accumulators are
+ * folded pairwise, the 64 lanes by a shuffle tree: ceil(ceil(nx / V) / 64) + log2 V + 6 additions at most.  phi-mean: a workgroup per
+ * 64 columns; wavefront w adds rows w, w + 4, ... in rising order, the four are combined (0 + 1) + (2 + 3): ceil(ny / 4) + 2 additions.
+ * With D that count + 3 (crd_ensemble_observe_section_info reports it) a mean of n values x satisfies
+ *   |mean - exact| <= D u sum|x| / n, u = 2^-53, also with fsum(x) / n standing for the exact mean
+ * (the + 3: the division by n, and the two roundings of fsum(x) / n; an accumulator's first addition, to zero, is exact and pays for
+ * the terms of second order).  A NaN in a row (column) makes that row's theta-mean (that column's phi-mean) NaN and touches nothing else.
+ * A field whose partial sums are all representable -- a uniform field of values with few significant bits, e.g. any uniform fp32
+ * field on a grid of less than 2^29 points a side -- has means equal to its value exactly.
+ *
+ * Cycle maps (cycles = 1): four more planes per member -- the previous sample's var0, an int32 count, t_first and t_last -- folded at
+ * every sample in the sampling pass itself (the state is read once for statistics, maps and cycles together).  At a point, in double,
+ * every operation rounded once, with x_prev / t_prev the previous sample's value and time:
+ *   d0 = x_prev - cycle_threshold, d1 = x - cycle_threshold; an upward crossing is d0 < 0 && d1 >= 0, at
+ *   tc = t_prev + (t - t_prev) * (-d0 / (d1 - d0)); then count += 1, t_first = tc if it is the first, t_last = tc.
+ * The first sample after begin only stores x_prev.  A NaN compares false: it makes no crossing and becomes the next x_prev.  The
+ * period map is (t_last - t_first) / (count - 1) where count >= 2, formed by the caller. */
+#define CRD_OBSERVE_MAX_SECTIONS 8
+#define CRD_SECTION_ROW 0
+#define CRD_SECTION_COLUMN 1
+#define CRD_SECTION_THETA_MEAN 2
+#define CRD_SECTION_PHI_MEAN 3
+typedef struct crd_observe_extras {
+	int32_t n_sections;                              /* 0 .. CRD_OBSERVE_MAX_SECTIONS, the same for every member */
+	int32_t cycles;                                  /* 1: keep the cycle maps */
+	int32_t kind[CRD_OBSERVE_MAX_SECTIONS];          /* CRD_SECTION_* */
+	int32_t index[CRD_OBSERVE_MAX_SECTIONS];         /* row j or column i; ignored by the two means */
+	double cycle_threshold;
+} crd_observe_extras;
+/* crd_ensemble_observe_begin with sections and cycle maps; extras == NULL is crd_ensemble_observe_begin itself, which launches exactly
+ * what it launched without this interface.  Besides its refusals, CRD_EINVAL before any device work for n_sections outside
+ * 0 .. CRD_OBSERVE_MAX_SECTIONS, an unknown kind, a row or column outside the grid, cycles other than 0 or 1, or a non-finite
+ * cycle_threshold with cycles on.  The record buffer grows by capacity x n_members x (sum of the sections' lengths) x 2 doubles
+ * (CRD_ENOMEM when it cannot be had; nothing is left open).  Everything said of sampling under crd_ensemble_observe_begin holds: the
+ * stride's count over calls, the refusal of a whole call when the room runs out, one sample per crd_ensemble_integrate_adaptive call
+ * at tout -- a failed member gets lines of NaNs, and its state is still folded into its cycle planes by the rule above. */
+int crd_ensemble_observe_begin_with(crd_ensemble *e, const crd_observe_options *opt, const crd_observe_extras *extras, int64_t capacity);
+/* Section `section` of the open observer: its kind and index, its values per field and D of the bound above (0 for the exact kinds).
+ * Any pointer may be NULL.  CRD_EINVAL with no observer open or for a section that was not configured. */
+int crd_ensemble_observe_section_info(const crd_ensemble *e, int section, int32_t *kind, int32_t *index, int64_t *length, int64_t *additions);
+/* Samples first .. first + count - 1 of one section, values[count][n_members][length][2]: synchronises, ONE device-to-host copy.
+ * CRD_EINVAL for a section that was not configured or a range outside the recorded samples. */
+int crd_ensemble_observe_read_section(crd_ensemble *e, int section, int64_t first, int64_t count, double *values);
+/* One member's cycle maps as they stand, ny * nx values each (row-major, theta fastest), any of them NULL: the count of upward
+ * crossings, and the times of the first and of the last (NaN where count = 0).  Synchronises.  CRD_EINVAL when cycles are off. */
+int crd_ensemble_observe_cycles(crd_ensemble *e, int member, int32_t *count, double *t_first, double *t_last);
+/* One section of a single-slab context's state, values[length][2]: the single-slab counterpart of crd_state_observe.  One synchronous
+ * call on the sections kernel with a one-entry descriptor over the context's owned rows, bit-identical to the line of an ensemble of
+ * one holding that state: the axial profile of a large run without downloading it.  CRD_EINVAL for an unknown kind, a row or column
+ * outside the grid, or a context that is one of several slabs. */
+int crd_state_section(crd_ctx *ctx, int kind, int index, double *values);
+
 #ifdef __cplusplus
 }
 #endif
