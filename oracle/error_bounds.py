@@ -1,4 +1,4 @@
-"""Per-point rounding-error bounds for the HIP right-hand side and one RK4 step.  TEST INFRASTRUCTURE ONLY.
+"""Per-point rounding-error bounds for the HIP right-hand side, one RK4 step and one error-controlled attempt.  TEST INFRASTRUCTURE ONLY.
 
 Only tests/ may import this module.  It states, point by point and field by field, how far a correct kernel in a given
 precision may land from a high-precision reference, so that a mistake that is large where it happens fails even when it is
@@ -60,6 +60,68 @@ y0 + dt/6 (k1 + 2 k2 + 2 k3 + k4) on the host):
 
 A stage at a time before tBoundary has exact zeros on the absorbing rows: e_s = 0 there.  The bound is evaluated at the
 reference's stage values; the kernel's differ by dY_s, which moves S and |J| by O(u) of themselves (second order).
+
+One error-controlled attempt (Zonneveld 5(3)4, fused_item<..., EMBED = 2, ...>)
+----------------------------------------------------------------------------
+The propagated solution is classical RK4 (b5 = 0): its reference and per-point bound are the ones above.  The EMBED = 2 body keeps
+no running sums; with d_i = y_i - y0 taken from the stage values y_i = fl(y0 + c_i h k_i) still in registers it forms
+
+    y_new = fma(1/3, fma(2, d2, d1 + d3), fma(h/6, k4, y0)).
+
+Each d_i carries the rounding of its y_i, u (|y0| + c_i h |k_i|), one more u c_i h |k_i| for the rounded step size and one for the
+subtraction where it is not exact; weighted (1, 2, 1)/3 that is 4/3 u |y0| + 3 u h/6 (|k1| + 2 |k2| + 2 |k3|).  On top: d1 + d3, the inner
+fma, the rounded 1/3 and the outer fma round the k1..k3 sum 4 times (7 in all); fma(h/6, k4, y0), the rounded h/6 and the outer fma
+round the k4 term 3 times and y0 twice (10/3 with the 4/3).  The largest count is 7 <= K_ACC = 8: the same constant holds, with one
+spare instead of two.
+
+Fifth stage, at t + 3h/4 (its absorbing flag decided at that time), from
+z5 = fma(5/16, d1, fma(7/16, d2, fma(13/32, d3, fma(-h/32, k4, y0)))) = y0 + h (5/32 k1 + 7/32 k2 + 13/32 k3 - 1/32 k4):
+
+    dY5 = h sum |a5i| e_i + C5 u (|y0| + h sum |a5i| |k_i|),       e5 = stage_error(..., dY5).
+
+C5: y0 takes the innermost fma's rounding, the three outer ones and (5/16 + 7/16 + 13/32) u through the d_i: 5.2; a k_i term takes its
+d_i's three roundings and up to three fmas (k3: 6), k4 the rounded h and four fmas (5).  C5 = 6.
+
+The estimate.  Reference: err = h (2/3 k1 - 2 k2 - 2 k3 - 2 k4 + 16/3 k5) = h sum beta_i k_i, beta = b - b^ of
+oracle/arkode_erk.ZONNEVELD_5_3_4.  Device: e4 = fma(4/3, d1, fma(-4, d2, fma(-2, d3, (-2 h) k4))) when the row's stage 4 runs, and
+err = fma(fl(16/3) h, k5, e4) one iteration later:
+
+    d_err = h sum |beta_i| e_i + K_ERR u h sum |beta_i| |k_i| + K_Y u |y0|.
+
+K_ERR: a term takes its d_i's three roundings (above), the rounded 4/3 (k1 only), the fmas of e4 it sits inside (k1: 1, k2: 2, k3: 3;
+k4: the rounded h, its product and three fmas) and the last fma: k1 6, k2 6, k3 7, k4 6; k5 the rounded 16/3, its product with the
+rounded h and the last fma: 4.  K_ERR = 8 leaves one spare.  K_Y = sum_{i<=3} |beta_i| / c_i = 4/3 + 4 + 2 = 22/3 is the price of
+forming the estimate from stage VALUES: d_i inherits u |y_i| from y_i, an error of the size of y0 in a quantity of the size of h k,
+multiplied by beta_i / c_i.  (The kernel's header names it: "a rounding of y_i itself ... in quantities that are compared with
+rtol |y| + atol".  In fp32 it is the floor of the estimate: 22/3 2^-24 |y0| = 4.4e-7 |y0| per point.)  The reference's order,
+h (2/3 k1 - 2 (k2 + k3 + k4) + 16/3 k5) in the kernel's precision, has no such term and at most 7 roundings per k.
+
+The norm.  dsm_ref = sqrt(sum (err w)^2 / N), w = 1 / (rtol |y0| + atol), over both fields.  The device forms
+fma(rtol, |y0|, atol) from rtol and atol rounded to its precision (positive terms: 3 u) and divides (1 u): K_W = 4, so per point
+
+    delta = w d_err + K_W u |err| w,
+
+and by the triangle inequality of the RMS norm |dsm_gpu - dsm_ref| <= D + sigma (dsm_ref + D), D = sqrt(sum delta^2 / N).
+sigma is the summation: a lane adds its rows' squares in the KERNEL's precision, err2 = fma(eu, eu, fma(ev, ev, err2)), over at most
+one chunk's rows -- 32 at most (fused_chunk_rows without the one-round and 64-row plans, which an attempt does not use;
+ensemble_attempt_plan), so N_ACC = 64 additions of non-negative terms: the sum is off by at most 64 u of itself, the norm by
+32 u.  In fp32 that is 1.9e-6 of dsm (4.8e-7 with the 4-row chunks of a test-sized grid): stated here because nothing else does.
+Then fp64 throughout: the lane's value widened (exact), a 6-level butterfly, one partial per work item, thread t of 256 adding items
+t, t + 256, ..., an 8-level tree, the slabs' sums, the division by N and the root: K_RED = 24 roundings of 2^-53 cover a launch of up
+to 2048 items on 4 slabs, 1.3e-15 of dsm.  Negligible beside 32 u in fp32; of its size in fp64, so it is in the bound:
+
+    sigma = (N_ACC u + K_RED 2^-53) / 2.
+
+Dense output (Hermite, ARK_NORMAL)
+----------------------------------
+theta = (tout - t_n) / h in (0, 1):  y(theta) = h00 y_n + h01 y_{n+1} + h (h10 f_n + h11 f_{n+1}) with the cubic Hermite basis
+(oracle/arkode_erk.hermite_arkode with tau = theta - 1).  y_n is exact input and f_n = f(t_n, y_n) has the RHS bound; the device's
+y_{n+1} is within the attempt's bound B, so its f_{n+1} = f(t_{n+1}, y_{n+1}) is within stage_error(f_{n+1}; dY = B):
+
+    bound = |h01| B + h |h10| e(f_n) + h |h11| stage_error(f_{n+1}; B) + K_HERM u (|h00 y_n| + |h01 y_{n+1}| + h |h10 f_n| + h |h11 f_{n+1}|)
+
+K_HERM = 4 + 2: the kernel's four roundings (h11 f_{n+1}'s product and three fused multiply-adds around it), and two for a
+coefficient, which the host forms in double -- a cubic in theta, times h -- and rounds to the kernel's precision.
 """
 import numpy as np
 
@@ -78,6 +140,14 @@ K_ACC = 8.0
 # [2.6, 1e6] (crd_device.h: reciprocal; relative, so the range's scale does not matter).  fp32: the estimate's error squared
 # (2^-46) plus the refined value's rounding and the residual's, 3 u.
 RHO = {"f64": 2.2e-15, "f32": 3.0 * 2.0 ** -24}
+# The attempt's constants: counted in the docstring ("One error-controlled attempt"), from crd_fused_impl.h: fused_item, EMBED = 2.
+C5 = 6.0          # roundings on the fifth stage's input
+K_ERR = 8.0       # roundings on a term h beta_i k_i of the estimate (largest count 7)
+K_Y = 22.0 / 3.0  # sum_{i<=3} |beta_i| / c_i: the stage values' own rounding, u |y0|, carried into the estimate by d_i = y_i - y0
+K_W = 4.0         # the weight's three roundings and the quotient's
+N_ACC = 64        # additions into a lane's sum of squares in the kernel's precision: 32 rows at most, both fields
+K_RED = 24.0      # fp64 roundings between a lane's sum and dsm
+K_HERM = 6.0      # the interpolant's four roundings + two on a coefficient
 KF, KK, V0, V1, VM2, VM3, K2, KR, KA, EPS = 1.0, 10.0, 1.0, 7.3, 65.0, 500.0, 1.0, 2.0, 0.9, cn.EPSILON
 
 
@@ -192,13 +262,11 @@ def rhs_bound(problem, t, y, precision, j0=0):
     return np.stack([fu, fv], axis=-1), bu, bv
 
 
-def rk4_step_bound(problem, t, dt, y, precision, j0=0):
-    """(ref, bound_u, bound_v) for one classical RK4 step of size dt from (t, y), as rhs_bound (a band's first and last 4 rows
-    are not meaningful)."""
-    P = _Problem(problem)
-    rd = reference_dtype(precision)
+def _rk4_stages(P, t, dt, y0u, y0v, precision, j0):
+    """The four classical stages from (t, y0) in the reference's dtype: (ks, es, ref, bounds) -- the stage derivatives, the bounds on
+    the device's errors in them, the step's reference result and its per-point bounds (the docstring's "One RK4 step")."""
+    rd = y0u.dtype.type
     un = UNIT[precision]
-    y0u, y0v = _split(y, rd)
     a0u, a0v = np.abs(y0u.astype(np.float64)), np.abs(y0v.astype(np.float64))
     h = rd(dt)
     cs, ws = (0.0, 0.5, 0.5, 1.0), (1.0, 2.0, 2.0, 1.0)
@@ -223,7 +291,104 @@ def rk4_step_bound(problem, t, dt, y, precision, j0=0):
         prop = h6 * sum(w * e[f] for w, e in zip(ws, es))
         size = a0 + h6 * sum(w * np.abs(k[f].astype(np.float64)) for w, k in zip(ws, ks))
         bounds.append(prop + K_ACC * un * size)
+    return ks, es, ref, bounds
+
+
+def rk4_step_bound(problem, t, dt, y, precision, j0=0):
+    """(ref, bound_u, bound_v) for one classical RK4 step of size dt from (t, y), as rhs_bound (a band's first and last 4 rows
+    are not meaningful)."""
+    P = _Problem(problem)
+    y0u, y0v = _split(y, reference_dtype(precision))
+    _, _, ref, bounds = _rk4_stages(P, t, dt, y0u, y0v, precision, j0)
     return ref, bounds[0], bounds[1]
+
+
+class AttemptBound:
+    """erk_attempt_bound's result.  state: (ref, bound_u, bound_v) of y_new, as rk4_step_bound's (for check()); err: the reference's
+    per-point estimate (rows, nx, 2) with its per-point bounds err_bound_u / err_bound_v (not weighted); dsm, dsm_bound: the
+    reference's WRMS norm and the bound on |dsm_device - dsm|; f_new_bound(): see hermite_bound."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def erk_attempt_bound(problem, t, h, y, precision, rtol, atol, j0=0):
+    """One Zonneveld 5(3)4 attempt of size h from (t, y): the propagated state's reference and per-point bound, the reference's
+    per-point error estimate and the bound on the device's, and the WRMS norm dsm_ref with the bound on |dsm_device - dsm_ref|
+    (module docstring).  y as rk4_step_bound's; the norm is over all rows given (the whole grid: a band's edge rows are not
+    meaningful).  Returns an AttemptBound."""
+    from oracle.arkode_erk import ZONNEVELD_5_3_4 as tab
+
+    P = _Problem(problem)
+    rd = reference_dtype(precision)
+    un = UNIT[precision]
+    y0u, y0v = _split(y, rd)
+    ks, es, ref, bounds = _rk4_stages(P, t, h, y0u, y0v, precision, j0)
+    hh, hf = rd(h), float(h)
+    a5 = tab["A"][4][:4]
+    beta = [b - b2 for b, b2 in zip(tab["b"], tab["b2"])]
+    t5 = t + tab["c"][4] * hf
+    y0 = (y0u, y0v)
+    a0 = [np.abs(v.astype(np.float64)) for v in y0]
+    ak = [[np.abs(k[f].astype(np.float64)) for f in (0, 1)] for k in ks]
+    Y5 = [y0[f] + hh * sum(rd(a) * k[f] for a, k in zip(a5, ks)) for f in (0, 1)]
+    dY5 = [hf * sum(abs(a) * e[f] for a, e in zip(a5, es)) + C5 * un * (a0[f] + hf * sum(abs(a) * k[f] for a, k in zip(a5, ak))) for f in (0, 1)]
+    k5 = P.rhs(t5, Y5[0], Y5[1], rd, j0)
+    e5 = P.stage_error(precision, t5, Y5[0], Y5[1], j0, dY5[0], dY5[1])
+    ks5, es5 = ks + [k5], es + [e5]
+    ak.append([np.abs(k5[f].astype(np.float64)) for f in (0, 1)])
+    # beta as exact rationals of the reference's dtype: 2/3 and 16/3 are not binary fractions
+    bw = [rd(2) / rd(3), rd(-2), rd(-2), rd(-2), rd(16) / rd(3)]
+    assert all(abs(float(a) - b) <= 1e-15 for a, b in zip(bw, beta)), (bw, beta)
+    err, d_err, delta2, e2 = [], [], 0.0, rd(0)
+    for f in (0, 1):
+        er = hh * sum(b * k[f] for b, k in zip(bw, ks5))
+        de = hf * sum(abs(b) * e[f] for b, e in zip(beta, es5)) + K_ERR * un * hf * sum(abs(b) * k[f] for b, k in zip(beta, ak)) + K_Y * un * a0[f]
+        w = 1.0 / (rtol * a0[f] + atol)
+        delta = w * de + K_W * un * np.abs(er.astype(np.float64)) * w
+        wr = rd(1) / (rd(rtol) * np.abs(y0[f]) + rd(atol))
+        e2 = e2 + np.sum((er * wr) ** 2)
+        delta2 += float(np.sum(delta * delta))
+        err.append(er)
+        d_err.append(de)
+    n = 2 * y0u.size
+    dsm = float(np.sqrt(e2 / n))
+    D = float(np.sqrt(delta2 / n))
+    sigma = 0.5 * (N_ACC * un + K_RED * UNIT["f64"])
+    dsm_bound = D + sigma * (dsm + D)
+
+    def f_new_bound(t_new):
+        """f(t_new, y_new) in the reference's dtype and the bound on the device's f at ITS y_new: (f, e_u, e_v)."""
+        fu, fv = P.rhs(t_new, ref[..., 0], ref[..., 1], rd, j0)
+        eu, ev = P.stage_error(precision, t_new, ref[..., 0], ref[..., 1], j0, bounds[0], bounds[1])
+        return np.stack([fu, fv], axis=-1), eu, ev
+
+    return AttemptBound(state=(ref, bounds[0], bounds[1]), err=np.stack(err, axis=-1), err_bound_u=d_err[0], err_bound_v=d_err[1], dsm=dsm,
+                        dsm_bound=dsm_bound, rms_delta=D, sigma=sigma, f_new_bound=f_new_bound)
+
+
+def hermite_bound(problem, t, h, theta, y, precision, attempt, j0=0):
+    """(ref, bound_u, bound_v) of the dense output at t + theta h inside the accepted step `attempt` (erk_attempt_bound's result for
+    the same t, h, y): the reference-precision cubic Hermite interpolant of the reference's y_n, y_{n+1}, f_n, f_{n+1} and the bound
+    of the module docstring ("Dense output")."""
+    from oracle.arkode_erk import hermite_arkode
+
+    rd = reference_dtype(precision)
+    un = UNIT[precision]
+    f0, e0u, e0v = rhs_bound(problem, t, y, precision, j0)
+    f1, e1u, e1v = attempt.f_new_bound(t + float(h))
+    y0 = np.stack(_split(y, rd), axis=-1)
+    y1, b1u, b1v = attempt.state
+    tau = rd(theta) - rd(1)
+    ref = hermite_arkode(tau, rd(h), y0, y1, f0, f1)
+    th = float(theta)
+    h00, h01 = 1 - (3 * th * th - 2 * th ** 3), 3 * th * th - 2 * th ** 3
+    h10, h11 = th * (1 - th) ** 2, th * th * (th - 1)
+    out = []
+    for f, b1, e0, e1 in ((0, b1u, e0u, e1u), (1, b1v, e0v, e1v)):
+        size = (abs(h00) * np.abs(y0[..., f]) + abs(h01) * np.abs(y1[..., f]) + float(h) * (abs(h10) * np.abs(f0[..., f]) + abs(h11) * np.abs(f1[..., f]))).astype(np.float64)
+        out.append(abs(h01) * b1 + float(h) * (abs(h10) * e0 + abs(h11) * e1) + K_HERM * un * size)
+    return ref, out[0], out[1]
 
 
 def worst(got, ref, bound_u, bound_v, rows=None, j0=0):

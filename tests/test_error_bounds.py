@@ -290,3 +290,229 @@ def test_reciprocal_error_is_its_own_term():
     bare = ref.astype(np.float64).copy()
     bare[..., 1] += 2.0 ** -24.4 * np.abs(w)  # the estimate's own error, as the reciprocal without its Newton step would leave it
     assert eb.worst(bare, ref, bu, bv)["v"][0] > 1.0
+
+
+# ---- one error-controlled attempt (Zonneveld 5(3)4): restatements, honest, powerful ----------------------------------------------
+ATTEMPT_CONFIGS = [
+    ("fhn-torus", co.FHN, co.TORUS, 1.25, {}),
+    ("fhn-torus-varybeta", co.FHN, co.TORUS, 1.25, dict(vary_beta=1, beta_min=0.3, beta_max=1.4)),
+    ("fhn-flat", co.FHN, co.FLAT, 1.25, {}),
+    ("goldbeter-torus", co.GOLDBETER, co.TORUS, 0.4, {}),
+    ("goldbeter-flat-varybeta", co.GOLDBETER, co.FLAT, 0.4, dict(vary_beta=1, beta_min=0.0, beta_max=1.0)),
+    ("diffusion-only", co.GOLDBETER, co.TORUS, 0.4, dict(just_diffusion=1)),
+]  # the six configurations of the device gate (tests/test_gpu_error_bounds.py: CONFIGS), in its order
+ATTEMPT_VALID = 54  # columns a wavefront of the attempt kernel stores (64 lanes, an apron of 5 a side)
+MODELS = {co.FHN: "fhn", co.GOLDBETER: "goldbeter"}
+SURFACES = {co.TORUS: "torus", co.FLAT: "flat"}
+# The step of the attempt gates, host and device alike, as a fraction of crd.stable_dt.
+ATTEMPT_STEP = 0.9
+ATTEMPT_DSM = 0.1  # the norm the tolerances are scaled to: accepted with room to spare, far above the estimate's rounding floor
+
+
+def attempt_problem(case, nx, ny, t_boundary=0.0, **over):
+    _, model, surface, beta, kw = case
+    kw = dict(kw, **over)
+    return co.make_problem(model, surface, nx, L, W, kw.pop("diff", D), kw.pop("beta", beta), ny=ny, t_boundary=t_boundary, **kw)
+
+
+def attempt_step(op):
+    """ATTEMPT_STEP x crd.stable_dt.  A diffusion-only run takes the bound of its diffusion alone: crd.stable_dt adds Goldbeter's
+    reaction rate, which the run does not have, and on a coarse grid that leaves h |lambda| of the diffusion so small that the
+    estimate, a fifth-order quantity, is below fp32's rounding.  1 / stable_dt is linear in D plus that constant, so two calls
+    isolate the diffusion's part."""
+    import crdmodel_amd as crd
+
+    s = lambda diff: crd.stable_dt(crd.make_params(MODELS[op.model], SURFACES[op.surface], op.nx, L, W, diff, 1.0, ny=op.ny))  # noqa: E731
+    if op.just_diffusion:
+        return ATTEMPT_STEP / (1.0 / s(2 * op.diff) - 1.0 / s(op.diff))
+    return ATTEMPT_STEP * s(op.diff)
+
+
+def attempt_state(op, seed, R=np.float64):
+    """state() with grid-scale noise of 0.2 instead of 1e-5: the embedded estimate is a high-order quantity, next to nothing on a
+    smooth field; the noise gives every point an estimate of the same order, far above the fp32 floor of 22/3 u |y0|
+    (error_bounds: K_Y), so that a single column or row carries its share of the norm wherever it lies.  Rounded to R."""
+    y = state(op, seed)
+    y += 0.2 * np.random.default_rng(seed + 1000).standard_normal(y.shape)
+    if op.model == co.GOLDBETER:
+        y = np.abs(y)
+    return y.astype(R)
+
+
+def attempt_bound(op, t, h, y, precision):
+    """(tol, erk_attempt_bound) with rtol = atol = tol scaled on the REFERENCE so that its norm is ATTEMPT_DSM (the norm is
+    proportional to 1 / tol when both scale together), asserted to lie in [1e-3, 0.5]."""
+    first = eb.erk_attempt_bound(op, t, h, y, precision, 1e-4, 1e-4)
+    assert np.isfinite(first.dsm) and first.dsm > 0.0, first.dsm
+    tol = float(np.float32(1e-4 * first.dsm / ATTEMPT_DSM))  # (a float32 value: the same number in both kernels' precisions ... and in print)
+    ab = eb.erk_attempt_bound(op, t, h, y, precision, tol, tol)
+    assert 1e-3 <= ab.dsm <= 0.5, (tol, ab.dsm)
+    return tol, ab
+
+
+def kernel_order_attempt(op, t, h, y, R, rtol, atol, chunk=4, mutant=None, at=None):
+    """fused_item<..., EMBED = 2, ...> in precision R, in its order (crd_fused_impl.h): stage values by one fused multiply-add,
+    d_i = y_i - y0, y_new, z5 and e4 out of them at the row's stage 4, k5 at t + 3/4 h, err = fma(fl(16/3) h, k5, e4), the weights
+    by one fused multiply-add, a lane's sum of squares in R over its chunk's rows (both fields), everything after that in double.
+    Returns (y_new, err, dsm).  mutant (at: its column or row):
+      "stale"   stage 5 of column `at` (a strip's last) reads its east neighbour from y0 instead of z5
+      "twice"   column `at` (>= nx - 1: nx - 1 itself) is counted twice
+      "row"     row `at` (a chunk's first) is not counted
+      "time"    stage 5's absorbing flag is decided at t + h
+      "five"    16/3 is 5"""
+    fma = _fma(R)
+    f = lambda ts, z: kernel_order_rhs(op, ts, z, R)  # noqa: E731
+    h1, h2, h6 = R(h), R(0.5 * h), R(h / 6.0)
+    y0 = y.astype(R)
+    k1 = f(t, y0)
+    y1 = fma(h2, k1, y0)
+    k2 = f(t + 0.5 * h, y1)
+    y2 = fma(h2, k2, y0)
+    k3 = f(t + 0.5 * h, y2)
+    y3 = fma(h1, k3, y0)
+    k4 = f(t + h, y3)
+    d1, d2, d3 = y1 - y0, y2 - y0, y3 - y0
+    ynew = fma(R(1.0 / 3.0), fma(R(2.0), d2, d1 + d3), fma(h6, k4, y0))
+    h32, h2m = R(-1.0 / 32.0) * h1, R(-2.0) * h1
+    z5 = fma(R(5.0 / 16.0), d1, fma(R(7.0 / 16.0), d2, fma(R(13.0 / 32.0), d3, fma(h32, k4, y0))))
+    e4 = fma(R(4.0 / 3.0), d1, fma(R(-4.0), d2, fma(R(-2.0), d3, h2m * k4)))
+    k5 = f(t + (1.0 if mutant == "time" else 0.75) * h, z5)
+    if mutant == "stale":
+        zs = z5.copy()
+        zs[:, (at + 1) % op.nx] = y0[:, (at + 1) % op.nx]
+        k5[:, at] = f(t + 0.75 * h, zs)[:, at]
+    h163 = R(5.0 if mutant == "five" else 16.0 / 3.0) * h1
+    err = fma(h163, k5, e4)
+    e = err / fma(R(rtol), np.abs(y0), R(atol))
+    rows, nx = y0.shape[:2]
+    total = 0.0
+    for j0 in range(0, rows, chunk):
+        acc = np.zeros(nx, dtype=R)
+        for j in range(j0, min(j0 + chunk, rows)):
+            if mutant == "row" and j == at:
+                continue
+            acc = fma(e[j, :, 0], e[j, :, 0], fma(e[j, :, 1], e[j, :, 1], acc))
+        total += float(np.sum(acc.astype(np.float64)))
+        if mutant == "twice":
+            total += float(acc[at])
+    return ynew, err, float(np.sqrt(total / (2 * rows * nx)))
+
+
+def reference_order_attempt(op, t, h, y, rtol, atol):
+    """oracle/arkode_erk.erk_attempt (the reference's order: stage increments, then h sum (b - b^) k) around the float32
+    restatement of the reference's f, and ARKode's WRMS norm, all in float32."""
+    from oracle import arkode_erk as ark
+
+    P, g = _float32_problem(op)
+    f = lambda ts, z: np.stack(cn.rhs(P.model, P.surface, g, op.diff, ts, z[..., 0], z[..., 1], dtype=np.float32, **P.kw), axis=-1)  # noqa: E731
+    tab = {k: ([[np.float32(a) for a in r] for r in v] if k == "A" else v) for k, v in ark.ZONNEVELD_5_3_4.items()}
+    h32 = np.float32(h)
+    k = []
+    for i in range(5):
+        z = y
+        if i > 0:
+            inc = sum(tab["A"][i][j] * k[j] for j in range(i) if tab["A"][i][j] != 0)
+            z = y + h32 * inc
+        k.append(f(t + tab["c"][i] * h, z))
+    f32 = np.float32
+    ynew = y + (h32 / f32(6)) * (k[0] + f32(2) * k[1] + f32(2) * k[2] + k[3])
+    err = h32 * (f32(2.0 / 3.0) * k[0] - f32(2) * (k[1] + k[2] + k[3]) + f32(16.0 / 3.0) * k[4])
+    e = err / (f32(rtol) * np.abs(y) + f32(atol))
+    return ynew, err, float(np.sqrt(np.sum(e * e, dtype=np.float32) / f32(e.size)))
+
+
+ATTEMPT_GRIDS = [(55, 33), (109, 41)]  # strip edges of the attempt kernel (54 columns), a last chunk of one row
+
+
+def attempt_placements(h):
+    """(label, tBoundary - t): absorbing rows off; stage 4 (t + h) free and stage 5 (t + 3/4 h) absorbing; on for all five."""
+    return [("off", 0.0), ("between 3/4 h and h", 0.8 * h), ("on", 2.0 * h)]
+
+
+@pytest.mark.parametrize("case", ATTEMPT_CONFIGS, ids=[c[0] for c in ATTEMPT_CONFIGS])
+def test_attempt_restatements_stay_inside_the_state_estimate_and_norm_bounds(case):
+    """Honest: the attempt in the kernel's order (fp32 and fp64) and in the reference's (fp32, torus) against erk_attempt_bound --
+    y_new and the estimate per point, the WRMS norm as a scalar.  Worst ratios over these cases, as printed (DESIGN.md,
+    "Tolerances"): kernel order state 0.29, estimate 0.63 (Goldbeter; FHN 0.46), norm 0.005; reference order 0.17, 0.12, 0.004.
+    K_ERR = 8 is the count's: Goldbeter needs no empirical constant of its own beyond the K its stage errors already carry.  (On
+    1000 x 65 FHN's v reaches 0.94 of the estimate's bound in the kernel's order: there h k_v is below an ulp of v, every stage value
+    rounds back to v itself, and the K_Y u |y0| term is what is left -- the bound is sharp, not slack.)"""
+    t = 0.3
+    worst = {}
+    for nx, ny in ATTEMPT_GRIDS:
+        h = attempt_step(attempt_problem(case, nx, ny))
+        for label, tb in attempt_placements(h):
+            op = attempt_problem(case, nx, ny, t_boundary=t + tb if tb else 0.0)
+            for precision, R in (("f64", np.float64), ("f32", np.float32)):
+                y = attempt_state(op, nx + ny, R)
+                tol, ab = attempt_bound(op, t, h, y, precision)
+                runs = [("kernel", kernel_order_attempt(op, t, h, y, R, tol, tol))]
+                if precision == "f32" and reference_order_applies(op):
+                    runs.append(("reference", reference_order_attempt(op, t, h, y, tol, tol)))
+                for order, (ynew, err, dsm) in runs:
+                    name = "%s order %s %s %dx%d tB %s" % (order, precision, case[0], nx, ny, label)
+                    ws = eb.check(name + " state", ynew, ab.state)
+                    we = eb.check(name + " estimate", err, (ab.err, ab.err_bound_u, ab.err_bound_v))
+                    rn = abs(dsm - ab.dsm) / ab.dsm_bound
+                    assert rn <= 1.0, (name, dsm, ab.dsm, ab.dsm_bound)
+                    key = (order, precision)
+                    worst[key] = tuple(max(a, b) for a, b in zip(worst.get(key, (0, 0, 0)), (worst_ratio(ws), worst_ratio(we), rn)))
+    for key, w in sorted(worst.items()):
+        print("BOUND attempt %s order %s %s: worst err/bound state %.3g, estimate %.3g, norm %.3g" % (key + (case[0],) + w))
+
+
+MUTANT_GRIDS = [(217, 41), (1000, 65)]  # four strips and a ragged fifth; the largest grid of the device gate
+
+
+@pytest.fixture(scope="module", params=[(g, p) for g in MUTANT_GRIDS for p in ("f64", "f32")], ids=lambda q: "%dx%d-%s" % (q[0] + (q[1],)))
+def mutant_case(request):
+    (nx, ny), precision = request.param
+    R = np.float64 if precision == "f64" else np.float32
+    h = attempt_step(attempt_problem(ATTEMPT_CONFIGS[0], nx, ny))
+    t = 0.3
+    out = {}
+    # absorbing rows off, and for "time" tBoundary between stage 5's time and stage 4's (there the two boundary rows, whose estimate
+    # is then the first-order -2 h k4, carry most of the norm, and an ordinary row's share is next to nothing)
+    for key, tb in (("off", 0.0), ("time", t + 0.8 * h)):
+        op = attempt_problem(ATTEMPT_CONFIGS[0], nx, ny, t_boundary=tb)
+        y = attempt_state(op, 11, R)
+        tol, ab = attempt_bound(op, t, h, y, precision)
+        _, _, dsm = kernel_order_attempt(op, t, h, y, R, tol, tol)
+        assert abs(dsm - ab.dsm) <= ab.dsm_bound
+        out[key] = (op, t, h, y, R, tol, ab, precision)
+    return out
+
+
+@pytest.mark.parametrize("mutant", ["stale", "twice", "row", "time", "five"])
+def test_attempt_mutants_exceed_the_norm_bound(mutant_case, mutant):
+    """Powerful: five mistakes that leave y_new exact and move only the scalar err_last fail the norm bound -- stage 5 reading a
+    stale east neighbour at a strip's last column, column nx - 1 counted twice, a chunk's first row not counted, stage 5's
+    absorbing flag decided at t + h, 16/3 replaced by 5 -- on FHN, torus, at the tolerances of the device gate.
+
+    Reach.  fp64: every mutant exceeds the bound by a factor above 1e9 on every grid.  fp32: the bound has a floor, the stage
+    values' own rounding carried into the estimate (error_bounds: K_Y u |y0| per point), and a single column's or row's share of
+    the norm, about 1 / (2 nx) or 1 / (2 ny) of it, has to stand above that.  At 1000 x 65 (N = 130000 values, the largest grid of
+    the device gate) the margins of mutants 1-3 are 13 (stale), 3.2 (twice), 41 (row); a column's share falls with 1 / nx against
+    a constant floor, so "twice" reaches to about nx = 3000 on this state, N = 400000: the device gate stays below that.  The
+    reach has a lower end too: on narrow grids the step is bound by the reaction rate, h |lambda| of the diffusion is small and
+    the estimate, a fifth-order quantity, lies nearer the floor -- at 55 x 33 in fp32 "twice" and "row" come to 0.4 and 0.2 of the
+    bound and are not seen there (stale 364, time 2500, five 1600 are), which is why the mutants run from 217 columns on."""
+    op, t, h, y, R, tol, ab, precision = mutant_case["time" if mutant == "time" else "off"]
+    at = {"stale": min(ATTEMPT_VALID, op.nx) - 1, "twice": op.nx - 1, "row": 4 * (op.ny // 8)}.get(mutant)
+    ynew, _, dsm = kernel_order_attempt(op, t, h, y, R, tol, tol, mutant=mutant, at=at)
+    eb.check("mutant %s state" % mutant, ynew, ab.state)  # the solution cannot show it
+    ratio = abs(dsm - ab.dsm) / ab.dsm_bound
+    print("BOUND mutant %s %s %dx%d: |dsm - dsm_ref| / bound %.3g" % (mutant, precision, op.nx, op.ny, ratio))
+    assert ratio > 2.0, ratio
+
+
+def test_attempt_bound_on_a_band_is_the_whole_grids():
+    """erk_attempt_bound's per-point parts on a cropped band starting at global row j0, away from the band's edges."""
+    op = attempt_problem(ATTEMPT_CONFIGS[1], 64, 48, t_boundary=1.0)
+    y = attempt_state(op, 2)
+    whole = eb.erk_attempt_bound(op, 0.99, 0.02, y, "f32", 1e-3, 1e-3)
+    for j0 in (-7, 20):
+        rows = np.arange(j0, j0 + 20) % 48
+        band = eb.erk_attempt_bound(op, 0.99, 0.02, y[rows], "f32", 1e-3, 1e-3, j0=j0 % 48)
+        for a, b in zip(band.state + (band.err, band.err_bound_u, band.err_bound_v), whole.state + (whole.err, whole.err_bound_u, whole.err_bound_v)):
+            assert np.allclose(a[5:-5].astype(np.float64), b[rows[5:-5]].astype(np.float64), rtol=1e-9, atol=0)

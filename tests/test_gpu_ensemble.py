@@ -114,6 +114,33 @@ def test_fp32_members_even_and_odd_nx(gpu_device, nx):
     check_ensemble([base, params_like(base, beta=0.6)], 0.0, 0.002, [(0, 5)])
 
 
+def members_in_steps(nx, ny, dt, precision="f64"):
+    """fhn_members' variety with tBoundary in units of dt: none; between two stages of step 5 of the call (stages at 5 / 5.5 / 5.5 /
+    6 dt); beyond the call; at a stage time exactly; at a step's end."""
+    base = crd.make_params("fhn", "torus", nx, 80.0, 20.0, 0.12, 1.25, ny=ny, beta_min=0.7, beta_max=1.7, precision=precision)
+    return [params_like(base, t_boundary=0.0), params_like(base, beta=0.9, t_boundary=5.25 * dt), params_like(base, vary_beta=1, t_boundary=15 * dt),
+            params_like(base, diffusion=0.05, t_boundary=5.5 * dt), params_like(base, vary_beta=1, diffusion=0.08, beta_min=0.5, beta_max=2.0, t_boundary=3 * dt)]
+
+
+@pytest.mark.parametrize("nx,ny", [(230, 33), (300, 9), (390, 21)])
+def test_partly_filled_last_block_of_strips_fp64(gpu_device, nx, ny):
+    """Five, six and seven strips of 56 columns: with sw = 4 wavefronts per block the last block of a row of strips has one, two
+    and three live wavefronts, the others return in front of the body's barriers.  Short ny: 33 (one row more than whole chunks of
+    4, 8, 16 or 32 rows), 9 and 21 (ny % 4 == 1).  Members differ as fhn_members' do; tBoundary falls inside the calls.
+    (ensemble_plan's 32-row chunk is out of reach at test size: it needs B x blocks-per-member >= two rounds of resident blocks,
+    upwards of a thousand blocks, i.e. hundreds of members of a grid this small, each of them then stepped alone twice by
+    check_ensemble.  The grids here get its 4-row chunks.)"""
+    dt = 0.8 * min(crd.stable_dt(p) for p in members_in_steps(nx, ny, 1.0))
+    check_ensemble(members_in_steps(nx, ny, dt), 0.0, dt, [(0, 5), (5, 3)])
+
+
+@pytest.mark.parametrize("nx,ny", [(490, 33), (229, 13)])
+def test_partly_filled_last_block_of_strips_fp32(gpu_device, nx, ny):
+    """fp32: even nx = 490, five strips of 120 columns with two columns per lane; odd nx = 229, five strips of 56 with one."""
+    dt = 0.8 * min(crd.stable_dt(p) for p in members_in_steps(nx, ny, 1.0, "f32"))
+    check_ensemble(members_in_steps(nx, ny, dt, "f32"), 0.0, dt, [(0, 5), (5, 3)])
+
+
 def test_two_members_match_the_oracle(gpu_device):
     nx, dt, n = 32, 0.02, 10
     members = [crd.make_params("fhn", "torus", nx, 80.0, 20.0, 0.12, 1.25, t_boundary=0.1),
