@@ -162,6 +162,17 @@ constexpr bool kCoop = false;
 template <typename Real, int MODEL, int COLS, int STEPS = 2>
 constexpr bool kCoop = sizeof(Real) == 8 && COLS == 1 && (MODEL == CRD_MODEL_GOLDBETER || STEPS == 3);
 #endif
+// The three-step block strip reads row p + 1 out of its ring slot DURING iteration p (ring_read_ahead below) instead of at the top of
+// iteration p + 1, where the wavefront stood still for the reads' LDS latency in front of its first stage -- at two wavefronts per SIMD
+// only one other wavefront can cover that: 8192^2 0.2041 -> 0.2005 ms per step, 4096^2 0.0625 -> 0.0618, same bits
+// (profiles/r07/ring_read_ahead_ab.txt).  The two-step Goldbeter block strip keeps the read at the top (not measured there).
+#if defined(CRD_NO_READ_AHEAD)  // (experiment switch: the row read at the top of its iteration, as in the two-step pipelines)
+template <typename Real, int MODEL, int COLS, int STEPS>
+constexpr bool kReadAhead = false;
+#else
+template <typename Real, int MODEL, int COLS, int STEPS>
+constexpr bool kReadAhead = kCoop<Real, MODEL, COLS, STEPS> && STEPS == 3;
+#endif
 // An edge slot holds the 4 STEPS quantities of an iteration (each step's input row and its three stage values): 64 B at two steps,
 // 96 of 128 at three.
 // (Round 6 tried slots placed on the LDS banks lanes 0 / 63 would have had in the dump area -- lane 63's slot shares its banks with lane
@@ -663,17 +674,43 @@ __device__ __forceinline__ void ring_read(unsigned lds_lane, V &u, V &v)
 template <int VMCNT, int OFF_U, int OFF_V>
 __device__ __forceinline__ void ring_read_with_edges(unsigned lds_lane, double &u, double &v, double2r (&e)[4])
 {
+#ifdef CRD_PROBE_NORINGREAD  // (probe build: what the row's LDS reads and their wait cost at the top of an iteration -- the stages run on whatever the registers held)
+	asm volatile("s_waitcnt vmcnt(%6)" : "+v"(u), "+v"(v), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]) : "n"(VMCNT) : "memory");
+	return;
+#endif
 	asm volatile("s_waitcnt vmcnt(%7)\n\tds_read_b64 %0, %6 offset:%8\n\tds_read_b64 %1, %6 offset:%9\n\ts_waitcnt lgkmcnt(0)"
 	             : "=&v"(u), "=&v"(v), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]) : "v"(lds_lane), "n"(VMCNT), "n"(OFF_U), "n"(OFF_V) : "memory");
 }
 template <int VMCNT, int OFF_U, int OFF_V>
 __device__ __forceinline__ void ring_read_with_edges(unsigned lds_lane, double &u, double &v, double2r (&e)[6])
 {
+#ifdef CRD_PROBE_NORINGREAD
+	asm volatile("s_waitcnt vmcnt(%8)" : "+v"(u), "+v"(v), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]) : "n"(VMCNT) : "memory");
+	return;
+#endif
 	asm volatile("s_waitcnt vmcnt(%9)\n\tds_read_b64 %0, %8 offset:%10\n\tds_read_b64 %1, %8 offset:%11\n\ts_waitcnt lgkmcnt(0)"
 	             : "=&v"(u), "=&v"(v), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]) : "v"(lds_lane), "n"(VMCNT), "n"(OFF_U), "n"(OFF_V) : "memory");
 }
 template <int VMCNT, int OFF_U, int OFF_V, typename V, int N>
 __device__ __forceinline__ void ring_read_with_edges(unsigned, V &, V &, double2r (&)[N]) {}  // (COOP is fp64, one column per lane)
+// The read of the NEXT iteration's row (kReadAhead), issued and not waited for: the wait on vmcnt is the slot's.  What retires the read
+// is the `s_waitcnt lgkmcnt(0)` in front of the barrier of the SAME iteration (edge_exchange); up to there nothing may name the registers
+// (tools/kernel_regs.py: async_lds_read_hazards stops the build if something does).
+template <int VMCNT, int OFF_U, int OFF_V>
+__device__ __forceinline__ void ring_read_ahead(unsigned lds_lane, double &u, double &v)
+{
+	asm volatile("s_waitcnt vmcnt(%3)\n\tds_read_b64 %0, %2 offset:%4\n\tds_read_b64 %1, %2 offset:%5" : "=&v"(u), "=&v"(v) : "v"(lds_lane), "n"(VMCNT), "n"(OFF_U), "n"(OFF_V) : "memory");
+}
+// ... and the top of the next iteration: the wait is for the edge reads in flight (edge_exchange).  The row's data landed at the previous
+// iteration's barrier wait already; its registers are operands here only so that they stay live, and tied to this place, up to it.
+__device__ __forceinline__ void ring_row_landed(double &u, double &v, double2r (&e)[6])
+{
+	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(u), "+v"(v), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]) : : "memory");
+}
+template <int VMCNT, int OFF_U, int OFF_V, typename V>
+__device__ __forceinline__ void ring_read_ahead(unsigned, V &, V &) {}  // (kReadAhead is fp64, one column per lane, three steps)
+template <typename V, int N>
+__device__ __forceinline__ void ring_row_landed(V &, V &, double2r (&)[N]) {}
 // LDS bytes of a block's rings
 template <typename Real, int COLS, int STEPS = 2>
 constexpr int kRingBytes = kMaxWavesPerBlock * kRingRowsOf<typename LaneValue<Real, COLS>::type, STEPS> * 2 * kLanes * COLS * (int)sizeof(Real);
@@ -719,6 +756,14 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	// iterations and the stores of kRingRows iterations -- none of the latter while the pipeline still fills.
 	constexpr int kWaitFill = (kRingRows - 1) * 2 * G1, kWaitSteady = kWaitFill + 2 * kRingRows;
 	static_assert(kWaitSteady <= 63, "vmcnt is six bits");
+	// (kReadAhead) Row p + 1 is read in iteration p, behind that iteration's fill (and its first step's stages) and in front of its stores.  Its slot was filled at iteration
+	// p + 1 - kRingRows (or, for the first kRingRows rows, in front of the loop); issued after that fill are the stores of that iteration,
+	// fill and stores of the kRingRows - 2 iterations p + 2 - kRingRows .. p - 1, and the fill of iteration p: kRingRows - 1 fills as before,
+	// and the stores of kRingRows - 1 iterations, one fewer than at the top of iteration p + 1 -- this iteration's own are not out yet.
+	// While fewer than kRingRows - 1 of those iterations stored (p + 1 - kRingRows < FILL) the count is the fills alone, kWaitFill.
+	constexpr bool AHEAD = kReadAhead<Real, MODEL, COLS, STEPS>;
+	constexpr int kWaitAhead = kWaitFill + 2 * (kRingRows - 1);
+	static_assert(kWaitAhead <= 63, "vmcnt is six bits");
 	const int lane = threadIdx.x & (kLanes - 1);
 	const int nx = s.nx;
 	// column of lane 0 (before wrapping), and this lane's place in what the apron surrounds: the wavefront's 64 lanes -- or the block's
@@ -821,6 +866,8 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 #pragma unroll
 	for (int k = 0; k < kRingRows; k++) fill((jbase + k < jlast) ? jbase + k : jlast, k * SLOT);
 	int jn = (jbase + kRingRows < jlast) ? jbase + kRingRows : jlast;  // the row the next fill takes (the tail re-reads the last valid row)
+	// (kReadAhead) the first row's reads go out here: kRingRows - 1 fills behind its own
+	if constexpr (AHEAD) ring_read_ahead<kWaitFill, 0, RB>(ring_lane, P[0].u0[0], P[0].v0[0]);
 	Real pb = brow[jbase];                                            // b(j) of the row the next iteration takes
 	int trip_byte = 0;                                                // ring byte offset of the slots of this trip of four iterations
 	unsigned ring_trip = ring_lane;
@@ -877,6 +924,12 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			nv = stage_fma(h6, dv, Q.aV[S4]);
 		}
 	};
+	auto next_trip = [&]() {
+		if constexpr (kRingRows > M) {
+			trip_byte = (trip_byte + M * SLOT) & (kRingRows * SLOT - 1);
+			ring_trip = ring_lane + (unsigned)trip_byte;
+		}
+	};
 	auto iteration = [&](int m, auto kk, auto fed_c) {
 		constexpr int FED = decltype(fed_c)::value;  // iterations before this one, if fewer than FILL
 		constexpr int K = decltype(kk)::value;
@@ -894,9 +947,15 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 #pragma unroll
 		for (int n = 0; n < STEPS; n++) b4[n] = P[n].bq[S4];
 		// row p out of its ring slot (filled kRingRows iterations ago) ...
-		if (m < FILL + kRingRows) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitFill) : "memory");  // (fewer operations in flight while no rows come out yet)
+		if (!AHEAD && m < FILL + kRingRows) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitFill) : "memory");  // (fewer operations in flight while no rows come out yet)
 		V E[STEPS][4];
-		if constexpr (COOP) {
+		if constexpr (AHEAD) {
+			// ... which the previous iteration read ahead (landed at its barrier wait); the wait is for the neighbours' edge values
+			ring_row_landed(P[0].u0[S0], P[0].v0[S0], edge);
+#pragma unroll
+			for (int n = 0; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
+			edge_publish<(K & 1) * kEdgeParityBytes<STEPS>>(edge_pub, P[0].u0[S0]);
+		} else if constexpr (COOP) {
 			// ... together with the neighbours' edge values, whose reads the previous iteration issued behind its barrier
 			ring_read_with_edges<kWaitSteady, S0 * SLOT, S0 * SLOT + RB>(ring_trip, P[0].u0[S0], P[0].v0[S0], edge);
 #pragma unroll
@@ -913,11 +972,21 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 #endif
 		jn = (jn < jlast) ? jn + 1 : jlast;
 		pb = brow[(p < jlast) ? p + 1 : jlast];
+		if constexpr (AHEAD && K == M - 1) next_trip();  // (the read ahead below is the next trip's first slot)
 		V nu, nv;
 		if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);  // (see the stores below)
+		// (kReadAhead) Row p + 1 out of its ring slot -- the next one of this trip, or the first of the next -- straight into the registers it
+		// lives in: the first step's stages are the last to need row p - 3, whose slot that is, so the read goes out behind them, costs no
+		// second register set, and lands under the stages of the later steps (this iteration's barrier wait, edge_exchange, retires it).  (Behind the item's last row it reads the slot the tail's
+		// fills keep rewriting: one read per iteration, whatever the row.)
+		[[maybe_unused]] auto read_ahead = [&]() {
+			if (m + 1 < FILL + kRingRows) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitFill) : "memory");
+			ring_read_ahead<kWaitAhead, ((K + 1) % M) * SLOT, ((K + 1) % M) * SLOT + RB>(ring_trip, P[0].u0[(K + 1) % M], P[0].v0[(K + 1) % M]);
+		};
 #ifdef CRD_PROBE_NOMATH  // (probe build: the launch as a copy -- its memory traffic alone)
 		nu = P[0].u0[S0] + (V)b4[0];
 		nv = P[0].v0[S0] + (V)b4[STEPS - 1];
+		if constexpr (AHEAD) read_ahead();
 #else
 		// step n of the launch: the new row p - 4 (n + 1), which is the next pipeline's newest row (same slot: rows shifted by 4)
 		for_sequence(
@@ -934,6 +1003,7 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			    }
 			    constexpr int live = FED - 8 * N < 0 ? 0 : (FED - 8 * N > 8 ? 8 : FED - 8 * N);
 			    stages(P[N], p - kApron * N, kk, std::integral_constant<int, live>{}, 4 * N, b4[N], nu, nv, E[N], std::integral_constant<int, 4 * N>{});
+			    if constexpr (AHEAD && N == 0) read_ahead();
 		    },
 		    std::make_integer_sequence<int, STEPS>{});
 #endif
@@ -970,24 +1040,18 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		// iteration needs of it go out at once and land while that iteration waits for its row
 		if constexpr (COOP) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS>>(edge_con, edge);
 	};
-	auto next_trip = [&]() {
-		if constexpr (kRingRows > M) {
-			trip_byte = (trip_byte + M * SLOT) & (kRingRows * SLOT - 1);
-			ring_trip = ring_lane + (unsigned)trip_byte;
-		}
-	};
 	int m = 0;
 	for_sequence(  // the pipeline fills (a chunk has at least one row: FILL iterations and more)
 	    [&](auto i) {
 		    constexpr int I = decltype(i)::value;
 		    iteration(I, std::integral_constant<int, I % M>{}, i);
-		    if constexpr (I % M == M - 1) next_trip();
+		    if constexpr (!AHEAD && I % M == M - 1) next_trip();  // (kReadAhead: the trip's last iteration moves on itself, in front of its read ahead)
 	    },
 	    std::make_integer_sequence<int, FILL>{});
 	m = FILL;
 	for (; m + M - 1 < niter; m += M) {
 		for_sequence([&](auto k) { iteration(m + decltype(k)::value, k, std::integral_constant<int, FILL>{}); }, std::make_integer_sequence<int, M>{});
-		next_trip();
+		if constexpr (!AHEAD) next_trip();
 	}
 	for_sequence(
 	    [&](auto k) {
@@ -995,7 +1059,14 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	    },
 	    std::make_integer_sequence<int, M - 1>{});
 	// the fills still in flight write LDS: they must have landed before the wavefront ends and its LDS goes to the next workgroup
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	// (... and the last read ahead, which no iteration takes: its registers pass through here, or the compiler would hand them to something
+	// else while the read is in flight)
+	if constexpr (AHEAD)
+		asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
+		             : "+v"(P[0].u0[0]), "+v"(P[0].u0[1]), "+v"(P[0].u0[2]), "+v"(P[0].u0[3]), "+v"(P[0].v0[0]), "+v"(P[0].v0[1]), "+v"(P[0].v0[2]), "+v"(P[0].v0[3])
+		             :
+		             : "memory");
+	else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // ABSORB = false: no stage of the step has t < tBoundary (every launch after the switch-off time, every launch of a run with

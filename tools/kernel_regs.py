@@ -103,7 +103,12 @@ def async_lds_read_hazards(body):
     two asm blocks -- at the loop's back edge, say -- the copy would read a register whose data has not landed (round 6 met exactly that
     when it tried the same for the ring reads: results changed from run to run).  Nothing in the language forbids it, so the build
     checks the assembly: from each such read, along fall-through and taken branches, up to the waiting asm block, no instruction may
-    mention a destination register."""
+    mention a destination register.
+
+    The three-step block strip's read of the NEXT row (ring_read_ahead: two ds_read_b64 issued behind the first step's stages, retired
+    by the wait in front of the same iteration's barrier in edge_exchange) is found the same way -- any ds_read of an asm block without
+    its own wait -- and twice did its work while that read was being written: a second register set that the compiler copied with the
+    read in flight, and the read behind an item's last row, whose registers, dead to the compiler, went to the next stage's temporaries."""
     n = len(body)
     label_at = {}
     for k, ln in enumerate(body):
