@@ -219,6 +219,8 @@ _SIGNATURES = {
     "crd_ensemble_download": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "crd_ensemble_step_rk4": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64]),
     "crd_ensemble_step_rk4_timed": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_double)]),
+    "crd_ensemble_set_steps_per_launch": (C.c_int, [_vp, C.c_int]),
+    "crd_ensemble_get_steps_per_launch": (C.c_int, [_vp]),
     "crd_ensemble_synchronize": (C.c_int, [_vp]),
     "crd_ensemble_max_abs": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "crd_ensemble_integrate_adaptive": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(AdaptiveOptions), C.POINTER(AdaptiveStats),

@@ -22,6 +22,9 @@ struct crd_ensemble {
 	int nx = 0, ny = 0;
 	size_t real_size = 8;
 	EnsemblePlan plan;
+	int steps_per_launch = 1;              // crd_ensemble_set_steps_per_launch: 1, or 2 (pairs, crd_ensemble_multi.hip)
+	bool pair_planned = false;
+	EnsemblePlan pair_plan;                // the pair launches' plan: fixed at the first crd_ensemble_set_steps_per_launch(e, 2)
 	std::vector<EnsembleMember> members;   // host copy of the descriptor table
 	EnsembleMember *table = nullptr;       // ... on the device
 	std::vector<void *> allocs;            // every device allocation but the table
@@ -340,24 +343,81 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 	st.nchunks = e->plan.nchunks;
 	st.member_blocks = st.nsb * st.nchunks;
 	st.nblocks = st.member_blocks * e->n;
+	const bool pairs = e->steps_per_launch == 2;
+	EnsemblePair pr{};  // the same constants on the pair launches' own plan
+	if (pairs) {
+		pr.step = st;
+		pr.step.nstrips = e->pair_plan.nstrips;
+		pr.step.sw = e->pair_plan.sw;
+		pr.step.nsb = e->pair_plan.nsb;
+		pr.step.chunk = e->pair_plan.chunk;
+		pr.step.nchunks = e->pair_plan.nchunks;
+		pr.step.member_blocks = pr.step.nsb * pr.step.nchunks;
+		pr.step.nblocks = pr.step.member_blocks * e->n;
+	}
 	const double cs[4] = {0.0, 0.5, 0.5, 1.0};
 	double latest_boundary = -INFINITY;  // the absorbing rows are on at stage time t exactly when t < some member's tBoundary
 	for (const crd_params &p : e->p) latest_boundary = std::max(latest_boundary, p.t_boundary);
-	for (int64_t s = 0; s < nsteps; s++) {
+	const bool can_absorb = e->model != dev::kModelDiffusionOnly;
+	for (int64_t s = 0; s < nsteps;) {
 		const double t = t0 + (double)s * dt;  // as run_steps forms it
 		bool absorb = false;
 		for (int k = 0; k < 4; k++) {
 			st.t_stage[k] = t + cs[k] * dt;  // as make_fused_call forms it
 			absorb = absorb || st.t_stage[k] < latest_boundary;
 		}
-		st.src = e->cur;
-		ENS_TRY(e, launch_ensemble_step(e->precision, e->model, e->plan.cols, absorb && e->model != dev::kModelDiffusionOnly, e->table, st, e->stream));
-		e->cur = 1 - e->cur;
-		if (ob.open && ++ob.steps % ob.opt.stride == 0)
-			if (int rc = observer_sample(e, t0 + (double)(s + 1) * dt)) return rc;  // the time as the next step's t is formed
+		// Two steps in one launch where the setting asks for pairs, two steps are left, and -- an observer open -- the first of them does
+		// not complete a stride: a pair never straddles a sample.
+		int taken = 1;
+		if (pairs && s + 2 <= nsteps && !(ob.open && (ob.steps + 1) % ob.opt.stride == 0)) {
+			const double t2 = t0 + (double)(s + 1) * dt;  // the second step's t as the next single step's is formed
+			for (int k = 0; k < 4; k++) {
+				pr.step.t_stage[k] = st.t_stage[k];
+				pr.t_stage2[k] = t2 + cs[k] * dt;
+				absorb = absorb || pr.t_stage2[k] < latest_boundary;
+			}
+			pr.step.src = e->cur;
+			ENS_TRY(e, launch_ensemble_pair(e->precision, e->model, e->pair_plan.cols, absorb && can_absorb, e->table, pr, e->stream));
+			taken = 2;
+		} else {
+			st.src = e->cur;
+			ENS_TRY(e, launch_ensemble_step(e->precision, e->model, e->plan.cols, absorb && can_absorb, e->table, st, e->stream));
+		}
+		e->cur = 1 - e->cur;  // (a pair flips once: its first step's state never reaches memory)
+		s += taken;
+		if (ob.open && (ob.steps += taken) % ob.opt.stride == 0)
+			if (int rc = observer_sample(e, t0 + (double)s * dt)) return rc;  // the time as the next step's t is formed
 	}
 	return CRD_OK;
 }
+
+int crd_ensemble_set_steps_per_launch(crd_ensemble *e, int steps)
+{
+	if (!e) return CRD_EINVAL;
+	if (steps != 1 && steps != 2) return efail(e, CRD_EINVAL, "steps per launch must be 1 or 2 (got " + std::to_string(steps) + ")");
+	if (steps == 2) {
+		static_assert(CRD_ENSEMBLE_PAIR_MIN_ROWS == kEnsemblePairMinRows, "crd.h states the pair kernels' bound");
+		if (e->ny < kEnsemblePairMinRows)
+			return efail(e, CRD_EINVAL, "two steps per launch need members of at least " + std::to_string(kEnsemblePairMinRows) + " rows (CRD_ENSEMBLE_PAIR_MIN_ROWS); these have " +
+			                                std::to_string(e->ny));
+#ifdef CRD_NO_ENSEMBLE_PAIRS
+		return efail(e, CRD_EINVAL, "this build of libcrd carries no pair kernels (built without the check of their assembly: make KERNEL_TABLE=0)");
+#else
+		if (!e->pair_planned) {
+			ENS_TRY(e, hipSetDevice(e->device));
+			EnsemblePlan plan;
+			ENS_TRY(e, ensemble_pair_plan(e->precision, e->model, e->nx, e->ny, e->n, &plan));
+			if ((long)e->n * plan.nsb * plan.nchunks > INT32_MAX) return efail(e, CRD_EINVAL, "too many work items for one launch");
+			e->pair_plan = plan;
+			e->pair_planned = true;
+		}
+#endif
+	}
+	e->steps_per_launch = steps;
+	return CRD_OK;
+}
+
+int crd_ensemble_get_steps_per_launch(const crd_ensemble *e) { return e ? e->steps_per_launch : CRD_EINVAL; }
 
 int crd_ensemble_step_rk4_timed(crd_ensemble *e, double t0, double dt, int64_t nsteps, double *ms_total)
 {

@@ -52,6 +52,25 @@ hipError_t launch_ensemble_planes_to_aos(int precision, int dst_is_f64, const vo
 hipError_t launch_ensemble_max_abs(int precision, const EnsembleMember *table, int members, int src, size_t n, double *out_dev, hipStream_t s);
 
 
+// ---- two steps per launch (crd_ensemble_multi.hip; crd_ensemble.cpp: crd_ensemble_set_steps_per_launch) ----
+
+// What one launch of the ensemble pair shares over its members: the first step's constants and geometry (the pair's own plan), and the
+// second step's stage times, t + dt + c_k dt with t + dt formed as the next single step's t is (t0 + (s + 1) dt).
+struct EnsemblePair {
+	EnsembleStep step;
+	double t_stage2[4];
+};
+// The smallest member height a pair runs on: the two-step body's own conditions (a row index wraps at most once: ny >= 8; an item's
+// pipeline -- its chunk and 16 apron rows -- touches fewer than 2 ny rows: a one-row chunk from ny = 9 on).  CRD_ENSEMBLE_PAIR_MIN_ROWS.
+constexpr int kEnsemblePairMinRows = 9;
+// Fixed plan of the pair launches (the two-step apron: 48 valid columns per wavefront, 112 with two columns per lane, the block as the
+// strip for Goldbeter in fp64).  Needs the device.  hipErrorInvalidValue below kEnsemblePairMinRows rows.
+hipError_t ensemble_pair_plan(int precision, int model, int nx, int ny, int members, EnsemblePlan *plan);
+// Two RK4 steps of every member: `absorb` selects the instantiation with the absorbing-row selects (some member has t_stage < tBoundary
+// at some of the pair's eight stages).
+hipError_t launch_ensemble_pair(int precision, int model, int cols, bool absorb, const EnsembleMember *table, const EnsemblePair &e, hipStream_t s);
+
+
 // ---- error-controlled integration (crd_ensemble_adaptive.hip; crd_ensemble.cpp: crd_ensemble_integrate_adaptive) ----
 
 // One member's attempt of a round: an entry of a table in device memory, written by the host before each round's launch and read

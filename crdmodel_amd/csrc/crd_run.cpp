@@ -41,6 +41,7 @@ struct Options {
 	bool decomp_mpi = false;
 	// --ensemble KEY=v1,v2,...: members that differ in one or more parameters, zipped over the lists (run_ensemble)
 	std::vector<std::pair<std::string, std::vector<double>>> ensemble;
+	int ensemble_steps = 0;  // --ensemble-steps 1|2: RK4 steps per launch of the ensemble (crd_ensemble_set_steps_per_launch); 0: not given
 	// --observe STRIDE [--probe i,j]... [--observe-maps THRESHOLD]: the ensemble's observer (crd_ensemble_observe_*)
 	bool observe = false, observe_maps = false;
 	long long observe_stride = 0;
@@ -61,10 +62,12 @@ struct Options {
 		          << " --model fhn|goldbeter --surface torus|flat [--gpus G] [--devices D] [--dt DT] [--stepper auto|staged|fused]\n"
 		             "       [--precision 64|32] [--adaptive|--adaptive-rk43|--fixed] [--binary|--binary-only] [--ref-steady-state] [--decomp D0xD1|mpi [--block-contexts]]\n"
 		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary=V1,V2,... (repeatable)]\n"
+		             "       [--ensemble-steps 1|2]\n"
 		             "       [--observe STRIDE [--probe I,J (repeatable)] [--observe-maps THRESHOLD]\n"
 		             "                         [--section row:J|column:I|theta-mean|phi-mean (repeatable)] [--observe-cycles THRESHOLD]]\n"
 		             "       <Config file path>\n"
 		             "  --ensemble: fixed-step RK4, or error-controlled (each member its own ARKode-style steps) when the ini asks for [Solver] adaptive = 1\n"
+		             "  --ensemble-steps: fixed steps one launch takes (2: pairs, the same bits as single steps; members of at least 9 rows; not with adaptive = 1)\n"
 		             "  --observe: with --ensemble, member_<k>/observables.txt -- time, min / max / sum / sum of squares of both fields and the probes' values\n"
 		             "             after every STRIDE-th step (error-controlled: at every output), recorded on the GPU; --observe-maps: also\n"
 		             "             amplitude_map.npy and activation_time.npy (first sample with var0 >= THRESHOLD); --section: also\n"
@@ -128,6 +131,7 @@ void parse_ensemble(const std::string &arg, Options *o)
 void check_ensemble_options(const Options &o)
 {
 	if (o.ensemble.empty()) {
+		if (o.ensemble_steps) usage_error("--ensemble-steps sets an ensemble's steps per launch: it needs --ensemble");
 		if (o.observe) usage_error("--observe records an ensemble's members: it needs --ensemble");
 		if (!o.probes.empty()) usage_error("--probe belongs to --observe, which needs --ensemble");
 		if (o.observe_maps) usage_error("--observe-maps belongs to --observe, which needs --ensemble");
@@ -339,6 +343,8 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 	if (cfg.adaptive == 2)
 		usage_error("--ensemble integrates error-controlled with ARKode's pair only: the ini asks for [Solver] adaptive = 2 (RK4(3); pass --fixed, or set adaptive = 1)");
 	const bool adaptive = cfg.adaptive == 1;
+	if (adaptive && o.ensemble_steps)
+		usage_error("--ensemble-steps sets the steps of a fixed-step launch: the ini asks for [Solver] adaptive = 1, which takes attempts, not steps (pass --fixed)");
 	if (cfg.n_gpus > 1) usage_error("--ensemble runs on one GPU: the ini asks for [Solver] gpus = " + std::to_string(cfg.n_gpus) + " (pass --gpus 1)");
 	const int B = (int)o.ensemble[0].second.size();
 	std::vector<crd_run_config> mc((size_t)B, cfg);
@@ -376,6 +382,11 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		std::cerr << "\nCRD_ERROR: crd_ensemble_create failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(nullptr) << "\n\n";
 		return 1;
 	}
+	if (o.ensemble_steps && (rc = crd_ensemble_set_steps_per_launch(ens, o.ensemble_steps)) != CRD_OK) {
+		std::cerr << "\nCRD_ERROR: --ensemble-steps " << o.ensemble_steps << ": " << crd_ensemble_last_error(ens) << "\n\n";
+		crd_ensemble_destroy(ens);
+		return 1;
+	}
 	crd_grid g;
 	crd_ensemble_info(ens, nullptr, &g);
 	if (!o.quiet) {
@@ -392,7 +403,8 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 			          << "\n   atol = " << cfg.atol << "\n";
 		else
 			std::cout << "   integrator = classical RK4 on GPU, dt = " << dt << " (" << steps_per_output << " steps per output; "
-			          << (dt_member < 0 ? std::string("from [Solver] dt / --dt") : "the smallest member's dtSafety x stable dt: member " + std::to_string(dt_member)) << ")\n";
+			          << (dt_member < 0 ? std::string("from [Solver] dt / --dt") : "the smallest member's dtSafety x stable dt: member " + std::to_string(dt_member)) << ")\n"
+			          << (crd_ensemble_get_steps_per_launch(ens) == 2 ? "   two steps per launch\n" : "");
 	}
 
 	std::vector<crd_writer *> wr((size_t)B, nullptr);
@@ -601,6 +613,11 @@ int main(int argc, char *argv[])
 			else if (s == "--ref-steady-state") o.ref_steady_state = true;
 			else if (s == "--block-contexts") o.block_contexts = true;
 			else if (s == "--ensemble") parse_ensemble(next(), &o);
+			else if (s == "--ensemble-steps") {
+				const std::string v = next();
+				o.ensemble_steps = v == "1" ? 1 : v == "2" ? 2 : 0;
+				if (!o.ensemble_steps) usage_error("--ensemble-steps takes 1 or 2 (got '" + v + "')");
+			}
 			else if (s == "--observe") {
 				const std::string v = next();
 				char *end = nullptr;

@@ -466,6 +466,16 @@ class Ensemble:
     def synchronize(self):
         self._check(lib().crd_ensemble_synchronize(self._h), "crd_ensemble_synchronize")
 
+    def set_steps_per_launch(self, n):
+        """RK4 steps one launch of step_rk4 takes: 1 (the default) or 2 -- pairs, with the bits of single steps
+        (crd_ensemble_set_steps_per_launch).  CrdError for anything else, and for 2 on members of fewer than
+        CRD_ENSEMBLE_PAIR_MIN_ROWS rows; the setting is then unchanged."""
+        self._check(lib().crd_ensemble_set_steps_per_launch(self._h, int(n)), "crd_ensemble_set_steps_per_launch")
+
+    @property
+    def steps_per_launch(self):
+        return int(lib().crd_ensemble_get_steps_per_launch(self._h))
+
     def max_abs(self):
         """max |var0| per member (a list; non-finite for a member that blew up)."""
         v = (C.c_double * self.n_members)()

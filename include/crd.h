@@ -544,6 +544,18 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 /* ... bracketed by events on the ensemble's stream; blocks until done; ms_total: device time of the batch. */
 int crd_ensemble_step_rk4_timed(crd_ensemble *e, double t0, double dt, int64_t nsteps, double *ms_total);
 int crd_ensemble_synchronize(crd_ensemble *e);
+/* RK4 steps one launch of crd_ensemble_step_rk4 takes: 1 (the default) or 2.  With 2, a call steps PAIRS from its start -- both steps
+ * of every member in one launch, the state across memory once per two steps -- and a single step for an odd remainder; with an observer
+ * open a pair never straddles a sample (the step that completes a stride is taken alone).  Results, samples and sample times are those
+ * of single steps bit for bit: a pair is the sequence of two single steps per point.  The two-step pipeline needs room in phi (an item
+ * touches its rows and 16 apron rows, fewer than 2 ny in all): CRD_EINVAL for steps = 2 on members of fewer than
+ * CRD_ENSEMBLE_PAIR_MIN_ROWS rows, and for any steps other than 1 or 2 (crd_ensemble_last_error says which); the setting is then
+ * unchanged.  The first call with 2 plans the pair launches (a fixed rule of grid, precision, model and member count).  A library built
+ * without the build-time check of the pair kernels' assembly (make KERNEL_TABLE=0) carries no pair kernels and refuses 2 likewise.
+ * crd_ensemble_integrate_adaptive takes attempts, not steps, and is not affected. */
+#define CRD_ENSEMBLE_PAIR_MIN_ROWS 9
+int crd_ensemble_set_steps_per_launch(crd_ensemble *e, int steps);
+int crd_ensemble_get_steps_per_launch(const crd_ensemble *e); /* 1 or 2; CRD_EINVAL (negative) for NULL */
 /* max |var0| of every member, per_member[0 .. n_members) (non-finite for a member that blew up; synchronises).  The blow-up guard of
  * each member's run (its ARKode call's failure, src/FHNmodel_torus.cpp:424-435). */
 int crd_ensemble_max_abs(crd_ensemble *e, double *per_member);

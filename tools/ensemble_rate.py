@@ -7,6 +7,13 @@ asynchronous, one synchronisation at the end).  Both device-synchronised, warmed
 of the fp64 state); `in_infinity_cache` says whether the members' two state buffers (2 x 16 B per point each) fit the 256 MiB cache.
 
     python tools/ensemble_rate.py [--members 1,4,16,64] [--window 1.0] [--json OUT]
+
+--steps-per-launch 1,2 measures the ENSEMBLE alone under each setting (Ensemble.set_steps_per_launch: single steps, pairs) in one
+process: after a warm-up of --window seconds, --batches batches (at least 9) per setting, the settings interleaved batch by batch, each
+batch timed by events on the ensemble's stream; reports the median per-step time, the batches' spread (min .. max) and the ratio of
+the medians.  --precision 64|32.
+
+    python tools/ensemble_rate.py --steps-per-launch 1,2 [--precision 32] [--batches 11] [--cases fhn] [--members 16]
 """
 import argparse
 import json
@@ -99,13 +106,73 @@ def measure(case, n, window, dt):
     }
 
 
+def measure_settings(case, n, precision, settings, window, batches, dt):
+    members = members_of(case, n)
+    for m in members:
+        m.precision = crd._capi.PRECISION_F64 if precision == 64 else crd._capi.PRECISION_F32
+    g = crd.grid_of(members[0])
+    points = g.nx * g.ny
+    real = 8 if precision == 64 else 4
+    with crd.Ensemble(members) as e:
+        for k, m in enumerate(members):
+            e.upload(k, crd.initial_conditions(crd.run_config(m)))
+        # steps per batch: an even count that fills about a tenth of the window under single steps; the warm-up fills the window
+        ms = e.step_rk4_timed(0.0, dt, 16)
+        ms = e.step_rk4_timed(0.0, dt, 16)
+        steps = max(16, 2 * int(0.05 * window * 1e3 / max(ms / 16, 1e-6)))
+        t_end = time.perf_counter() + window
+        while time.perf_counter() < t_end:
+            for k in settings:
+                e.set_steps_per_launch(k)
+                e.step_rk4_timed(0.0, dt, steps)
+        us = {k: [] for k in settings}
+        for _ in range(batches):
+            for k in settings:
+                e.set_steps_per_launch(k)
+                us[k].append(1e3 * e.step_rk4_timed(0.0, dt, steps) / steps)
+    row = {"case": case, "grid": [g.nx, g.ny], "precision": precision, "members": n, "steps_per_batch": steps, "batches": batches,
+           "in_infinity_cache": n * 2 * 2 * real * points <= INFINITY_CACHE, "settings": {}}
+    for k in settings:
+        med = float(np.median(us[k]))
+        row["settings"][str(k)] = {"us_per_step_median": med, "us_per_step_min": min(us[k]), "us_per_step_max": max(us[k]), "gpss": n * points / (med * 1e-6),
+                                   "roof_frac_one_pass_per_step": n * points * 4 * real / (med * 1e-6) / ROOF_BYTES_PER_S}
+    return row
+
+
+def main_settings(a):
+    settings = [int(x) for x in a.steps_per_launch.split(",")]
+    if a.batches < 9:
+        sys.exit("--batches: at least 9")
+    rows = []
+    for case in a.cases.split(","):
+        dt = 0.004 if case == "fhn" else 0.002
+        for n in [int(x) for x in a.members.split(",")]:
+            r = measure_settings(case, n, a.precision, settings, a.window, a.batches, dt)
+            rows.append(r)
+            base = r["settings"][str(settings[0])]["us_per_step_median"]
+            print("%-9s fp%d %4dx%-4d B=%2d  " % (case, a.precision, r["grid"][0], r["grid"][1], n) + "  ".join(
+                "steps/launch %d: %8.2f us/step (%.2f .. %.2f) %.3e gpss x%.3f" % (k, q["us_per_step_median"], q["us_per_step_min"], q["us_per_step_max"], q["gpss"],
+                                                                                     base / q["us_per_step_median"])
+                for k, q in ((k, r["settings"][str(k)]) for k in settings)) + "  [%d batches of %d steps, %s]" % (
+                    a.batches, r["steps_per_batch"], "in Infinity Cache" if r["in_infinity_cache"] else "beyond Infinity Cache"), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump({"device": "MI355X", "rows": rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--members", default="1,4,16,64")
     ap.add_argument("--cases", default="fhn,goldbeter")
     ap.add_argument("--window", type=float, default=1.0)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--steps-per-launch", default=None, help="e.g. 1,2: the ensemble alone under each setting, interleaved batches")
+    ap.add_argument("--precision", type=int, choices=(64, 32), default=64)
+    ap.add_argument("--batches", type=int, default=11)
     a = ap.parse_args()
+    if a.steps_per_launch:
+        return main_settings(a)
     rows = []
     for case in a.cases.split(","):
         dt = 0.004 if case == "fhn" else 0.002  # (under both grids' RK4 stability bounds: 0.0052, 0.0069)

@@ -5,6 +5,10 @@
     tools/kernel_regs.py --asm build/x-hip-amdgcn-amd-amdhsa-gfx950.s ...         # reads assembly the build kept (-save-temps=obj)
         [--table build/crd_kernel_table.inc]   the step kernels' rows as C initialisers (compiled into libcrd: crd_get_launch_geometry)
         [--json profiles/r05/kernel_table.json]
+    tools/kernel_regs.py --check --asm build/y-hip-amdgcn-amd-amdhsa-gfx950.s ...  # the two contracts alone, over EVERY kernel: exit 0 / 3 / 4
+        (every kernel is reported and held to the LDS read hazards; the vmcnt contract -- no vector memory skipped on the execution mask --
+        binds the kernels that fill LDS by DMA, the only ones whose waits count operations by hand: a unit that includes crd_fused_impl.h
+        also EMITS its error-sum kernel, whose one store under `if (threadIdx.x == 0)` is skipped by design)
 
 The loop is the kernel's largest loop by vector instructions (the pipeline's steady state: the unrolled iterations of one trip);
 counts are static -- instructions in the loop body between its header label and its back edge, whatever branches inside it skip.
@@ -210,7 +214,9 @@ def parse(text):
             mix["total"] = sum(v for k_, v in mix.items() if k_ not in ("moves", "nops"))
             if best is None or mix["valu"] > best["valu"]:
                 best = mix
-        kernels.append({"mangled": name, "exec_skipped_vmem": len(exec_skipped_vmem(body)), "async_lds_read_hazards": len(async_lds_read_hazards(body)),
+        # (LDS-DMA fills: the kernels whose waits count vector-memory operations by hand -- the ones check_only holds to exec_skipped_vmem)
+        lds_dma = any(re.match(r"\s*buffer_load_\w+\s.*\blds\b", ln) for ln in body)
+        kernels.append({"mangled": name, "lds_dma": lds_dma, "exec_skipped_vmem": len(exec_skipped_vmem(body)), "async_lds_read_hazards": len(async_lds_read_hazards(body)),
                         "vgprs": meta.get("NumVgprs", 0), "sgprs": meta.get("TotalNumSgprs", meta.get("NumSgprs", 0)), "scratch": meta.get("ScratchSize", 0),
                         "occupancy": meta.get("Occupancy", 0), "lds": meta.get("LDSByteSize", 0), "loop": best or {"valu": 0, "salu": 0, "vmem": 0, "lds": 0, "other": 0, "moves": 0, "nops": 0, "total": 0}})
     for k, nm in zip(kernels, demangle([k["mangled"] for k in kernels])):
@@ -231,18 +237,50 @@ def table_digest(rows):
 STEP_KERNEL = re.compile(r"crd_rk4_fused_step_kernel<(double|float), (\d+), (true|false), (\d+), (\d+), (true|false), (\d+)>")
 
 
+def check_only(kernels):
+    """The two contracts over every kernel given, whatever its name (units outside the kernel table: the ensemble pair,
+    crd_ensemble_multi.hip) -- the vmcnt contract where a kernel fills LDS by DMA, the read hazards everywhere: one line per kernel, the exit status -- 0, 4 for an asynchronous LDS read hazard, 3 for a vector-memory
+    region skipped on the execution mask, the table mode's codes.  Nothing is written but the report."""
+    if not kernels:
+        sys.stderr.write("kernel_regs.py --check: no kernel in the assembly given\n")
+        return 2
+    status = 0
+    for k in kernels:
+        bad = []
+        if k["async_lds_read_hazards"]:
+            bad.append("%d register(s) with LDS reads in flight touched before the asm block that waits for them" % k["async_lds_read_hazards"])
+        # (the vmcnt contract is the ring pipelines': a kernel without LDS-DMA fills counts nothing by hand -- the error-sum kernel a unit
+        # inherits from crd_fused_impl.h stores under `if (threadIdx.x == 0)`, rightly)
+        skipped = k["exec_skipped_vmem"] if k["lds_dma"] else 0
+        if skipped:
+            bad.append("%d vector-memory region(s) skipped on the execution mask" % skipped)
+        print("%-6s %s" % ("FAIL" if bad else "ok", k["name"]))
+        for b in bad:
+            sys.stderr.write("kernel_regs.py: %s: %s\n" % (k["name"], b))
+        if k["async_lds_read_hazards"]:
+            status = 4
+        elif skipped and status == 0:
+            status = 3
+    return status
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("source", nargs="?")
     ap.add_argument("--asm", nargs="*", default=[])
     ap.add_argument("--table", default="")
     ap.add_argument("--json", default="")
+    ap.add_argument("--check", action="store_true", help="only check every kernel: asynchronous LDS read hazards everywhere, exec-skipped vector memory in the kernels that fill LDS by DMA")
     a, extra = ap.parse_known_args()
+    if a.check and (a.table or a.json):
+        ap.error("--check writes no table: it goes without --table / --json")
     kernels = []
     if a.source:
         kernels += parse(compile_to_asm(a.source, extra))
     for path in a.asm:
         kernels += parse(open(path).read())
+    if a.check:
+        sys.exit(check_only(kernels))
     rows = []
     for k in kernels:
         m = STEP_KERNEL.search(k["name"])
