@@ -212,6 +212,8 @@ _SIGNATURES = {
     "crd_launch_plan_candidate": (C.c_int, [C.c_int, C.POINTER(LaunchPlan)]),
     "crd_get_step_timing": (C.c_int, [_vp, C.POINTER(StepTiming)]),
     "crd_ensemble_create": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_vp)]),
+    "crd_ensemble_create_mixed": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_vp)]),
+    "crd_ensemble_member_grid": (C.c_int, [_vp, C.c_int, C.POINTER(Grid)]),
     "crd_ensemble_destroy": (None, [_vp]),
     "crd_ensemble_last_error": (C.c_char_p, [_vp]),
     "crd_ensemble_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(Grid)]),

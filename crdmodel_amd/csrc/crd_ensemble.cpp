@@ -1,6 +1,8 @@
 // crd_ensemble.cpp -- ensembles behind the C ABI (include/crd.h, crd_ensemble_*): B independent single-slab problems of one geometry,
 // stepped by one launch per RK4 step (crd_ensemble.hip).  Host code only.  A member owns its tables and two state buffers; the
-// members' descriptors sit in a device table the step kernel reads.
+// members' descriptors sit in a device table the step kernel reads.  crd_ensemble_create_mixed lets the members differ in surface and
+// grid: each has its own crd_grid; where nx or ny truly differ (`mixed`) the fixed steps and the basic observer go through the
+// per-member block mapping (crd_ensemble_mixed.hip, crd_ensemble_mixed_multi.hip), and everything else is refused.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -19,7 +21,13 @@ struct crd_ensemble {
 	std::vector<crd_params> p;
 	crd_grid g{};
 	int n = 0, device = 0, precision = CRD_PRECISION_F64, model = CRD_MODEL_FHN;  // model: kernel_model's (diffusion-only is its own)
-	int nx = 0, ny = 0;
+	int nx = 0, ny = 0;                    // member 0's (every member's unless `mixed`)
+	std::vector<crd_grid> grids;           // every member's own grid
+	bool mixed = false;                    // members differ in nx or ny (crd_ensemble_create_mixed only)
+	size_t max_points = 0;                 // nx * ny of the largest member
+	int min_ny = 0;
+	std::vector<EnsembleShape> shapes, pair_shapes;  // mixed: the members' shapes under the step plan and under the pair plan (n + 1 entries)
+	EnsembleShape *shapes_dev = nullptr, *pair_shapes_dev = nullptr;  // ... on the device (in allocs)
 	size_t real_size = 8;
 	EnsemblePlan plan;
 	int steps_per_launch = 1;              // crd_ensemble_set_steps_per_launch: 1, or 2 (pairs, crd_ensemble_multi.hip)
@@ -29,7 +37,7 @@ struct crd_ensemble {
 	EnsembleMember *table = nullptr;       // ... on the device
 	std::vector<void *> allocs;            // every device allocation but the table
 	int cur = 0;                           // the buffer holding every member's current state
-	void *stage = nullptr;                 // AoS staging of upload / download (nx * ny pairs of doubles)
+	void *stage = nullptr;                 // AoS staging of upload / download (nx * ny pairs of doubles of the largest member)
 	double *max_dev = nullptr, *max_host = nullptr;  // n doubles each; max_host page-locked
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -61,8 +69,8 @@ struct crd_ensemble {
 		ObserveProbes probes{};
 		int64_t capacity = 0, count = 0;       // samples: room, recorded (enqueued)
 		int64_t steps = 0;                     // fixed steps taken since begin (the stride's count, carried over calls)
-		int blocks = 0, row_doubles = 0;       // sampling blocks per member; doubles per member and sample: 8 + 2 n_probes
-		size_t map_plane = 0;                  // doubles per map plane (nx * ny, rounded up to an even count: 16-byte planes)
+		int blocks = 0, row_doubles = 0;       // sampling blocks per member (mixed: of the largest; the partials' stride); doubles per member and sample: 8 + 2 n_probes
+		size_t map_plane = 0;                  // doubles per map plane (nx * ny of the largest member, rounded up to an even count: 16-byte planes)
 		double *records = nullptr;             // capacity x n x row_doubles
 		double *partials = nullptr;            // n x blocks x 8
 		double *maps = nullptr;                // n x 3 x map_plane (minimum, maximum, activation time), or null
@@ -110,6 +118,19 @@ const char *disagreement(const crd_params &a, const crd_grid &ga, const crd_para
 	return nullptr;
 }
 
+// The first field in which member k differs from member 0 where members of a mixed-geometry ensemble must agree, or nullptr.
+const char *mixed_disagreement(const crd_params &a, const crd_params &b)
+{
+	if (a.model != b.model) return "model";
+	if (a.precision != b.precision) return "precision";
+	if (a.just_diffusion != b.just_diffusion) return "just_diffusion";
+	return nullptr;
+}
+
+size_t member_points(const crd_ensemble *e, int member) { return (size_t)e->grids[(size_t)member].nx * (size_t)e->grids[(size_t)member].ny; }
+
+constexpr const char *kMixedRefusal = "members of different shape";
+
 int check_member(crd_ensemble *e, int member)
 {
 	if (member < 0 || member >= e->n) return efail(e, CRD_EINVAL, "member index out of range");
@@ -136,6 +157,13 @@ int observer_sample(crd_ensemble *e, double t)
 	crd_ensemble::Observer &ob = e->obs;
 	const size_t n = (size_t)e->nx * (size_t)e->ny;
 	double *const row = ob.records + (size_t)ob.count * (size_t)e->n * (size_t)ob.row_doubles;
+	if (e->mixed) {  // (no sections, no cycle maps: refused when the observer was opened)
+		ENS_TRY(e, launch_observe_sample_mixed(e->precision, e->table, e->shapes_dev, e->n, e->cur, ob.blocks, ob.partials, ob.maps, ob.map_plane, ob.opt.threshold, t, e->stream));
+		ENS_TRY(e, launch_observe_finish_mixed(e->precision, e->table, e->shapes_dev, e->n, e->cur, ob.blocks, ob.partials, ob.probes, row, ob.row_doubles, e->stream));
+		ob.t.push_back(t);
+		ob.count++;
+		return CRD_OK;
+	}
 	if (ob.cycles) {
 		const ObserveCycles cy{ob.cycle_planes, ob.map_plane, ob.cycle_threshold, ob.t.empty() ? 0.0 : ob.t.back(), ob.t.empty() ? 1 : 0};
 		ENS_TRY(e, launch_observe_sample_cycles(e->precision, e->table, e->n, e->cur, n, ob.partials, ob.maps, ob.map_plane, ob.opt.threshold, t, cy, e->stream));
@@ -152,11 +180,19 @@ int observer_sample(crd_ensemble *e, double t)
 	return CRD_OK;
 }
 
-}  // namespace
+void member_extents(const crd_ensemble *e, std::vector<int> *nx, std::vector<int> *ny)
+{
+	nx->clear();
+	ny->clear();
+	for (const crd_grid &g : e->grids) {
+		nx->push_back((int)g.nx);
+		ny->push_back((int)g.ny);
+	}
+}
 
-extern "C" {
-
-int crd_ensemble_create(const crd_params *members, int n_members, int device, crd_ensemble **out)
+// crd_ensemble_create (mixed_entry false: members of one geometry, today's refusals and messages) and crd_ensemble_create_mixed
+// (members agree on model, precision and just_diffusion only).
+int create_ensemble(const crd_params *members, int n_members, int device, bool mixed_entry, crd_ensemble **out)
 {
 	if (!out) return CRD_EINVAL;
 	*out = nullptr;
@@ -168,11 +204,33 @@ int crd_ensemble_create(const crd_params *members, int n_members, int device, cr
 		std::string why;
 		if (!validate_params(members[k], &why)) return efail(nullptr, CRD_EINVAL, "member " + std::to_string(k) + ": " + why);
 		if (int rc = crd_grid_from_params(&members[k], &grids[(size_t)k])) return efail(nullptr, rc, "member " + std::to_string(k) + ": bad geometry");
-		if (const char *f = disagreement(members[0], grids[0], members[k], grids[(size_t)k]))
+		if (mixed_entry) {
+			if (const char *f = mixed_disagreement(members[0], members[k]))
+				return efail(nullptr, CRD_EINVAL, "member " + std::to_string(k) + " differs from member 0 in " + f + " (members of a mixed-geometry ensemble must agree on model, precision and just_diffusion)");
+		} else if (const char *f = disagreement(members[0], grids[0], members[k], grids[(size_t)k])) {
 			return efail(nullptr, CRD_EINVAL, "member " + std::to_string(k) + " differs from member 0 in " + f + " (members may differ in diffusion, beta, beta_min, beta_max, vary_beta and t_boundary only)");
+		}
 	}
-	if (grids[0].ny < 2 * kStepHalo) return efail(nullptr, CRD_EINVAL, "every member needs at least 8 rows");
-	if (grids[0].ny > INT32_MAX / 2) return efail(nullptr, CRD_EINVAL, "members too tall");
+	bool mixed = false;
+	if (mixed_entry) {
+		// (block ids are 32-bit: at most one block per strip of 48 columns -- the pairs' -- and chunk of 4 rows, over all members together)
+		long blocks = 0;
+		for (int k = 0; k < n_members; k++) {
+			const crd_grid &g = grids[(size_t)k];
+			if (g.ny < 2 * kStepHalo)
+				return efail(nullptr, CRD_EINVAL, "member " + std::to_string(k) + " has ny = " + std::to_string(g.ny) + " rows: every member needs at least 8 rows");
+			if (g.ny > INT32_MAX / 2) return efail(nullptr, CRD_EINVAL, "member " + std::to_string(k) + " is too tall (ny = " + std::to_string(g.ny) + ")");
+			if (g.nx > INT32_MAX / 2) return efail(nullptr, CRD_EINVAL, "member " + std::to_string(k) + " is too wide (nx = " + std::to_string(g.nx) + ")");
+			blocks += (long)((g.nx + 47) / 48) * (long)((g.ny + 3) / 4);
+			if (blocks > INT32_MAX)
+				return efail(nullptr, CRD_EINVAL, "member " + std::to_string(k) + ": with its nx = " + std::to_string(g.nx) + " and ny = " + std::to_string(g.ny) +
+				                                      " the block ids of members 0 .. " + std::to_string(k) + " together overflow 32 bits (too many work items for one launch)");
+			mixed = mixed || g.nx != grids[0].nx || g.ny != grids[0].ny;
+		}
+	} else {
+		if (grids[0].ny < 2 * kStepHalo) return efail(nullptr, CRD_EINVAL, "every member needs at least 8 rows");
+		if (grids[0].ny > INT32_MAX / 2) return efail(nullptr, CRD_EINVAL, "members too tall");
+	}
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
 		(void)hipGetLastError();
@@ -189,16 +247,22 @@ int crd_ensemble_create(const crd_params *members, int n_members, int device, cr
 	};
 	e->p.assign(members, members + n_members);
 	e->g = grids[0];
+	e->grids = grids;
+	e->mixed = mixed;
 	e->n = n_members;
 	e->device = device;
 	e->precision = members[0].precision;
 	e->real_size = e->precision == CRD_PRECISION_F64 ? 8 : 4;
 	e->nx = (int)e->g.nx;
 	e->ny = (int)e->g.ny;
+	e->min_ny = e->ny;
+	for (int k = 0; k < n_members; k++) {
+		e->max_points = std::max(e->max_points, member_points(e, k));
+		e->min_ny = std::min(e->min_ny, (int)grids[(size_t)k].ny);
+	}
 	e->model = (members[0].model == CRD_MODEL_GOLDBETER && members[0].just_diffusion) ? dev::kModelDiffusionOnly : members[0].model;
-	const size_t points = (size_t)e->nx * (size_t)e->ny, plane = points * e->real_size;
 	// (block ids are 32-bit: at most one block per strip of 56 columns and chunk of 4 rows per member)
-	if ((long)n_members * ((e->nx + 55) / 56) * ((e->ny + 3) / 4) > INT32_MAX) return bail(efail(e, CRD_EINVAL, "too many work items for one launch"));
+	if (!mixed_entry && (long)n_members * ((e->nx + 55) / 56) * ((e->ny + 3) / 4) > INT32_MAX) return bail(efail(e, CRD_EINVAL, "too many work items for one launch"));
 
 	auto step = [&](hipError_t r, const char *what) {
 		if (r != hipSuccess) efail(e, r == hipErrorOutOfMemory ? CRD_ENOMEM : CRD_EHIP, std::string(what) + ": " + hipGetErrorString(r));
@@ -214,7 +278,7 @@ int crd_ensemble_create(const crd_params *members, int n_members, int device, cr
 	    !step(hipEventCreate(&e->ev0), "hipEventCreate") || !step(hipEventCreate(&e->ev1), "hipEventCreate"))
 		return bail(CRD_EHIP);
 	void *q = nullptr;
-	if (!device_alloc(2 * points * sizeof(double), &e->stage) || !device_alloc((size_t)n_members * sizeof(double), &q)) return bail(CRD_ENOMEM);
+	if (!device_alloc(2 * e->max_points * sizeof(double), &e->stage) || !device_alloc((size_t)n_members * sizeof(double), &q)) return bail(CRD_ENOMEM);
 	e->max_dev = static_cast<double *>(q);
 	if (!step(hipHostMalloc((void **)&e->max_host, (size_t)n_members * sizeof(double), hipHostMallocPortable), "hipHostMalloc")) return bail(CRD_ENOMEM);
 
@@ -222,6 +286,8 @@ int crd_ensemble_create(const crd_params *members, int n_members, int device, cr
 	for (int k = 0; k < n_members; k++) {
 		EnsembleMember &m = e->members[(size_t)k];
 		m = EnsembleMember{};
+		const crd_grid &gk = e->grids[(size_t)k];
+		const size_t plane = member_points(e, k) * e->real_size;
 		// two state buffers, each both fields: u then v, nx * ny reals apiece
 		for (int b = 0; b < 2; b++) {
 			if (!device_alloc(2 * plane, &q)) return bail(e->err.empty() ? CRD_ENOMEM : CRD_EHIP);
@@ -231,7 +297,7 @@ int crd_ensemble_create(const crd_params *members, int n_members, int device, cr
 		}
 		Coefficients co;
 		std::vector<double> brow;
-		build_step_tables(members[k], e->g, -kGhost, e->g.ny + kGhost, &co, &brow);
+		build_step_tables(members[k], gk, -kGhost, gk.ny + kGhost, &co, &brow);  // (the member's own grid: its surface, lengths and mesh)
 		void *tables[4] = {nullptr, nullptr, nullptr, nullptr};
 		const std::vector<double> *src[4] = {&co.cE, &co.cWn, &co.cP, &brow};
 		for (int t = 0; t < 4; t++) {
@@ -248,12 +314,31 @@ int crd_ensemble_create(const crd_params *members, int n_members, int device, cr
 	if (!step(hipMalloc((void **)&e->table, (size_t)n_members * sizeof(EnsembleMember)), "hipMalloc(table)") ||
 	    !step(hipMemcpy(e->table, e->members.data(), (size_t)n_members * sizeof(EnsembleMember), hipMemcpyHostToDevice), "hipMemcpy(table)"))
 		return bail(CRD_EHIP);
-	if (!step(ensemble_plan(e->precision, e->model, e->nx, e->ny, n_members, &e->plan), "ensemble_plan") ||
-	    !step(hipStreamSynchronize(e->stream), "device initialisation"))
+	if (e->mixed) {
+		std::vector<int> nxs, nys;
+		member_extents(e, &nxs, &nys);
+		e->shapes.resize((size_t)n_members + 1);
+		if (!step(ensemble_plan_mixed(e->precision, e->model, nxs.data(), nys.data(), n_members, &e->plan, e->shapes.data()), "ensemble_plan_mixed")) return bail(CRD_EHIP);
+		if (const int k = mixed_overflow_member(e->shapes.data(), n_members); k >= 0)  // (refused above on a coarser count: not reached)
+			return bail(efail(e, CRD_EINVAL, "too many work items for one launch: the block ids overflow 32 bits at member " + std::to_string(k)));
+		if (!device_alloc(e->shapes.size() * sizeof(EnsembleShape), &q)) return bail(CRD_ENOMEM);
+		e->shapes_dev = static_cast<EnsembleShape *>(q);
+		if (!step(hipMemcpy(e->shapes_dev, e->shapes.data(), e->shapes.size() * sizeof(EnsembleShape), hipMemcpyHostToDevice), "hipMemcpy(shapes)")) return bail(CRD_EHIP);
+	} else if (!step(ensemble_plan(e->precision, e->model, e->nx, e->ny, n_members, &e->plan), "ensemble_plan")) {
 		return bail(CRD_EHIP);
+	}
+	if (!step(hipStreamSynchronize(e->stream), "device initialisation")) return bail(CRD_EHIP);
 	*out = e;
 	return CRD_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int crd_ensemble_create(const crd_params *members, int n_members, int device, crd_ensemble **out) { return create_ensemble(members, n_members, device, false, out); }
+
+int crd_ensemble_create_mixed(const crd_params *members, int n_members, int device, crd_ensemble **out) { return create_ensemble(members, n_members, device, true, out); }
 
 void crd_ensemble_destroy(crd_ensemble *e)
 {
@@ -283,6 +368,13 @@ int crd_ensemble_info(const crd_ensemble *e, int *n_members, crd_grid *g)
 	return CRD_OK;
 }
 
+int crd_ensemble_member_grid(const crd_ensemble *e, int member, crd_grid *g)
+{
+	if (!e || !g || member < 0 || member >= e->n) return CRD_EINVAL;
+	*g = e->grids[(size_t)member];
+	return CRD_OK;
+}
+
 int crd_ensemble_upload(crd_ensemble *e, int member, const void *y, int host_is_f64)
 {
 	if (!e || !y) return CRD_EINVAL;
@@ -290,7 +382,7 @@ int crd_ensemble_upload(crd_ensemble *e, int member, const void *y, int host_is_
 	if (e->precision == CRD_PRECISION_F64 && !host_is_f64) return efail(e, CRD_EINVAL, "an fp64 ensemble takes double host buffers");
 	TraceRange range("crd_ensemble_upload");
 	ENS_TRY(e, hipSetDevice(e->device));
-	const size_t points = (size_t)e->nx * (size_t)e->ny;
+	const size_t points = member_points(e, member);
 	const EnsembleMember &m = e->members[(size_t)member];
 	ENS_TRY(e, hipMemcpyAsync(e->stage, y, 2 * points * (host_is_f64 ? 8 : 4), hipMemcpyHostToDevice, e->stream));
 	if (!e->adapt.empty()) e->adapt[(size_t)member].dense.pending = e->adapt[(size_t)member].ark.live = false;  // this member starts afresh
@@ -306,7 +398,7 @@ int crd_ensemble_download(crd_ensemble *e, int member, void *y, int host_is_f64)
 	if (e->precision == CRD_PRECISION_F64 && !host_is_f64) return efail(e, CRD_EINVAL, "an fp64 ensemble fills double host buffers");
 	TraceRange range("crd_ensemble_download");
 	ENS_TRY(e, hipSetDevice(e->device));
-	const size_t points = (size_t)e->nx * (size_t)e->ny;
+	const size_t points = member_points(e, member);
 	const EnsembleMember &m = e->members[(size_t)member];
 	ENS_TRY(e, launch_ensemble_planes_to_aos(e->precision, host_is_f64, m.u[e->cur], m.v[e->cur], e->stage, points, e->stream));
 	ENS_TRY(e, hipMemcpyAsync(y, e->stage, 2 * points * (host_is_f64 ? 8 : 4), hipMemcpyDeviceToHost, e->stream));
@@ -343,6 +435,7 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 	st.nchunks = e->plan.nchunks;
 	st.member_blocks = st.nsb * st.nchunks;
 	st.nblocks = st.member_blocks * e->n;
+	if (e->mixed) st.nblocks = e->shapes[(size_t)e->n].first_block;  // (strips and chunks are the members' own: the shape table's)
 	const bool pairs = e->steps_per_launch == 2;
 	EnsemblePair pr{};  // the same constants on the pair launches' own plan
 	if (pairs) {
@@ -354,6 +447,7 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 		pr.step.nchunks = e->pair_plan.nchunks;
 		pr.step.member_blocks = pr.step.nsb * pr.step.nchunks;
 		pr.step.nblocks = pr.step.member_blocks * e->n;
+		if (e->mixed) pr.step.nblocks = e->pair_shapes[(size_t)e->n].first_block;
 	}
 	const double cs[4] = {0.0, 0.5, 0.5, 1.0};
 	double latest_boundary = -INFINITY;  // the absorbing rows are on at stage time t exactly when t < some member's tBoundary
@@ -377,11 +471,15 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 				absorb = absorb || pr.t_stage2[k] < latest_boundary;
 			}
 			pr.step.src = e->cur;
-			ENS_TRY(e, launch_ensemble_pair(e->precision, e->model, e->pair_plan.cols, absorb && can_absorb, e->table, pr, e->stream));
+			if (e->mixed)
+				ENS_TRY(e, launch_ensemble_pair_mixed(e->precision, e->model, e->pair_plan.cols, absorb && can_absorb, e->table, e->pair_shapes_dev, e->n, e->min_ny, pr, e->stream));
+			else
+				ENS_TRY(e, launch_ensemble_pair(e->precision, e->model, e->pair_plan.cols, absorb && can_absorb, e->table, pr, e->stream));
 			taken = 2;
 		} else {
 			st.src = e->cur;
-			ENS_TRY(e, launch_ensemble_step(e->precision, e->model, e->plan.cols, absorb && can_absorb, e->table, st, e->stream));
+			if (e->mixed) ENS_TRY(e, launch_ensemble_step_mixed(e->precision, e->model, e->plan.cols, absorb && can_absorb, e->table, e->shapes_dev, e->n, st, e->stream));
+			else ENS_TRY(e, launch_ensemble_step(e->precision, e->model, e->plan.cols, absorb && can_absorb, e->table, st, e->stream));
 		}
 		e->cur = 1 - e->cur;  // (a pair flips once: its first step's state never reaches memory)
 		s += taken;
@@ -397,13 +495,35 @@ int crd_ensemble_set_steps_per_launch(crd_ensemble *e, int steps)
 	if (steps != 1 && steps != 2) return efail(e, CRD_EINVAL, "steps per launch must be 1 or 2 (got " + std::to_string(steps) + ")");
 	if (steps == 2) {
 		static_assert(CRD_ENSEMBLE_PAIR_MIN_ROWS == kEnsemblePairMinRows, "crd.h states the pair kernels' bound");
-		if (e->ny < kEnsemblePairMinRows)
+		if (e->mixed) {
+			for (int k = 0; k < e->n; k++)
+				if (e->grids[(size_t)k].ny < kEnsemblePairMinRows)
+					return efail(e, CRD_EINVAL, "two steps per launch need members of at least " + std::to_string(kEnsemblePairMinRows) + " rows (CRD_ENSEMBLE_PAIR_MIN_ROWS); member " +
+					                                std::to_string(k) + " has " + std::to_string(e->grids[(size_t)k].ny));
+		} else if (e->ny < kEnsemblePairMinRows)
 			return efail(e, CRD_EINVAL, "two steps per launch need members of at least " + std::to_string(kEnsemblePairMinRows) + " rows (CRD_ENSEMBLE_PAIR_MIN_ROWS); these have " +
 			                                std::to_string(e->ny));
 #ifdef CRD_NO_ENSEMBLE_PAIRS
 		return efail(e, CRD_EINVAL, "this build of libcrd carries no pair kernels (built without the check of their assembly: make KERNEL_TABLE=0)");
 #else
-		if (!e->pair_planned) {
+		if (!e->pair_planned && e->mixed) {
+			ENS_TRY(e, hipSetDevice(e->device));
+			EnsemblePlan plan;
+			std::vector<int> nxs, nys;
+			member_extents(e, &nxs, &nys);
+			std::vector<EnsembleShape> shapes((size_t)e->n + 1);
+			ENS_TRY(e, ensemble_pair_plan_mixed(e->precision, e->model, nxs.data(), nys.data(), e->n, &plan, shapes.data()));
+			if (const int k = mixed_overflow_member(shapes.data(), e->n); k >= 0)
+				return efail(e, CRD_EINVAL, "too many work items for one launch: the pair launches' block ids overflow 32 bits at member " + std::to_string(k));
+			void *q = nullptr;
+			ENS_TRY(e, hipMalloc(&q, shapes.size() * sizeof(EnsembleShape)));
+			e->allocs.push_back(q);
+			ENS_TRY(e, hipMemcpy(q, shapes.data(), shapes.size() * sizeof(EnsembleShape), hipMemcpyHostToDevice));
+			e->pair_shapes_dev = static_cast<EnsembleShape *>(q);
+			e->pair_shapes = shapes;
+			e->pair_plan = plan;
+			e->pair_planned = true;
+		} else if (!e->pair_planned) {
 			ENS_TRY(e, hipSetDevice(e->device));
 			EnsemblePlan plan;
 			ENS_TRY(e, ensemble_pair_plan(e->precision, e->model, e->nx, e->ny, e->n, &plan));
@@ -445,7 +565,8 @@ int crd_ensemble_max_abs(crd_ensemble *e, double *per_member)
 {
 	if (!e || !per_member) return CRD_EINVAL;
 	ENS_TRY(e, hipSetDevice(e->device));
-	ENS_TRY(e, launch_ensemble_max_abs(e->precision, e->table, e->n, e->cur, (size_t)e->nx * (size_t)e->ny, e->max_dev, e->stream));
+	if (e->mixed) ENS_TRY(e, launch_ensemble_max_abs_mixed(e->precision, e->table, e->shapes_dev, e->n, e->cur, e->max_points, e->max_dev, e->stream));
+	else ENS_TRY(e, launch_ensemble_max_abs(e->precision, e->table, e->n, e->cur, (size_t)e->nx * (size_t)e->ny, e->max_dev, e->stream));
 	ENS_TRY(e, hipMemcpyAsync(e->max_host, e->max_dev, (size_t)e->n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	for (int k = 0; k < e->n; k++) per_member[k] = e->max_host[k];
@@ -561,6 +682,7 @@ extern "C" {
 int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats, int32_t *status)
 {
 	if (!e) return CRD_EINVAL;
+	if (e->mixed) return efail(e, CRD_EINVAL, std::string("crd_ensemble_integrate_adaptive: ") + kMixedRefusal + " integrate with fixed steps only");
 	crd_adaptive_options o;
 	crd_adaptive_defaults(&o);
 	if (opt) o = *opt;
@@ -879,15 +1001,21 @@ int crd_ensemble_observe_begin_with(crd_ensemble *e, const crd_observe_options *
 	if (capacity < 1) return efail(e, CRD_EINVAL, "observer capacity must be at least 1 sample (got " + std::to_string(capacity) + ")");
 	if (opt->n_probes < 0 || opt->n_probes > CRD_OBSERVE_MAX_PROBES)
 		return efail(e, CRD_EINVAL, "an observer takes 0 .. " + std::to_string(CRD_OBSERVE_MAX_PROBES) + " probes (got " + std::to_string(opt->n_probes) + ")");
+	if (e->mixed && extras && (extras->n_sections != 0 || extras->cycles != 0))
+		return efail(e, CRD_EINVAL, std::string("crd_ensemble_observe_begin_with: ") + kMixedRefusal + " take " + (extras->n_sections != 0 ? "no sections" : "no cycle maps") +
+		                                " (statistics, probes and maps only)");
 	for (int q = 0; q < opt->n_probes; q++)
-		if (opt->probe_i[q] < 0 || opt->probe_i[q] >= e->nx || opt->probe_j[q] < 0 || opt->probe_j[q] >= e->ny)
-			return efail(e, CRD_EINVAL, "probe " + std::to_string(q) + " (i = " + std::to_string(opt->probe_i[q]) + ", j = " + std::to_string(opt->probe_j[q]) +
-			                                ") is outside the " + std::to_string(e->nx) + " x " + std::to_string(e->ny) + " grid");
+		for (int k = 0; k < (e->mixed ? e->n : 1); k++) {  // (members of one shape: member 0 stands for all, with today's message)
+			const int nx = (int)e->grids[(size_t)k].nx, ny = (int)e->grids[(size_t)k].ny;
+			if (opt->probe_i[q] < 0 || opt->probe_i[q] >= nx || opt->probe_j[q] < 0 || opt->probe_j[q] >= ny)
+				return efail(e, CRD_EINVAL, "probe " + std::to_string(q) + " (i = " + std::to_string(opt->probe_i[q]) + ", j = " + std::to_string(opt->probe_j[q]) +
+				                                ") is outside the " + std::to_string(nx) + " x " + std::to_string(ny) + " grid" + (e->mixed ? " of member " + std::to_string(k) : std::string()));
+		}
 	if (opt->maps != 0 && opt->maps != 1) return efail(e, CRD_EINVAL, "observer maps is 0 or 1");
 	if (opt->maps && !std::isfinite(opt->threshold)) return efail(e, CRD_EINVAL, "observer maps need a finite threshold");
 	static_assert(CRD_OBSERVE_MAX_PROBES == kObserveMaxProbes, "the header's probe limit is the kernels'");
 	static_assert(CRD_OBSERVE_MAX_SECTIONS == kObserveMaxSections, "the header's section limit is the kernels'");
-	const size_t n = (size_t)e->nx * (size_t)e->ny, B = (size_t)e->n;
+	const size_t n = e->max_points, B = (size_t)e->n;  // (the partials' stride and the map planes are sized for the largest member)
 	crd_ensemble::Observer ob;
 	size_t section_doubles = 0;  // of the whole section buffer
 	if (extras) {
@@ -972,7 +1100,7 @@ int crd_ensemble_observe_count(const crd_ensemble *e, int64_t *n_samples)
 int crd_ensemble_observe_info(const crd_ensemble *e, int32_t *blocks_per_member, int64_t *values_per_field, crd_observe_options *opt, int64_t *capacity)
 {
 	if (!e || !e->obs.open) return CRD_EINVAL;
-	if (blocks_per_member) *blocks_per_member = e->obs.blocks;
+	if (blocks_per_member) *blocks_per_member = e->mixed ? observe_blocks(member_points(e, 0)) : e->obs.blocks;  // (member 0's, as crd_ensemble_info)
 	if (values_per_field) *values_per_field = (int64_t)e->nx * (int64_t)e->ny;
 	if (opt) *opt = e->obs.opt;
 	if (capacity) *capacity = e->obs.capacity;
@@ -1005,7 +1133,7 @@ int crd_ensemble_observe_maps(crd_ensemble *e, int member, double *min_u, double
 	if (!e->obs.open || !e->obs.maps) return efail(e, CRD_EINVAL, "no observer with maps is open");
 	if (int rc = check_member(e, member)) return rc;
 	ENS_TRY(e, hipSetDevice(e->device));
-	const size_t n = (size_t)e->nx * (size_t)e->ny;
+	const size_t n = member_points(e, member);
 	double *const out[3] = {min_u, max_u, t_act};
 	for (int q = 0; q < 3; q++)
 		if (out[q]) ENS_TRY(e, hipMemcpyAsync(out[q], e->obs.maps + ((size_t)member * 3 + (size_t)q) * e->obs.map_plane, n * sizeof(double), hipMemcpyDeviceToHost, e->stream));

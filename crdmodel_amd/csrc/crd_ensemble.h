@@ -71,6 +71,44 @@ hipError_t ensemble_pair_plan(int precision, int model, int nx, int ny, int memb
 hipError_t launch_ensemble_pair(int precision, int model, int cols, bool absorb, const EnsembleMember *table, const EnsemblePair &e, hipStream_t s);
 
 
+// ---- members of different shape (crd_ensemble_mixed.hip, crd_ensemble_mixed_multi.hip; crd_ensemble.cpp: crd_ensemble_create_mixed) ----
+
+// One member's shape under one plan: an entry of a second device table beside EnsembleMember's, written once when the plan is made
+// and read through the constant address space (scalar loads).  The table has members + 1 entries: first_block is the prefix of the
+// members' block counts (nsb * nchunks) in member-major order, the last entry's the launch's block count (its other fields are zero).
+struct EnsembleShape {
+	int nx, ny;
+	int nstrips, nsb, nchunks;  // strips of columns, blocks across one chunk of rows, chunks of rows: the member's own
+	int first_block;
+};
+// Both plans below mark a prefix that leaves 32 bits with first_block = -1 from the first member past it on (the last entry too);
+// such a plan must not be launched.  The member at which the block ids overflow, or -1 where they fit.
+inline int mixed_overflow_member(const EnsembleShape *shapes, int members)
+{
+	if (shapes[members].first_block >= 0) return -1;
+	int k = 0;
+	while (k + 1 < members && shapes[k + 1].first_block >= 0) k++;
+	return k;
+}
+// Fixed plan over a list of shapes: plan->cols, sw, chunk and resident_blocks hold for the launch (nstrips, nsb, nchunks stay zero:
+// they are per member, in shapes[0 .. members]).  cols = 2 only in fp32 with every nx even; strips are cut per member as ensemble_plan
+// cuts them; sw = min(4, the most strips of any member); ONE chunk height, ensemble_plan's halving rule over the members' blocks
+// together, never above the smallest ny.  Needs the device.
+hipError_t ensemble_plan_mixed(int precision, int model, const int *nx, const int *ny, int members, EnsemblePlan *plan, EnsembleShape *shapes);
+// launch_ensemble_step over members of different shape: e.sw, e.chunk, e.nblocks (the shapes' total), e.src and the step's constants
+// are the launch's; nx, ny, strips and chunks come from shapes (a device table of members + 1 entries).
+hipError_t launch_ensemble_step_mixed(int precision, int model, int cols, bool absorb, const EnsembleMember *table, const EnsembleShape *shapes, int members,
+                                      const EnsembleStep &e, hipStream_t s);
+// launch_ensemble_max_abs, each member over its own nx * ny points; max_n: the largest member's.
+hipError_t launch_ensemble_max_abs_mixed(int precision, const EnsembleMember *table, const EnsembleShape *shapes, int members, int src, size_t max_n, double *out_dev,
+                                         hipStream_t s);
+// The pair launches' plan over a list of shapes (ensemble_pair_plan's rule; the chunk never above 2 min ny - 17), and the launch.
+// hipErrorInvalidValue where a member has fewer than kEnsemblePairMinRows rows.
+hipError_t ensemble_pair_plan_mixed(int precision, int model, const int *nx, const int *ny, int members, EnsemblePlan *plan, EnsembleShape *shapes);
+hipError_t launch_ensemble_pair_mixed(int precision, int model, int cols, bool absorb, const EnsembleMember *table, const EnsembleShape *shapes, int members, int min_ny,
+                                      const EnsemblePair &e, hipStream_t s);
+
+
 // ---- error-controlled integration (crd_ensemble_adaptive.hip; crd_ensemble.cpp: crd_ensemble_integrate_adaptive) ----
 
 // One member's attempt of a round: an entry of a table in device memory, written by the host before each round's launch and read
@@ -153,6 +191,13 @@ hipError_t launch_observe_sample(int precision, const EnsembleMember *table, int
 hipError_t launch_observe_finish(int precision, const EnsembleMember *table, int members, int src, size_t n, const double *partials_dev, const ObserveProbes &probes, int nx,
                                  double *row_dev, int row_doubles, hipStream_t s);
 hipError_t launch_observe_fill(double *x, size_t n, double value, hipStream_t s);
+// ... over members of different shape: n_k = nx_k * ny_k from shapes, G_k = observe_blocks(n_k) as ever, so a member's row is the bits
+// it has in any ensemble.  The sampling grid is (max_blocks = max G_k, members), blocks beyond G_k return; member k's partials sit at
+// partials_dev + k * max_blocks * 8, its map planes at maps_dev + 3 k map_plane (map_plane >= the largest n_k).
+hipError_t launch_observe_sample_mixed(int precision, const EnsembleMember *table, const EnsembleShape *shapes, int members, int src, int max_blocks, double *partials_dev,
+                                       double *maps_dev, size_t map_plane, double threshold, double t, hipStream_t s);
+hipError_t launch_observe_finish_mixed(int precision, const EnsembleMember *table, const EnsembleShape *shapes, int members, int src, int max_blocks,
+                                       const double *partials_dev, const ObserveProbes &probes, double *row_dev, int row_doubles, hipStream_t s);
 
 // Cycle maps: what the sampling pass needs besides the sample's time.  Member k's four planes of `plane` >= n doubles each at
 // planes + 4 k plane: the previous sample's var0, the time of the first and of the last upward crossing of `threshold` (NaN where

@@ -17,6 +17,7 @@
 // DESIGN.md, "Ensembles" (observers).
 #include "crd_device.h"
 #include "crd_ensemble.h"
+#include "crd_ensemble_mixed.h"
 
 namespace crd {
 
@@ -98,9 +99,10 @@ __device__ __forceinline__ void cycle_update(double *__restrict__ prev, double *
 
 // grid (G, members), kObserveThreads lanes.  Group c of V consecutive points belongs to lane (c mod 256) of block ((c / 256) mod G);
 // partial record of (member, block): min u, max u, sum u, sum u^2, then v's four.  The body of every instantiation of the sampling kernel.
+// G: the member's sampling blocks; slots: partial records between two members (the launch's gridDim.x; members of one shape: both).
 template <typename Real, bool MAPS, bool CYCLES>
 __device__ __forceinline__ void observe_sample_body(const EnsembleMember *members, int src, size_t n, double *__restrict__ partials, double *__restrict__ maps,
-                                                    size_t map_plane, double threshold, double t, const ObserveCycles &cy)
+                                                    size_t map_plane, double threshold, double t, const ObserveCycles &cy, unsigned G, unsigned slots)
 {
 	constexpr int V = Wide<Real>::n;
 	using Vec = typename Wide<Real>::type;
@@ -118,7 +120,7 @@ __device__ __forceinline__ void observe_sample_body(const EnsembleMember *member
 	int *const ccount = CYCLES ? reinterpret_cast<int *>(clast + cy.plane) : nullptr;
 	// 16 bytes per lane and load where both of this member's planes allow it (decided per block; the result does not depend on it)
 	const bool wide = (((uintptr_t)u | (uintptr_t)v) & 15) == 0;
-	const size_t groups = (n + V - 1) / V, stride = (size_t)gridDim.x * kObserveThreads;
+	const size_t groups = (n + V - 1) / V, stride = (size_t)G * kObserveThreads;
 
 	FieldStats<V> a, b;
 	a.clear();
@@ -176,7 +178,7 @@ __device__ __forceinline__ void observe_sample_body(const EnsembleMember *member
 		const int k = threadIdx.x;
 		const double w0 = part[0][k], w1 = part[1][k], w2 = part[2][k], w3 = part[3][k];  // pairwise: (0 + 1) + (2 + 3)
 		const double out = (k & 3) == 0 ? nan_min(nan_min(w0, w1), nan_min(w2, w3)) : (k & 3) == 1 ? nan_max(nan_max(w0, w1), nan_max(w2, w3)) : (w0 + w1) + (w2 + w3);
-		partials[((size_t)member * gridDim.x + blockIdx.x) * 8 + k] = out;
+		partials[((size_t)member * slots + blockIdx.x) * 8 + k] = out;
 	}
 }
 
@@ -184,7 +186,7 @@ template <typename Real, bool MAPS>
 __global__ void __launch_bounds__(kObserveThreads) crd_observe_sample_kernel(const EnsembleMember *members, int src, size_t n, double *__restrict__ partials,
                                                                              double *__restrict__ maps, size_t map_plane, double threshold, double t)
 {
-	observe_sample_body<Real, MAPS, false>(members, src, n, partials, maps, map_plane, threshold, t, ObserveCycles{});
+	observe_sample_body<Real, MAPS, false>(members, src, n, partials, maps, map_plane, threshold, t, ObserveCycles{}, gridDim.x, gridDim.x);
 }
 
 // ... with the cycle maps folded in the same pass.
@@ -192,18 +194,19 @@ template <typename Real, bool MAPS>
 __global__ void __launch_bounds__(kObserveThreads) crd_observe_sample_cycles_kernel(const EnsembleMember *members, int src, size_t n, double *__restrict__ partials,
                                                                                     double *__restrict__ maps, size_t map_plane, double threshold, double t, ObserveCycles cy)
 {
-	observe_sample_body<Real, MAPS, true>(members, src, n, partials, maps, map_plane, threshold, t, cy);
+	observe_sample_body<Real, MAPS, true>(members, src, n, partials, maps, map_plane, threshold, t, cy, gridDim.x, gridDim.x);
 }
 
 // One workgroup per member.  row: the sample's rows, member k's at row + k * row_doubles: the eight statistics, then (u, v) of each probe.
+// (blocks: the member's partial records; slots: records between two members)
 template <typename Real>
-__global__ void __launch_bounds__(64) crd_observe_finish_kernel(const EnsembleMember *members, int src, const double *__restrict__ partials, int blocks, ObserveProbes pr,
-                                                                int nx, double *__restrict__ row, int row_doubles)
+__device__ __forceinline__ void observe_finish_body(const EnsembleMember *members, int src, const double *__restrict__ partials, int blocks, int slots, const ObserveProbes &pr,
+                                                    int nx, double *__restrict__ row, int row_doubles)
 {
 	const int member = blockIdx.x, k = threadIdx.x;
 	double *const out = row + (size_t)member * row_doubles;
 	if (k < 8) {
-		const double *const p = partials + (size_t)member * blocks * 8 + k;
+		const double *const p = partials + (size_t)member * slots * 8 + k;
 		auto fold = [&](double r, double o) { return (k & 3) == 0 ? nan_min(r, o) : (k & 3) == 1 ? nan_max(r, o) : r + o; };
 		double r = p[0];
 		int g = 1;
@@ -220,6 +223,44 @@ __global__ void __launch_bounds__(64) crd_observe_finish_kernel(const EnsembleMe
 		const Real *const plane = static_cast<const Real *>((k & 1) ? mem->v[src] : mem->u[src]);
 		out[k] = (double)plane[(size_t)pr.j[q] * nx + pr.i[q]];
 	}
+}
+
+template <typename Real>
+__global__ void __launch_bounds__(64) crd_observe_finish_kernel(const EnsembleMember *members, int src, const double *__restrict__ partials, int blocks, ObserveProbes pr,
+                                                                int nx, double *__restrict__ row, int row_doubles)
+{
+	observe_finish_body<Real>(members, src, partials, blocks, blocks, pr, nx, row, row_doubles);
+}
+
+// ---- members of different shape: n_k = nx_k * ny_k from the shape table, G_k = observe_blocks(n_k) -- the member's partition, and with
+// it every bit of its row, is what it is in any ensemble.  Further instantiations: the kernels above keep their code and registers. ----
+
+__device__ __forceinline__ unsigned observe_blocks_of(size_t n)  // observe_blocks
+{
+	const size_t g = (n + kObservePointsPerBlock - 1) / kObservePointsPerBlock;
+	return (unsigned)(g < 1 ? 1 : g > (size_t)kObserveMaxBlocks ? (size_t)kObserveMaxBlocks : g);
+}
+
+// grid (max_k G_k, members): blocks beyond the member's G_k return; member k's partials at partials + k * gridDim.x * 8
+template <typename Real, bool MAPS>
+__global__ void __launch_bounds__(kObserveThreads) crd_observe_sample_mixed_kernel(const EnsembleMember *members, const EnsembleShape *shapes, int src,
+                                                                                   double *__restrict__ partials, double *__restrict__ maps, size_t map_plane, double threshold,
+                                                                                   double t)
+{
+	ConstShape *const sh = (ConstShape *)shapes + blockIdx.y;
+	const size_t n = (size_t)sh->nx * (size_t)sh->ny;
+	const unsigned G = observe_blocks_of(n);
+	if (blockIdx.x >= G) return;
+	observe_sample_body<Real, MAPS, false>(members, src, n, partials, maps, map_plane, threshold, t, ObserveCycles{}, G, gridDim.x);
+}
+
+template <typename Real>
+__global__ void __launch_bounds__(64) crd_observe_finish_mixed_kernel(const EnsembleMember *members, const EnsembleShape *shapes, int src, const double *__restrict__ partials,
+                                                                      int slots, ObserveProbes pr, double *__restrict__ row, int row_doubles)
+{
+	ConstShape *const sh = (ConstShape *)shapes + blockIdx.x;
+	const int nx = sh->nx;
+	observe_finish_body<Real>(members, src, partials, (int)observe_blocks_of((size_t)nx * (size_t)sh->ny), slots, pr, nx, row, row_doubles);
 }
 
 __global__ void __launch_bounds__(256) crd_observe_fill_kernel(double *__restrict__ x, size_t n, double value)
@@ -458,6 +499,32 @@ hipError_t launch_observe_finish(int precision, const EnsembleMember *table, int
 	const int blocks = observe_blocks(n);
 	if (precision == CRD_PRECISION_F64) crd_observe_finish_kernel<double><<<members, 64, 0, s>>>(table, src, partials_dev, blocks, probes, nx, row_dev, row_doubles);
 	else crd_observe_finish_kernel<float><<<members, 64, 0, s>>>(table, src, partials_dev, blocks, probes, nx, row_dev, row_doubles);
+	return launch_status();
+}
+
+hipError_t launch_observe_sample_mixed(int precision, const EnsembleMember *table, const EnsembleShape *shapes, int members, int src, int max_blocks, double *partials_dev,
+                                       double *maps_dev, size_t map_plane, double threshold, double t, hipStream_t s)
+{
+	clear_launch_status();
+	if (members < 1 || !shapes || max_blocks < 1 || max_blocks > kObserveMaxBlocks) return hipErrorInvalidValue;
+	const dim3 grid((unsigned)max_blocks, (unsigned)members);
+	if (precision == CRD_PRECISION_F64) {
+		if (maps_dev) crd_observe_sample_mixed_kernel<double, true><<<grid, kObserveThreads, 0, s>>>(table, shapes, src, partials_dev, maps_dev, map_plane, threshold, t);
+		else crd_observe_sample_mixed_kernel<double, false><<<grid, kObserveThreads, 0, s>>>(table, shapes, src, partials_dev, nullptr, 0, threshold, t);
+	} else {
+		if (maps_dev) crd_observe_sample_mixed_kernel<float, true><<<grid, kObserveThreads, 0, s>>>(table, shapes, src, partials_dev, maps_dev, map_plane, threshold, t);
+		else crd_observe_sample_mixed_kernel<float, false><<<grid, kObserveThreads, 0, s>>>(table, shapes, src, partials_dev, nullptr, 0, threshold, t);
+	}
+	return launch_status();
+}
+
+hipError_t launch_observe_finish_mixed(int precision, const EnsembleMember *table, const EnsembleShape *shapes, int members, int src, int max_blocks,
+                                       const double *partials_dev, const ObserveProbes &probes, double *row_dev, int row_doubles, hipStream_t s)
+{
+	clear_launch_status();
+	if (members < 1 || !shapes || max_blocks < 1 || probes.n < 0 || probes.n > kObserveMaxProbes || row_doubles < 8 + 2 * probes.n) return hipErrorInvalidValue;
+	if (precision == CRD_PRECISION_F64) crd_observe_finish_mixed_kernel<double><<<members, 64, 0, s>>>(table, shapes, src, partials_dev, max_blocks, probes, row_dev, row_doubles);
+	else crd_observe_finish_mixed_kernel<float><<<members, 64, 0, s>>>(table, shapes, src, partials_dev, max_blocks, probes, row_dev, row_doubles);
 	return launch_status();
 }
 

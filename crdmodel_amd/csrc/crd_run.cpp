@@ -61,7 +61,7 @@ struct Options {
 		std::cerr << "Usage: " << argv0
 		          << " --model fhn|goldbeter --surface torus|flat [--gpus G] [--devices D] [--dt DT] [--stepper auto|staged|fused]\n"
 		             "       [--precision 64|32] [--adaptive|--adaptive-rk43|--fixed] [--binary|--binary-only] [--ref-steady-state] [--decomp D0xD1|mpi [--block-contexts]]\n"
-		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary=V1,V2,... (repeatable)]\n"
+		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary|surfaceLength|surfaceWidth|xMesh|surface=V1,V2,... (repeatable)]\n"
 		             "       [--ensemble-steps 1|2]\n"
 		             "       [--observe STRIDE [--probe I,J (repeatable)] [--observe-maps THRESHOLD]\n"
 		             "                         [--section row:J|column:I|theta-mean|phi-mean (repeatable)] [--observe-cycles THRESHOLD]]\n"
@@ -94,7 +94,23 @@ double *ensemble_field(const std::string &key, crd_params *p)
 	if (key == "betaMax") return &p->beta_max;
 	if (key == "diffusion") return &p->diffusion;
 	if (key == "tBoundary") return &p->t_boundary;
+	if (key == "surfaceLength") return &p->surface_length;
+	if (key == "surfaceWidth") return &p->surface_width;
 	return nullptr;
+}
+// ... and the keys that make the members' geometry differ (crd_ensemble_create_mixed): the two lengths above, xMesh (nx) and surface
+// (torus | flat, held as CRD_SURFACE_*).
+bool ensemble_geometry_key(const std::string &key) { return key == "surfaceLength" || key == "surfaceWidth" || key == "xMesh" || key == "surface"; }
+bool ensemble_key(const std::string &key)
+{
+	crd_params probe{};
+	return ensemble_field(key, &probe) || key == "xMesh" || key == "surface";
+}
+void set_ensemble_value(const std::string &key, double value, crd_params *p)
+{
+	if (key == "xMesh") p->nx = (int64_t)value;
+	else if (key == "surface") p->surface = (int)value;
+	else *ensemble_field(key, p) = value;
 }
 
 [[noreturn]] void usage_error(const std::string &msg)
@@ -107,18 +123,23 @@ void parse_ensemble(const std::string &arg, Options *o)
 {
 	const size_t eq = arg.find('=');
 	const std::string key = arg.substr(0, eq);
-	crd_params probe{};
-	if (eq == std::string::npos || !ensemble_field(key, &probe))
-		usage_error("--ensemble takes KEY=V1,V2,... with KEY one of beta, betaMin, betaMax, diffusion, tBoundary (got '" + arg + "')");
+	if (eq == std::string::npos || !ensemble_key(key))
+		usage_error("--ensemble takes KEY=V1,V2,... with KEY one of beta, betaMin, betaMax, diffusion, tBoundary, surfaceLength, surfaceWidth, xMesh, surface (got '" + arg + "')");
 	std::vector<double> values;
 	size_t at = eq + 1;
 	while (true) {
 		const size_t comma = arg.find(',', at);
 		const std::string v = arg.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
-		char *end = nullptr;
-		const double x = std::strtod(v.c_str(), &end);
-		if (v.empty() || *end != '\0' || !std::isfinite(x)) usage_error("--ensemble " + key + ": '" + v + "' is not a number");
-		values.push_back(x);
+		if (key == "surface") {
+			if (v != "torus" && v != "flat") usage_error("--ensemble surface: '" + v + "' is neither torus nor flat");
+			values.push_back(v == "torus" ? CRD_SURFACE_TORUS : CRD_SURFACE_FLAT);
+		} else {
+			char *end = nullptr;
+			const double x = std::strtod(v.c_str(), &end);
+			if (v.empty() || *end != '\0' || !std::isfinite(x)) usage_error("--ensemble " + key + ": '" + v + "' is not a number");
+			if (key == "xMesh" && (x < 1 || x != std::floor(x) || x > 1e9)) usage_error("--ensemble xMesh: '" + v + "' is not a positive whole number");
+			values.push_back(x);
+		}
 		if (comma == std::string::npos) break;
 		at = comma + 1;
 	}
@@ -264,7 +285,7 @@ bool write_npy_2d(const std::string &path, const std::vector<double> &a, long lo
 
 // What --observe leaves in <outdir>/member_<k>/: observables.txt, one line per sample in the state files' number format, and with
 // --observe-maps amplitude_map.npy (running maximum - running minimum of var0) and activation_time.npy.
-int write_observations(const Options &o, crd_ensemble *ens, int B, const crd_grid &g)
+int write_observations(const Options &o, crd_ensemble *ens, int B)
 {
 	int64_t n = 0;
 	int rc = crd_ensemble_observe_count(ens, &n);
@@ -272,10 +293,12 @@ int write_observations(const Options &o, crd_ensemble *ens, int B, const crd_gri
 	std::vector<double> t((size_t)n), stats((size_t)n * (size_t)B * 8), pv((size_t)n * (size_t)B * P * 2);
 	if (rc == CRD_OK) rc = crd_ensemble_observe_read(ens, 0, n, t.data(), stats.data(), pv.data());
 	if (rc != CRD_OK) return rc;
-	const size_t points = (size_t)(g.nx * g.ny);
-	std::vector<double> lo(points), hi(points), ta(points);
 	std::vector<std::vector<double>> section_values(o.sections.size());
 	for (int k = 0; k < B; k++) {
+		crd_grid g;  // the member's own
+		if ((rc = crd_ensemble_member_grid(ens, k, &g)) != CRD_OK) return rc;
+		const size_t points = (size_t)(g.nx * g.ny);
+		std::vector<double> lo(points), hi(points), ta(points);
 		const std::string dir = o.outdir + "/member_" + std::to_string(k);
 		FILE *f = std::fopen((dir + "/observables.txt").c_str(), "w");
 		if (!f) return CRD_EIO;
@@ -350,8 +373,23 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 	std::vector<crd_run_config> mc((size_t)B, cfg);
 	std::vector<crd_params> mp((size_t)B);
 	for (int k = 0; k < B; k++) {
-		for (const auto &kv : o.ensemble) *ensemble_field(kv.first, &mc[(size_t)k].params) = kv.second[(size_t)k];
+		for (const auto &kv : o.ensemble) set_ensemble_value(kv.first, kv.second[(size_t)k], &mc[(size_t)k].params);
 		mp[(size_t)k] = mc[(size_t)k].params;
+	}
+	// With a geometry key the members may differ in surface and grid (crd_ensemble_create_mixed); where nx or ny truly differ, what
+	// such an ensemble refuses is refused here, before any device is asked for, by the option's name.
+	bool geometry = false;
+	for (const auto &kv : o.ensemble) geometry = geometry || ensemble_geometry_key(kv.first);
+	std::vector<crd_grid> mg((size_t)B);
+	bool shapes_differ = false;
+	for (int k = 0; k < B; k++) {
+		if (crd_grid_from_params(&mp[(size_t)k], &mg[(size_t)k]) != CRD_OK) usage_error("member " + std::to_string(k) + ": bad geometry");
+		shapes_differ = shapes_differ || mg[(size_t)k].nx != mg[0].nx || mg[(size_t)k].ny != mg[0].ny;
+	}
+	if (geometry && shapes_differ) {
+		if (adaptive) usage_error("[Solver] adaptive = 1: members of different shape integrate with fixed steps only (pass --fixed)");
+		if (!o.sections.empty()) usage_error("--section: members of different shape take no sections");
+		if (o.observe_cycles) usage_error("--observe-cycles: members of different shape take no cycle maps");
 	}
 	const int Nt = cfg.output_timestep;
 	const double dTout = cfg.t_final / Nt;
@@ -366,20 +404,23 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 	const double dt = dTout / (double)steps_per_output;
 
 	if (o.observe) {  // (refused before any device is asked for)
-		crd_grid pg;
-		if (crd_grid_from_params(&mp[0], &pg) != CRD_OK) usage_error("bad geometry");
+		const crd_grid &pg = mg[0];
 		for (const auto &q : o.probes)
-			if (q.first < 0 || q.first >= pg.nx || q.second < 0 || q.second >= pg.ny)
-				usage_error("--probe " + std::to_string(q.first) + "," + std::to_string(q.second) + " is outside the " + std::to_string(pg.nx) + " x " + std::to_string(pg.ny) + " grid");
+			for (int k = 0; k < B; k++) {
+				const crd_grid &kg = mg[(size_t)k];
+				if (q.first < 0 || q.first >= kg.nx || q.second < 0 || q.second >= kg.ny)
+					usage_error("--probe " + std::to_string(q.first) + "," + std::to_string(q.second) + " is outside the " + std::to_string(kg.nx) + " x " + std::to_string(kg.ny) + " grid" +
+					            (shapes_differ ? " of member " + std::to_string(k) : std::string()));
+			}
 		for (const auto &q : o.sections)
 			if ((q.first == CRD_SECTION_ROW && (q.second < 0 || q.second >= pg.ny)) || (q.first == CRD_SECTION_COLUMN && (q.second < 0 || q.second >= pg.nx)))
 				usage_error(std::string("--section ") + section_name(q.first) + ":" + std::to_string(q.second) + " is outside the " + std::to_string(pg.nx) + " x " + std::to_string(pg.ny) + " grid");
 	}
 
 	crd_ensemble *ens = nullptr;
-	int rc = crd_ensemble_create(mp.data(), B, 0, &ens);
+	int rc = geometry ? crd_ensemble_create_mixed(mp.data(), B, 0, &ens) : crd_ensemble_create(mp.data(), B, 0, &ens);
 	if (rc != CRD_OK) {
-		std::cerr << "\nCRD_ERROR: crd_ensemble_create failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(nullptr) << "\n\n";
+		std::cerr << "\nCRD_ERROR: " << (geometry ? "crd_ensemble_create_mixed" : "crd_ensemble_create") << " failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(nullptr) << "\n\n";
 		return 1;
 	}
 	if (o.ensemble_steps && (rc = crd_ensemble_set_steps_per_launch(ens, o.ensemble_steps)) != CRD_OK) {
@@ -391,10 +432,11 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 	crd_ensemble_info(ens, nullptr, &g);
 	if (!o.quiet) {
 		std::cout << "\nEnsemble of " << B << " members on one GPU (" << (mp[0].model == CRD_MODEL_FHN ? "FHN" : "Goldbeter") << ", "
-		          << (mp[0].surface == CRD_SURFACE_TORUS ? "torus" : "flat surface") << ", nx = " << g.nx << ", ny = " << g.ny << "):\n";
+		          << (geometry ? std::string("each member's own surface and grid") : std::string(mp[0].surface == CRD_SURFACE_TORUS ? "torus" : "flat surface") + ", nx = " + std::to_string(g.nx) + ", ny = " + std::to_string(g.ny)) << "):\n";
 		for (int k = 0; k < B; k++) {
 			std::cout << "   member " << k << ":";
 			for (const auto &kv : o.ensemble) std::cout << " " << kv.first << " = " << kv.second[(size_t)k];
+			if (geometry) std::cout << "  (" << mg[(size_t)k].nx << " x " << mg[(size_t)k].ny << ")";
 			std::cout << "  -> " << o.outdir << "/member_" << k << "\n";
 		}
 		std::cout << "   Tfinal = " << cfg.t_final << ", output timesteps = " << Nt << "\n";
@@ -408,7 +450,9 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 	}
 
 	std::vector<crd_writer *> wr((size_t)B, nullptr);
-	std::vector<double> buf((size_t)(2 * g.nx * g.ny));
+	int64_t most_points = 0;
+	for (const crd_grid &kg : mg) most_points = std::max(most_points, kg.nx * kg.ny);
+	std::vector<double> buf((size_t)(2 * most_points));  // (the largest member's state; a member fills its own nx * ny pairs)
 	auto cleanup = [&]() {
 		for (auto *w : wr) crd_writer_close(w);
 		crd_ensemble_destroy(ens);
@@ -417,7 +461,7 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		const std::string dir = o.outdir + "/member_" + std::to_string(k);
 		std::error_code ec;
 		std::filesystem::create_directories(dir, ec);
-		if ((rc = crd_initial_conditions(&mc[(size_t)k], 0, g.ny - 1, buf.data())) != CRD_OK) {
+		if ((rc = crd_initial_conditions(&mc[(size_t)k], 0, mg[(size_t)k].ny - 1, buf.data())) != CRD_OK) {
 			die("crd_initial_conditions", rc, nullptr);
 			cleanup();
 			return 1;
@@ -519,7 +563,7 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 			std::fflush(stdout);
 		}
 	}
-	if (o.observe && (rc = write_observations(o, ens, B, g)) != CRD_OK) {
+	if (o.observe && (rc = write_observations(o, ens, B)) != CRD_OK) {
 		std::cerr << "\nCRD_ERROR: writing the observations failed with flag = " << rc << " (" << crd_status_string(rc) << "): " << crd_ensemble_last_error(ens) << "\n\n";
 		cleanup();
 		return 1;
@@ -543,7 +587,9 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		std::printf("   rate: %d members, %lld attempts in %.6f s of stepping = %.1f attempts/s\n", B, attempts, stepping_s, (double)attempts / stepping_s);
 		std::cout << "   ----------------------\n";
 	} else if (!o.quiet && stepping_s > 0.0) {
-		const double ps = (double)B * (double)g.nx * (double)g.ny * (double)steps_per_output * Nt / stepping_s;
+		double points = 0.0;  // (every member's own grid: they may differ in shape)
+		for (const crd_grid &kg : mg) points += (double)kg.nx * (double)kg.ny;
+		const double ps = points * (double)steps_per_output * Nt / stepping_s;
 		std::printf("\n   rate: %d members x %lld steps in %.6f s of stepping = %.4g grid-point-steps/s\n", B, (long long)steps_per_output * Nt, stepping_s, ps);
 		std::cout << "   ----------------------\n";
 	}

@@ -389,25 +389,44 @@ def _section_kind(kind):
 
 class Ensemble:
     """B independent single-slab problems on one GPU, stepped by one launch per RK4 step (crd_ensemble).  params_list: one Params per
-    member; members share model, surface, nx, ny, surface length / width, precision and justDiffusion, and may differ in diffusion,
-    beta, betaMin, betaMax, varyBeta and tBoundary.  Each member's result is bit-identical to a Slab of the same params stepped alone."""
+    member; by default members share model, surface, nx, ny, surface length / width, precision and justDiffusion, and may differ in diffusion,
+    beta, betaMin, betaMax, varyBeta and tBoundary.  Each member's result is bit-identical to a Slab of the same params stepped alone.
+    mixed=True (crd_ensemble_create_mixed): members share model, precision and justDiffusion only and may also differ in surface, nx, ny
+    and the surface's length and width; grid(member) is each member's own grid, and upload, download and observed_maps are shaped by it.
+    Members of different nx or ny take fixed steps (one or two per launch) and the basic observer; integrate_adaptive, sections and
+    cycle maps raise CrdError for them."""
 
-    def __init__(self, params_list, device=0):
+    def __init__(self, params_list, device=0, mixed=False):
         self._h = C.c_void_p()
         self.params = list(params_list)
         arr = (Params * max(len(self.params), 1))(*self.params)
-        rc = lib().crd_ensemble_create(arr, len(self.params), device, C.byref(self._h))
+        create, name = (lib().crd_ensemble_create_mixed, "crd_ensemble_create_mixed") if mixed else (lib().crd_ensemble_create, "crd_ensemble_create")
+        rc = create(arr, len(self.params), device, C.byref(self._h))
         if rc != capi.OK:
             self._h = None
-            raise CrdError(rc, "crd_ensemble_create", lib().crd_ensemble_last_error(None).decode())
+            raise CrdError(rc, name, lib().crd_ensemble_last_error(None).decode())
         n, g = C.c_int(), Grid()
         self._check(lib().crd_ensemble_info(self._h, C.byref(n), C.byref(g)), "crd_ensemble_info")
-        self.n_members, self.grid = n.value, g
-        self.nx, self.ny = g.nx, g.ny
+        self.n_members = n.value
+        self.nx, self.ny = g.nx, g.ny  # member 0's
+        self.grids = []
+        for k in range(self.n_members):
+            gk = Grid()
+            self._check(lib().crd_ensemble_member_grid(self._h, k, C.byref(gk)), "crd_ensemble_member_grid")
+            self.grids.append(gk)
         self.dtype = np.float64 if self.params[0].precision == PRECISION_F64 else np.float32
 
     def __len__(self):
         return self.n_members
+
+    def grid(self, member=0):
+        """Member `member`'s grid (crd_ensemble_member_grid); without mixed=True every member's is member 0's.  (Before mixed
+        geometry `grid` was an attribute holding the common Grid: `e.grid.nx` is now `e.grid().nx`, or `e.nx`.)"""
+        return self.grids[member]
+
+    def _shape(self, member):
+        g = self.grids[member]
+        return (g.ny, g.nx)
 
     # -- lifecycle ---------------------------------------------------------------------------------------------
     def close(self):
@@ -438,7 +457,7 @@ class Ensemble:
     # -- state -------------------------------------------------------------------------------------------------
     def upload(self, member, y):
         y = np.ascontiguousarray(y)
-        assert y.shape == (self.ny, self.nx, 2), (y.shape, (self.ny, self.nx, 2))
+        assert y.shape == self._shape(member) + (2,), (y.shape, self._shape(member) + (2,))
         if y.dtype == np.float64:
             self._check(lib().crd_ensemble_upload(self._h, member, y.ctypes.data, 1), "crd_ensemble_upload")
         elif y.dtype == np.float32 and self.dtype == np.float32:
@@ -447,7 +466,7 @@ class Ensemble:
             raise TypeError("state must be float64, or float32 for an f32 ensemble")
 
     def download(self, member, dtype=np.float64):
-        y = np.empty((self.ny, self.nx, 2), dtype=dtype)
+        y = np.empty(self._shape(member) + (2,), dtype=dtype)
         self._check(lib().crd_ensemble_download(self._h, member, y.ctypes.data, 1 if y.dtype == np.float64 else 0), "crd_ensemble_download")
         return y
 
@@ -578,7 +597,7 @@ class Ensemble:
         stats = np.empty((count, self.n_members, 2, 4))
         probes = np.empty((count, self.n_members, P, 2))
         self._check(lib().crd_ensemble_observe_read(self._h, first, count, t.ctypes.data, stats.ctypes.data, probes.ctypes.data), "crd_ensemble_observe_read")
-        n = float(info["values_per_field"])
+        n = np.array([float(g.nx) * float(g.ny) for g in self.grids])[None, :, None]  # values per field, per member
         mean = stats[..., 2] / n
         with np.errstate(invalid="ignore"):
             variance = np.maximum(stats[..., 3] / n - mean * mean, 0.0)
@@ -587,7 +606,7 @@ class Ensemble:
 
     def observed_maps(self, member):
         """Member `member`'s maps as they stand: (running minimum of var0, running maximum, activation time), [ny, nx] each."""
-        out = [np.empty((self.ny, self.nx)) for _ in range(3)]
+        out = [np.empty(self._shape(member)) for _ in range(3)]
         self._check(lib().crd_ensemble_observe_maps(self._h, member, *[a.ctypes.data for a in out]), "crd_ensemble_observe_maps")
         return tuple(out)
 

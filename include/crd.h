@@ -516,9 +516,11 @@ int crd_state_max_abs(crd_ctx *ctx, double *out);
  * Ensembles: B independent single-slab problems stepped together, one launch per RK4 step for all of them -- what a parameter
  * scan of the reference does with B separate runs (`mpirun ... FHNmodel_torus <ini>` once per value, src/FHNmodel_torus.cpp:148-497),
  * each with its own ARKode stepping loop.  On the reference's own small grids (data/FHNmodelArgs.ini: 400 x 1600) one problem's step
- * is bound by the launch, not by the device; B members share that launch.  Members must agree on model, surface, nx, the derived ny,
- * surface length and width, precision and justDiffusion; they may differ in diffusion, beta, betaMin, betaMax, varyBeta and
- * tBoundary.  One device.  Fixed-step classical RK4 (crd_ensemble_step_rk4): every member's result is bit-identical to a context
+ * is bound by the launch, not by the device; B members share that launch.  Members of crd_ensemble_create must agree on model,
+ * surface, nx, the derived ny, surface length and width, precision and justDiffusion; they may differ in diffusion, beta, betaMin,
+ * betaMax, varyBeta and tBoundary.  Members of crd_ensemble_create_mixed must agree on model, precision and justDiffusion only: the
+ * reference's own scan -- torus 80/20 against torus 40/20 against the flat control (data/FHNmodelArgs.ini: surfaceLength "80 for
+ * normal, 40 for more curved surface") -- in one ensemble; every size below is then the member's own.  One device.  Fixed-step classical RK4 (crd_ensemble_step_rk4): every member's result is bit-identical to a context
  * (crd_create) of the same parameters stepped alone with crd_step_rk4 and the one-launch stepper.  Error-controlled integration
  * (crd_ensemble_integrate_adaptive): every member takes its own step sequence, as a context of its parameters integrated alone with
  * crd_integrate_adaptive would.  Not thread-safe; calls on one ensemble must be serialised.
@@ -529,11 +531,24 @@ typedef struct crd_ensemble crd_ensemble;
  * CRD_EHIP without a device.  Each member owns two state buffers of its own (no ghost rows, none of a context's other planes); the
  * state starts at zero.  Replaces InitUserData + SetupDecomp of B single-rank runs (src/FHNmodel_torus.cpp:708-772). */
 int crd_ensemble_create(const crd_params *members, int n_members, int device, crd_ensemble **out);
+/* crd_ensemble_create for members that may also differ in surface, nx, ny, surface length and surface width (they must agree on model,
+ * precision and justDiffusion).  Refused before any HIP call, crd_ensemble_last_error(NULL) naming the member and the field: such a
+ * disagreement, a member of fewer than 8 rows, block ids of all members together overflowing 32 bits; CRD_EHIP without a device.
+ * Members that all share nx and ny (torus and flat at one mesh, lengths with ny pinned) make an ordinary ensemble: it launches exactly
+ * what crd_ensemble_create's launches and keeps every call below.  Members of different shape step with crd_ensemble_step_rk4 /
+ * _timed at one or two steps per launch -- a block finds its member by a scalar search of a per-member table of shapes; one chunk height
+ * and block size per launch, a fixed rule of the shapes, precision, model and member order -- and take the basic observer
+ * (crd_ensemble_observe_begin: statistics, probes, maps); every member's state, statistics row, probe values and maps stay bit-identical
+ * to the same problem alone.  They refuse, with CRD_EINVAL and "members of different shape" in crd_ensemble_last_error, and nothing
+ * opened or allocated: crd_ensemble_integrate_adaptive, and crd_ensemble_observe_begin_with with any section or with cycles. */
+int crd_ensemble_create_mixed(const crd_params *members, int n_members, int device, crd_ensemble **out);
 void crd_ensemble_destroy(crd_ensemble *e);
 const char *crd_ensemble_last_error(const crd_ensemble *e); /* never NULL; e may be NULL (creation errors) */
-/* Member count and the members' common grid.  Either pointer may be NULL. */
+/* Member count and the members' common grid (crd_ensemble_create_mixed: member 0's).  Either pointer may be NULL. */
 int crd_ensemble_info(const crd_ensemble *e, int *n_members, crd_grid *g);
-/* State of ONE member in the boundary layout (AoS, ny * nx pairs; host_is_f64 as crd_state_upload).  Synchronous; other members'
+/* Member `member`'s own grid.  CRD_EINVAL for a null pointer or an index out of range. */
+int crd_ensemble_member_grid(const crd_ensemble *e, int member, crd_grid *g);
+/* State of ONE member in the boundary layout (AoS, the member's ny * nx pairs; host_is_f64 as crd_state_upload).  Synchronous; other members'
  * states are not touched.  Stands in for the initial-condition upload of that member's run (src/FHNmodel_torus.cpp:285-354). */
 int crd_ensemble_upload(crd_ensemble *e, int member, const void *y_aos_host, int host_is_f64);
 int crd_ensemble_download(crd_ensemble *e, int member, void *y_aos_host, int host_is_f64);
@@ -549,7 +564,7 @@ int crd_ensemble_synchronize(crd_ensemble *e);
  * open a pair never straddles a sample (the step that completes a stride is taken alone).  Results, samples and sample times are those
  * of single steps bit for bit: a pair is the sequence of two single steps per point.  The two-step pipeline needs room in phi (an item
  * touches its rows and 16 apron rows, fewer than 2 ny in all): CRD_EINVAL for steps = 2 on members of fewer than
- * CRD_ENSEMBLE_PAIR_MIN_ROWS rows, and for any steps other than 1 or 2 (crd_ensemble_last_error says which); the setting is then
+ * CRD_ENSEMBLE_PAIR_MIN_ROWS rows (members of different shape: any member, named), and for any steps other than 1 or 2 (crd_ensemble_last_error says which); the setting is then
  * unchanged.  The first call with 2 plans the pair launches (a fixed rule of grid, precision, model and member count).  A library built
  * without the build-time check of the pair kernels' assembly (make KERNEL_TABLE=0) carries no pair kernels and refuses 2 likewise.
  * crd_ensemble_integrate_adaptive takes attempts, not steps, and is not affected. */
@@ -627,6 +642,8 @@ int crd_ensemble_observe_read(crd_ensemble *e, int64_t first, int64_t count, dou
 int crd_ensemble_observe_maps(crd_ensemble *e, int member, double *min_u, double *max_u, double *t_act);
 /* What states the rounding bound above: sampling blocks per member, values per field (nx ny), and the observer's options and
  * capacity.  Any pointer may be NULL.  CRD_EINVAL with no observer open. */
+/* (members of different shape, crd_ensemble_create_mixed: blocks_per_member and values_per_field are member 0's, as crd_ensemble_info's
+ * grid; member k's are those of its own nx * ny, crd_ensemble_member_grid) */
 int crd_ensemble_observe_info(const crd_ensemble *e, int32_t *blocks_per_member, int64_t *values_per_field, crd_observe_options *opt, int64_t *capacity);
 /* Close the observer and free what it holds (crd_ensemble_destroy does too).  CRD_EINVAL with no observer open. */
 int crd_ensemble_observe_end(crd_ensemble *e);

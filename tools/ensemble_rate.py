@@ -14,6 +14,15 @@ batch timed by events on the ensemble's stream; reports the median per-step time
 the medians.  --precision 64|32.
 
     python tools/ensemble_rate.py --steps-per-launch 1,2 [--precision 32] [--batches 11] [--cases fhn] [--members 16]
+
+--mixed measures a mixed-geometry ensemble (Ensemble(..., mixed=True)): 8 members of the shipped FHN 400 x 1600 grid plus 8 of
+400 x 800 (surfaceLength 40), fp64, ONE launch per step (or pair) for all sixteen, against the same members as TWO uniform ensembles
+stepped one after the other (each batch timed by events and waited for before the other starts; the sum of the two).  One process:
+after a warm-up, --batches batches (at least 9) per arrangement and setting, interleaved batch by batch; median, spread and the ratio
+two-uniform / mixed per --steps-per-launch setting (default 1,2).  --root DIR imports crdmodel_amd from another checkout: with a build
+of the parent commit (no mixed entry point) only the two uniform ensembles are timed -- the same-visit check that nothing existing moved.
+
+    python tools/ensemble_rate.py --mixed [--batches 11] [--root ../parent-build] [--json OUT]
 """
 import argparse
 import json
@@ -24,6 +33,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--root" in sys.argv[1:-1]:  # (before the import below: the package of another checkout)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--root") + 1])
 sys.path.insert(0, ROOT)
 import crdmodel_amd as crd  # noqa: E402
 
@@ -161,6 +172,84 @@ def main_settings(a):
             json.dump({"device": "MI355X", "rows": rows}, f, indent=1)
 
 
+def mixed_members():
+    """8 members of the shipped FHN grid (400 x 1600) and 8 at surfaceLength 40 (400 x 800), one beta each."""
+    p = crd.load_ini(os.path.join(INI, "fhn_shipped.ini"), "fhn", "torus").params
+    out = []
+    for k, b in enumerate(np.linspace(0.9, 1.3, 16)):
+        q = crd._capi.Params.from_buffer_copy(p)
+        q.beta, q.t_boundary = float(b), 0.0
+        if k >= 8:
+            q.surface_length = 40.0
+        out.append(q)
+    return out
+
+
+def main_mixed(a):
+    settings = [int(x) for x in (a.steps_per_launch or "1,2").split(",")]
+    if a.batches < 9:
+        sys.exit("--batches: at least 9")
+    members = mixed_members()
+    grids = [crd.grid_of(m) for m in members]
+    assert (grids[0].nx, grids[0].ny, grids[8].nx, grids[8].ny) == (400, 1600, 400, 800), [(g.nx, g.ny) for g in grids]
+    points = sum(g.nx * g.ny for g in grids)
+    dt = 0.8 * min(crd.stable_dt(m) for m in members)
+    y0 = [crd.initial_conditions(crd.run_config(m)) for m in members]
+    has_mixed = hasattr(crd._capi.lib(), "crd_ensemble_create_mixed")
+    arrangements = {"two_uniform": [crd.Ensemble(members[:8]), crd.Ensemble(members[8:])]}
+    if has_mixed:
+        arrangements["mixed"] = [crd.Ensemble(members, mixed=True)]
+    try:
+        for name, ens in arrangements.items():
+            first = 0
+            for e in ens:
+                for k in range(len(e)):
+                    e.upload(k, y0[first + k])
+                first += len(e)
+
+        def batch(name, k, steps):  # ms of `steps` steps: the ensembles of the arrangement one after the other
+            ms = 0.0
+            for e in arrangements[name]:
+                e.set_steps_per_launch(k)
+                ms += e.step_rk4_timed(0.0, dt, steps)
+            return ms
+
+        ms = batch("two_uniform", 1, 16)
+        ms = batch("two_uniform", 1, 16)
+        steps = max(16, 2 * int(0.05 * a.window * 1e3 / max(ms / 16, 1e-6)))
+        t_end = time.perf_counter() + a.window
+        while time.perf_counter() < t_end:
+            for name in arrangements:
+                for k in settings:
+                    batch(name, k, steps)
+        us = {(name, k): [] for name in arrangements for k in settings}
+        for _ in range(a.batches):
+            for k in settings:
+                for name in arrangements:
+                    us[(name, k)].append(1e3 * batch(name, k, steps) / steps)
+    finally:
+        for ens in arrangements.values():
+            for e in ens:
+                e.close()
+    row = {"case": "fhn 8 x 400x1600 + 8 x 400x800", "precision": 64, "steps_per_batch": steps, "batches": a.batches, "dt": dt, "root": ROOT, "mixed_entry_point": has_mixed,
+           "settings": {}}
+    for k in settings:
+        row["settings"][str(k)] = {}
+        for name in arrangements:
+            v = us[(name, k)]
+            med = float(np.median(v))
+            row["settings"][str(k)][name] = {"us_per_step_median": med, "us_per_step_min": min(v), "us_per_step_max": max(v), "gpss": points / (med * 1e-6)}
+        q = row["settings"][str(k)]
+        print("steps/launch %d:  " % k + "  ".join("%s %8.2f us/step (%.2f .. %.2f) %.3e gpss" % (name, r["us_per_step_median"], r["us_per_step_min"], r["us_per_step_max"], r["gpss"])
+                                                  for name, r in q.items())
+              + ("  two_uniform / mixed x%.3f" % (q["two_uniform"]["us_per_step_median"] / q["mixed"]["us_per_step_median"]) if has_mixed else "  (no mixed entry point in this build)")
+              + "  [%d batches of %d steps]" % (a.batches, steps), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump({"device": "MI355X", "rows": [row]}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--members", default="1,4,16,64")
@@ -170,7 +259,11 @@ def main():
     ap.add_argument("--steps-per-launch", default=None, help="e.g. 1,2: the ensemble alone under each setting, interleaved batches")
     ap.add_argument("--precision", type=int, choices=(64, 32), default=64)
     ap.add_argument("--batches", type=int, default=11)
+    ap.add_argument("--mixed", action="store_true", help="a mixed-geometry ensemble against the same members as two uniform ensembles in sequence")
+    ap.add_argument("--root", default=None, help="import crdmodel_amd from this checkout (a build of another commit)")
     a = ap.parse_args()
+    if a.mixed:
+        return main_mixed(a)
     if a.steps_per_launch:
         return main_settings(a)
     rows = []
