@@ -181,8 +181,8 @@ int crd_create_block(const crd_params *p, int c0, int d0, int c1, int d1, int de
 	// CRD_LAUNCH_PLAN=mode,mapping,columns,nt: what crd_set_launch_plan does, for a program one cannot change (crd_run under a profiler)
 	if (const char *e = std::getenv("CRD_LAUNCH_PLAN")) {
 		int m = -1, k = -1, cols = -1, nt = 0, st = 1;
-		if (std::sscanf(e, "%d,%d,%d,%d,%d", &m, &k, &cols, &nt, &st) >= 3 && m >= 0 && m <= 2 && k >= 0 && k <= 2 && cols >= 1 && cols <= 2 && nt >= 0 && nt <= 1 && st >= 1 &&
-		    st <= 3) {
+		if (std::sscanf(e, "%d,%d,%d,%d,%d", &m, &k, &cols, &nt, &st) >= 3 && m >= 0 && m <= 3 && k >= 0 && k <= 2 && cols >= 1 && cols <= 2 && nt >= 0 && nt <= 1 && st >= 1 &&
+		    st <= 3 && (m != 3 || st == 3)) {
 			c->plan.tuned = c->plan.pinned = 1;
 			c->plan.one_round = m;
 			c->plan.remap = k;
@@ -699,9 +699,10 @@ int crd_set_autotune(crd_ctx *c, int on)
 int crd_set_launch_plan(crd_ctx *c, int chunk_mode, int xcd_mapping, int columns_per_lane, int nontemporal_stores, int steps_per_launch)
 {
 	if (!c) return CRD_EINVAL;
-	if (chunk_mode < 0 || chunk_mode > 2 || xcd_mapping < 0 || xcd_mapping > 2 || columns_per_lane < 1 || columns_per_lane > 2 || nontemporal_stores < 0 ||
-	    nontemporal_stores > 1 || steps_per_launch < 1 || steps_per_launch > 3)
-		return fail(c, CRD_EINVAL, "crd_set_launch_plan: chunk mode 0..2, mapping 0..2, columns per lane 1..2, non-temporal stores 0..1, steps per launch 1..3");
+	if (chunk_mode < 0 || chunk_mode > 3 || xcd_mapping < 0 || xcd_mapping > 2 || columns_per_lane < 1 || columns_per_lane > 2 || nontemporal_stores < 0 ||
+	    nontemporal_stores > 1 || steps_per_launch < 1 || steps_per_launch > 3 ||
+	    (chunk_mode == 3 && steps_per_launch != 3))  // (the eight-wide block strip is a three-step plan)
+		return fail(c, CRD_EINVAL, "crd_set_launch_plan: chunk mode 0..3 (3: with three steps per launch only), mapping 0..2, columns per lane 1..2, non-temporal stores 0..1, steps per launch 1..3");
 	// (the error-controlled integrators' instantiations take the plan too; they step one column per lane whatever it says)
 	for (FusedPlan *pl : {&c->plan, &c->plan_embed, &c->plan_arkode}) {
 		pl->tuned = pl->pinned = 1;
@@ -722,6 +723,8 @@ int crd_get_launch_plan(const crd_ctx *c, crd_launch_plan *out)
 	out->autotune = c->plan.autotune;
 	out->tuned = c->plan.tuned;
 	out->one_round = c->plan.one_round;
+	// (chunk mode 3, the eight-wide block strip, is the three-step fp64 FHN kernel's alone: everywhere else it is mode 1)
+	if (c->plan.one_round == 3 && !(c->plan.tuned && fused_wide_supported(c->p.precision, c->desc, c->plan.steps))) out->one_round = 1;
 	out->xcd_mapping = c->plan.remap;
 	out->rows = c->plan.rows;
 	// (without a plan the launches take the default of their precision: two columns per lane in fp32 on an even nx)
@@ -771,7 +774,7 @@ int crd_get_launch_geometry(crd_ctx *c, crd_launch_geometry *out)
 	out->rows = (int32_t)rows;
 	out->wavefront_iterations = g.wave_iterations;
 	out->wavefront_iterations_effective = g.wave_iterations - (int64_t)g.strips * g.chunks * (g.fill_iterations / 2 + 1);
-	if (const KernelStats *k = step_kernel_stats(g.real_bytes, g.model, g.absorb, g.embed, g.cols, g.nt, g.steps)) {
+	if (const KernelStats *k = step_kernel_stats(g.real_bytes, g.model, g.absorb, g.embed, g.cols, g.nt, g.steps, g.waves_per_block > 4 ? g.waves_per_block : 4)) {
 		out->vgprs = k->vgprs;
 		out->sgprs = k->sgprs;
 		out->lds_bytes = k->lds_bytes;

@@ -24,6 +24,12 @@ int fused_steps_supported(int precision, const SlabDesc &d, int want)
 	return (want >= 2 && fused_two_steps_supported(d)) ? 2 : 1;
 }
 
+// Chunk mode 3 (eight wavefronts per block strip): where a launch of the plan is the three-step fp64 FHN kernel's (crd_fused_impl.h: kCanWide).
+bool fused_wide_supported(int precision, const SlabDesc &d, int want_steps)
+{
+	return precision == CRD_PRECISION_F64 && kernel_model(d) == CRD_MODEL_FHN && fused_steps_supported(precision, d, want_steps) == 3;
+}
+
 int fused_max_items(const SlabDesc &d)
 {
 	// upper bound on the work items of any launch on this slab: the narrowest strips, the shortest chunks the heuristic uses

@@ -41,7 +41,7 @@ constexpr int kApron = 4;                    // RK4 stages = halo depth
 constexpr int kLanes = 64;
 constexpr int kValid = kLanes - 2 * kApron;  // 56 output columns per wavefront
 constexpr int kWavesPerBlock = 4;     // default; the launch may use 1 .. kMaxWavesPerBlock (tuning knob)
-constexpr int kMaxWavesPerBlock = 4;  // (8 strips per workgroup never measured faster than 4)
+constexpr int kMaxWavesPerBlock = 4;  // (8 strips per workgroup never measured faster than 4 -- with a strip, and an apron, per WAVEFRONT; the one kernel whose block shares ONE apron and is bound by issue, the three-step fp64 block strip, has an eight-wide form: kWideWaves, profiles/r08/block_strip_eight_ab.txt)
 // Rows in flight per wavefront (a divisor of the unroll factor, so slots stay static).  Tuning builds override per model.
 #ifndef CRD_PREFETCH_FHN
 #define CRD_PREFETCH_FHN 4
@@ -173,6 +173,11 @@ constexpr bool kReadAhead = false;
 template <typename Real, int MODEL, int COLS, int STEPS>
 constexpr bool kReadAhead = kCoop<Real, MODEL, COLS, STEPS> && STEPS == 3;
 #endif
+// The eight-wide block strip (launch-plan chunk mode 3): the three-step fp64 FHN kernel with EIGHT wavefronts around one apron -- 488 valid
+// lanes of 512 instead of 232 of 256 -- as the only block of its CU (244 VGPRs: eight wavefronts per CU).
+constexpr int kWideWaves = 8;
+template <typename Real, int MODEL, int COLS, int STEPS>
+constexpr bool kCanWide = sizeof(Real) == 8 && MODEL == CRD_MODEL_FHN && COLS == 1 && STEPS == 3 && kCoop<Real, MODEL, COLS, STEPS>;
 // An edge slot holds the 4 STEPS quantities of an iteration (each step's input row and its three stage values): 64 B at two steps,
 // 96 of 128 at three.
 // (Round 6 tried slots placed on the LDS banks lanes 0 / 63 would have had in the dump area -- lane 63's slot shares its banks with lane
@@ -181,12 +186,13 @@ constexpr bool kReadAhead = kCoop<Real, MODEL, COLS, STEPS> && STEPS == 3;
 // cost is the transfer of its operands to the LDS, six cycles whatever the banks do; profiles/r06/three_step_ab.txt.)
 template <int STEPS>
 constexpr int kEdgeSlotBytes = STEPS == 3 ? 128 : 64;
-template <int STEPS>
-constexpr int kEdgeParityBytes = 4 /* kMaxWavesPerBlock */ * 2 * kEdgeSlotBytes<STEPS>;  // [wavefront][side]
-template <int STEPS>
-constexpr int kEdgeBytes = 2 * kEdgeParityBytes<STEPS>;                                  // [parity]
-template <int STEPS>
-constexpr int kEdgeDumpBytes = 4 /* kMaxWavesPerBlock */ * 64 * 8 + kEdgeBytes<STEPS>;   // where the lanes in between drop their values (+ the largest slot offset)
+// (WAVES: the wavefronts of the block -- kMaxWavesPerBlock, or 8 in the eight-wide three-step block strip, kWideWaves below)
+template <int STEPS, int WAVES = 4 /* kMaxWavesPerBlock */>
+constexpr int kEdgeParityBytes = WAVES * 2 * kEdgeSlotBytes<STEPS>;  // [wavefront][side]
+template <int STEPS, int WAVES = 4>
+constexpr int kEdgeBytes = 2 * kEdgeParityBytes<STEPS, WAVES>;       // [parity]
+template <int STEPS, int WAVES = 4>
+constexpr int kEdgeDumpBytes = WAVES * 64 * 8 + kEdgeBytes<STEPS, WAVES>;  // where the lanes in between drop their values (+ the largest slot offset)
 __device__ __forceinline__ double from_lane_below_old(double x, double old)
 {
 	int lo = __double2loint(x), hi = __double2hiint(x);
@@ -712,8 +718,8 @@ __device__ __forceinline__ void ring_read_ahead(unsigned, V &, V &) {}  // (kRea
 template <typename V, int N>
 __device__ __forceinline__ void ring_row_landed(V &, V &, double2r (&)[N]) {}
 // LDS bytes of a block's rings
-template <typename Real, int COLS, int STEPS = 2>
-constexpr int kRingBytes = kMaxWavesPerBlock * kRingRowsOf<typename LaneValue<Real, COLS>::type, STEPS> * 2 * kLanes * COLS * (int)sizeof(Real);
+template <typename Real, int COLS, int STEPS = 2, int WAVES = kMaxWavesPerBlock>
+constexpr int kRingBytes = WAVES * kRingRowsOf<typename LaneValue<Real, COLS>::type, STEPS> * 2 * kLanes * COLS * (int)sizeof(Real);
 
 // TWO classical RK4 steps of the item's rows in one pass over memory (STEPS = 2): the pipeline of fused_item twice over, eight stages
 // deep -- iteration m takes row p (out of its LDS ring slot), runs stages 1..4 of step n on rows p-1 .. p-4, hands the new row p-4
@@ -727,7 +733,7 @@ constexpr int kRingBytes = kMaxWavesPerBlock * kRingRowsOf<typename LaneValue<Re
 // Slot arithmetic: row r of either pipeline lives in slot r mod 4; the second pipeline's rows are the first one's shifted by 4,
 // i.e. the SAME slots -- the stage code is one lambda applied to two sets of arrays.  Per point the arithmetic is the sequence of
 // two single steps exactly (same fused multiply-adds, same constants), so the result is theirs bit for bit.
-template <typename Real, int MODEL, bool ABSORB, int COLS, bool NT, int STEPS = 2>
+template <typename Real, int MODEL, bool ABSORB, int COLS, bool NT, int STEPS = 2, int WAVES = kMaxWavesPerBlock>
 __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const FusedArgs<Real> &a, const int strip, const int chunk, lds_char *const block_rings,
                                                       const int sblk = 0, lds_char *const block_edges = nullptr)
 {
@@ -841,7 +847,7 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	if constexpr (COOP) {
 		const unsigned base = (unsigned)(uintptr_t)block_edges;
 		edge_pub = (lane == 0 || lane == kLanes - 1) ? base + (unsigned)((wave * 2 + (lane == 0 ? 0 : 1)) * kEdgeSlotBytes<STEPS>)
-		                                             : base + (unsigned)(kEdgeBytes<STEPS> + (wave * kLanes + lane) * 8);
+		                                             : base + (unsigned)(kEdgeBytes<STEPS, WAVES> + (wave * kLanes + lane) * 8);
 		edge_con = base + (unsigned)((lane == 0 ? (wave > 0 ? wave - 1 : wave) * 2 + 1 : (wave + 1 < a.sw ? wave + 1 : wave) * 2) * kEdgeSlotBytes<STEPS>);
 	}
 	const unsigned ring_lane = (unsigned)(uintptr_t)ring + (unsigned)lane * (unsigned)sizeof(V);
@@ -889,7 +895,7 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	};
 	auto stages = [&](Pipe &Q, const int p, auto kk, auto live_c, const int flag_bit, const Real b4, V &nu, V &nv, [[maybe_unused]] const V (&E)[4], auto qbase_c) {
 		constexpr int K = decltype(kk)::value;
-		[[maybe_unused]] constexpr int PUB = (K & 1) * kEdgeParityBytes<STEPS> + decltype(qbase_c)::value * 8;
+		[[maybe_unused]] constexpr int PUB = (K & 1) * kEdgeParityBytes<STEPS, WAVES> + decltype(qbase_c)::value * 8;
 		constexpr int live = decltype(live_c)::value;  // (compile-time: the filling iterations are so many pieces of straight-line code)
 		constexpr int S0 = K % M, S1 = (K + M - 1) % M, S2 = (K + M - 2) % M, S3 = (K + M - 3) % M, S4 = (K + 2 * M - 4) % M, S5 = (K + 2 * M - 5) % M;
 		V du, dv;
@@ -954,13 +960,13 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			ring_row_landed(P[0].u0[S0], P[0].v0[S0], edge);
 #pragma unroll
 			for (int n = 0; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
-			edge_publish<(K & 1) * kEdgeParityBytes<STEPS>>(edge_pub, P[0].u0[S0]);
+			edge_publish<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_pub, P[0].u0[S0]);
 		} else if constexpr (COOP) {
 			// ... together with the neighbours' edge values, whose reads the previous iteration issued behind its barrier
 			ring_read_with_edges<kWaitSteady, S0 * SLOT, S0 * SLOT + RB>(ring_trip, P[0].u0[S0], P[0].v0[S0], edge);
 #pragma unroll
 			for (int n = 0; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
-			edge_publish<(K & 1) * kEdgeParityBytes<STEPS>>(edge_pub, P[0].u0[S0]);
+			edge_publish<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_pub, P[0].u0[S0]);
 		} else {
 			ring_read<kWaitSteady, S0 * SLOT, S0 * SLOT + RB>(ring_trip, P[0].u0[S0], P[0].v0[S0]);
 #pragma unroll
@@ -999,7 +1005,7 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 				    P[N].u0[S0] = nu;
 				    P[N].v0[S0] = nv;
 				    P[N].bq[S0] = b4[N - 1];
-				    if constexpr (COOP) edge_publish<(K & 1) * kEdgeParityBytes<STEPS> + 32 * N>(edge_pub, nu);
+				    if constexpr (COOP) edge_publish<(K & 1) * kEdgeParityBytes<STEPS, WAVES> + 32 * N>(edge_pub, nu);
 			    }
 			    constexpr int live = FED - 8 * N < 0 ? 0 : (FED - 8 * N > 8 ? 8 : FED - 8 * N);
 			    stages(P[N], p - kApron * N, kk, std::integral_constant<int, live>{}, 4 * N, b4[N], nu, nv, E[N], std::integral_constant<int, 4 * N>{});
@@ -1038,7 +1044,7 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		out_row_v += nx;
 		// (COOP) what the block's wavefronts published during this iteration is complete beyond the barrier; the reads of what the next
 		// iteration needs of it go out at once and land while that iteration waits for its row
-		if constexpr (COOP) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS>>(edge_con, edge);
+		if constexpr (COOP) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge);
 	};
 	int m = 0;
 	for_sequence(  // the pipeline fills (a chunk has at least one row: FILL iterations and more)
@@ -1077,10 +1083,12 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 // Wavefronts per SIMD the register allocator is held to: the two-step pipelines live at the 168-register line (three wavefronts).
 template <typename Real, int MODEL, int COLS, int STEPS, bool ABSORB>
 constexpr int kMinWaves = (STEPS == 2 && COLS * (int)sizeof(Real) == 8 && MODEL == CRD_MODEL_FHN && !ABSORB) ? 3 : (STEPS == 3 ? 2 : 1);
-template <typename Real, int MODEL, bool ABSORB, int EMBED, int COLS, bool NT = false, int STEPS = 1>
-__global__ void __launch_bounds__(kLanes *kMaxWavesPerBlock) __attribute__((amdgpu_waves_per_eu(kMinWaves<Real, MODEL, COLS, STEPS, ABSORB>))) crd_rk4_fused_step_kernel(Slab<Real> s, FusedArgs<Real> a)
+// WAVES: the wavefronts of a block -- kMaxWavesPerBlock everywhere but in the eight-wide three-step block strip (kWideWaves).
+template <typename Real, int MODEL, bool ABSORB, int EMBED, int COLS, bool NT = false, int STEPS = 1, int WAVES = kMaxWavesPerBlock>
+__global__ void __launch_bounds__(kLanes *WAVES) __attribute__((amdgpu_waves_per_eu(kMinWaves<Real, MODEL, COLS, STEPS, ABSORB>))) crd_rk4_fused_step_kernel(Slab<Real> s, FusedArgs<Real> a)
 {
 	static_assert(STEPS == 1 || ((STEPS == 2 || STEPS == 3) && EMBED == 0), "several steps per launch: the plain step only");
+	static_assert(WAVES == kMaxWavesPerBlock || (WAVES == kWideWaves && kCanWide<Real, MODEL, COLS, STEPS> && !ABSORB), "eight wavefronts per block: the three-step fp64 FHN block strip without the selects only");
 	// The work item is a property of the wavefront: keep it (and everything derived from it: rows, trip counts, the
 	// per-row table reads, the boundary-row tests) in scalar registers.
 	// Optional remap: blocks are dealt round-robin over the 8 XCDs; the remap gives each XCD one contiguous run of items.
@@ -1110,9 +1118,9 @@ __global__ void __launch_bounds__(kLanes *kMaxWavesPerBlock) __attribute__((amdg
 	const int chunk = __builtin_amdgcn_readfirstlane(cblk);
 	if (strip >= a.nstrips || chunk >= a.nchunks) return;  // (a barrier waits for the surviving wavefronts of the workgroup only)
 	// the row rings of a two-step launch's wavefronts (fused_item_two_steps)
-	__shared__ __attribute__((aligned(16))) char rings[STEPS >= 2 ? kRingBytes<Real, COLS, STEPS> : 16];
+	__shared__ __attribute__((aligned(16))) char rings[STEPS >= 2 ? kRingBytes<Real, COLS, STEPS, WAVES> : 16];
 	lds_char *const block_rings = (lds_char *)rings;
-	__shared__ __attribute__((aligned(16))) char edges[(STEPS >= 2 && kCoop<Real, MODEL, COLS, STEPS>) ? kEdgeBytes<STEPS> + kEdgeDumpBytes<STEPS> : 16];
+	__shared__ __attribute__((aligned(16))) char edges[(STEPS >= 2 && kCoop<Real, MODEL, COLS, STEPS>) ? kEdgeBytes<STEPS, WAVES> + kEdgeDumpBytes<STEPS, WAVES> : 16];
 	lds_char *const block_edges = (lds_char *)edges;
 	if constexpr (ABSORB) {
 		// Does any row this chunk's pipeline touches -- [j0 - APRON, j1 + APRON) -- map to global row 0 or ny - 1?  The two are
@@ -1131,7 +1139,7 @@ __global__ void __launch_bounds__(kLanes *kMaxWavesPerBlock) __attribute__((amdg
 			else fused_item<Real, MODEL, false, EMBED, COLS, NT>(s, a, strip, chunk);
 		}
 	} else if constexpr (STEPS >= 2) {
-		fused_item_multi_step<Real, MODEL, false, COLS, NT, STEPS>(s, a, strip, chunk, block_rings, sblk, block_edges);
+		fused_item_multi_step<Real, MODEL, false, COLS, NT, STEPS, WAVES>(s, a, strip, chunk, block_rings, sblk, block_edges);
 	} else {
 		fused_item<Real, MODEL, false, EMBED, COLS, NT>(s, a, strip, chunk);
 	}
@@ -1217,9 +1225,9 @@ int resident_wavefronts(int cols, int steps = 1)
 }
 
 template <typename Real, int MODEL>
-int fused_chunk_rows(int nstrips, int rows, int chunk_mode, int cols, int steps = 1)  // 0: 32 rows, 1: one round, 2: 64 rows (two steps per launch: twice that)
+int fused_chunk_rows(int nstrips, int rows, int chunk_mode, int cols, int steps = 1, int sw = kWavesPerBlock)  // 0: 32 rows, 1: one round, 2: 64 rows (two steps per launch: twice that), 3: as 1, blocks of `sw` = kWideWaves wavefronts
 {
-	bool one_round = chunk_mode == 1;
+	bool one_round = chunk_mode == 1 || chunk_mode == 3;
 	const int slots = resident_wavefronts<Real, MODEL>(cols, steps);
 	// Two steps per launch: 16 fill rows per chunk instead of 8, and a pipeline bound by issue, not by the memory system: 128-row
 	// chunks (8192^2 fp64: 48 rows 0.301 ms per step, 64 0.289, 96 0.278, 128 0.267, 192 0.276, 256 0.276; fp32 alike,
@@ -1243,12 +1251,15 @@ int fused_chunk_rows(int nstrips, int rows, int chunk_mode, int cols, int steps 
 		// ones have fewer fill rows per row; 8192^2 fp64: 128 rows = 3.6 rounds 0.2667 ms per step, 155 = 2.97 rounds 0.2617, 235 =
 		// 1.96 rounds 0.2618, but 161 = 2.86 rounds 0.2669 and 241 = 1.90 rounds 0.2697; 16384^2 fp32: 128 rows 0.4948, 274 rows 0.4830;
 		// a rank's share of 1024 rows: one round of 61 rows; profiles/r04/whole_rounds.txt).
-		const long strip_blocks = (nstrips + kWavesPerBlock - 1) / kWavesPerBlock, resident_blocks = slots / kWavesPerBlock;
+		const long strip_blocks = (nstrips + sw - 1) / sw, resident_blocks = slots / sw;  // (sw: kWavesPerBlock, or the eight-wide block strip's kWideWaves)
 		for (long k = 1; k <= 8; k++) {
 			const long chunks = k * resident_blocks / strip_blocks;
 			if (chunks < 1) continue;
 			const long need = (rows + chunks - 1) / chunks;
-			if (need <= (steps == 3 ? 432 : 288)) {
+			// (The eight-wide block strip, one block per CU: 576 rows.  8192^2 is 17 strip blocks x 15 chunks of 547 rows = 0.996 rounds of 256
+			// resident blocks, 0.1954 ms per step; two rounds of 274-row chunks measured 0.2012, the four-wide plan's time -- what the wider block
+			// saves in apron lanes the second round's fill rows and tail give back; profiles/r08/block_strip_eight_ab.txt.)
+			if (need <= (sw == kWideWaves ? 576 : steps == 3 ? 432 : 288)) {
 				if (need >= 16) chunk = (int)need;
 				break;
 			}
@@ -1277,7 +1288,7 @@ int fused_chunk_rows(int nstrips, int rows, int chunk_mode, int cols, int steps 
 // Fourth dimension (round 3, late): non-temporal stores of the new state (row_store).  They keep L2 for what items share; which
 // mapping is fastest changes with them (the plain mapping gains most), so they are timed in combination.
 struct PlanCandidate {
-	int one_round, remap, cols, nt;  // one_round: the chunk mode -- 0 = 32 rows, 1 = stretched to one round, 2 = 64 rows
+	int one_round, remap, cols, nt;  // one_round: the chunk mode -- 0 = 32 rows, 1 = stretched to one round, 2 = 64 rows, 3 = as 1 with eight wavefronts per block strip (kWideWaves)
 	int steps = 1;                   // RK4 steps per launch (2: fused_item_two_steps)
 };
 // (round 4: 64-row chunks also under mappings 1 / 2 and with two columns per lane -- where fp64 issue binds, Goldbeter, the recompute
@@ -1294,6 +1305,10 @@ constexpr PlanCandidate kPlanCandidates[] = {
     // (whole-rounds chunks win by 7 % -- 293 rows = two rounds of resident blocks on 8192^2 against 192 rows = three and a bit --, plain
     // stores by half a per cent on some boxes)
     {0, 0, 1, 1, 3}, {0, 1, 1, 1, 3}, {0, 2, 1, 1, 3}, {1, 0, 1, 1, 3}, {1, 1, 1, 1, 3}, {1, 0, 1, 0, 3}, {1, 1, 1, 0, 3},
+    // (round 8) ... and its eight-wide form, chunk mode 3: 488 valid lanes of 512, one block per CU, whole rounds of 256 resident blocks
+    // (8192^2: -2.9 / -3.3 % against the best four-wide plan in two runs; 4096^2, where 9 x 488 columns waste what 18 x 232 do: +2.4 / +3.0 %.  Plain stores: +0.5 %,
+    // no candidate.  profiles/r08/block_strip_eight_ab.txt)
+    {3, 0, 1, 1, 3}, {3, 1, 1, 1, 3}, {3, 2, 1, 1, 3},
     // ... and in fp32: two columns per lane, a strip per wavefront (kThreeStepCols)
     {0, 0, 2, 1, 3}, {0, 1, 2, 1, 3}, {0, 2, 2, 1, 3}, {1, 0, 2, 1, 3}, {1, 1, 2, 1, 3}, {2, 1, 2, 1, 3}};
 constexpr int kNumPlanCandidates = (int)(sizeof kPlanCandidates / sizeof kPlanCandidates[0]);
@@ -1349,6 +1364,7 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 		const int v = std::atoi(e);
 		if (v >= 1 && v <= kMaxWavesPerBlock) sw = v;
 	}
+	const int sw_plain = sw;
 	a.sw = sw;
 	a.err_partials = c.err_partials ? c.err_partials + c.err_offset : nullptr;
 	a.err_lo = d.wrap ? INT32_MIN : 0;
@@ -1363,7 +1379,7 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 	// (fp32: the three-step pipeline with the absorbing-row selects does not fit the registers -- 256 and scratch; the steppers step
 	// such triples as a pair and a single step, run_steps: triple_absorbs)
 	if (c.steps == 3 && sizeof(Real) == 4 && absorb12) return hipErrorInvalidValue;
-	const dim3 block(kLanes * sw);
+	auto block = [&]() { return dim3(kLanes * sw); };
 
 	int cols = cols_default, steps = 1;
 	bool nt = false;
@@ -1373,7 +1389,7 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 	auto layout = [&]() {
 		const int rows_a = R[1] - R[0], rows_b = R[3] - R[2];
 		const int nsb = (a.nstrips + sw - 1) / sw;
-		a.chunk = chunk_override > 0 ? std::min(chunk_override, rows_a + rows_b) : fused_chunk_rows<Real, MODEL>(a.nstrips, rows_a + rows_b, plan_mode, cols, steps);
+		a.chunk = chunk_override > 0 ? std::min(chunk_override, rows_a + rows_b) : fused_chunk_rows<Real, MODEL>(a.nstrips, rows_a + rows_b, plan_mode, cols, steps, sw);
 		const int n1 = (rows_a + a.chunk - 1) / a.chunk, n2 = (rows_b + a.chunk - 1) / a.chunk;
 		a.nchunks = n1 + n2;
 		a.first2 = n2 > 0 ? n1 : a.nchunks;
@@ -1397,6 +1413,16 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 			}
 		}
 	};
+	// strips of the launch, given cols, steps and the block's width `w`
+	auto set_width = [&](int w) {
+		sw = a.sw = w;
+		const int valid = cols * kLanes - 2 * steps * (c.embed ? kApron + 1 : kApron);  // (the embedded estimators' fifth stage costs one more apron column per side)
+		a.nstrips = (d.nx + valid - 1) / valid;
+		if ((steps == 2 && cols == 1 && kCoop<Real, MODEL, 1, 2>) || (steps == 3 && kCoop<Real, MODEL, 1, 3>)) {  // the block as the strip: one apron around its sw wavefronts
+			const int block_valid = sw * kLanes - 2 * steps * kApron;
+			a.nstrips = sw * ((d.nx + block_valid - 1) / block_valid);
+		}
+	};
 	auto configure = [&](int one_round, int remap, int want_cols, int want_nt = 0, int want_steps = 1) {
 		steps = (want_steps == 3 && kCanThreeSteps<Real, MODEL> && (kThreeStepCols<Real, MODEL> == 1 || cols2_ok)) ? 3 : (want_steps >= 2 && kCanTwoSteps) ? 2 : 1;
 		nt = want_nt != 0;
@@ -1404,12 +1430,10 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 		cols = (want_cols == 2 && cols2_ok) ? 2 : 1;
 		if (const char *e = tuning::knob("CRD_FUSED_COLS")) cols = (std::atoi(e) == 2 && cols2_ok) ? 2 : 1;
 		if (steps == 3) cols = kThreeStepCols<Real, MODEL>;  // (the three-step pipeline has ONE form per model and precision)
-		const int valid = cols * kLanes - 2 * steps * (c.embed ? kApron + 1 : kApron);  // (the embedded estimators' fifth stage costs one more apron column per side)
-		a.nstrips = (d.nx + valid - 1) / valid;
-		if ((steps == 2 && cols == 1 && kCoop<Real, MODEL, 1, 2>) || (steps == 3 && kCoop<Real, MODEL, 1, 3>)) {  // the block as the strip: one apron around its sw wavefronts
-			const int block_valid = sw * kLanes - 2 * steps * kApron;
-			a.nstrips = sw * ((d.nx + block_valid - 1) / block_valid);
-		}
+		// Chunk mode 3, the eight-wide block strip: where the launch is the three-step fp64 FHN kernel's (kCanWide); everywhere else mode 1.
+		const bool wide = one_round == 3 && kCanWide<Real, MODEL, 1, 3> && steps == 3 && cols == 1 && !c.embed && sw_plain == kWavesPerBlock;
+		if (one_round == 3 && !wide) one_round = 1;
+		set_width(wide ? kWideWaves : sw_plain);
 		plan_mode = one_round;
 		plan_remap = remap;
 		layout();
@@ -1420,8 +1444,8 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 			auto with = [&](auto absorb_c, auto embed_c, auto nt_c) {
 				auto kernel = crd_rk4_fused_step_kernel<Real, MODEL, decltype(absorb_c)::value && kCanAbsorb, decltype(embed_c)::value, 1, decltype(nt_c)::value>;
 				// (the sum deferred to the caller -- another stream, launch_sum_partials: the event is this kernel's own completion)
-				if (c.err_defer_sum && c.done_event) hipExtLaunchKernelGGL(kernel, dim3(a.nblocks), block, 0, st, nullptr, c.done_event, 0, s, a);
-				else kernel<<<a.nblocks, block, 0, st>>>(s, a);
+				if (c.err_defer_sum && c.done_event) hipExtLaunchKernelGGL(kernel, dim3(a.nblocks), block(), 0, st, nullptr, c.done_event, 0, s, a);
+				else kernel<<<a.nblocks, block(), 0, st>>>(s, a);
 			};
 			auto with_embed = [&](auto absorb_c, auto nt_c) {
 				if (c.embed == 2) with(absorb_c, std::integral_constant<int, 2>{}, nt_c);
@@ -1440,16 +1464,30 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 		} else {
 			// plain step: absorbing rows x columns per lane x store hint x steps per launch, all compile-time
 			bool last_launch = true, first_launch = true;  // (of this call: the ones a done_event / a start_event is bound to)
+			bool bad_width = false;
 			auto with = [&](auto absorb_c, auto cols_c, auto nt_c, auto steps_c) {
 				constexpr int kSteps = decltype(steps_c)::value;
-				auto kernel = crd_rk4_fused_step_kernel<Real, MODEL, decltype(absorb_c)::value && kCanAbsorb, 0, decltype(cols_c)::value, decltype(nt_c)::value,
-				                                        (kSteps == 3 ? kCanThreeSteps<Real, MODEL> && decltype(cols_c)::value == kThreeStepCols<Real, MODEL> &&
-				                                                           !(sizeof(Real) == 4 && decltype(absorb_c)::value)  // (never launched: see above)
-				                                                     : kCanTwoSteps) ? kSteps : 1>;
-				hipEvent_t e0 = first_launch ? c.start_event : nullptr, e1 = last_launch ? c.done_event : nullptr;
-				if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(a.nblocks), block, 0, st, e0, e1, 0, s, a);
-				else kernel<<<a.nblocks, block, 0, st>>>(s, a);
-				first_launch = false;
+				constexpr int kLaunched = (kSteps == 3 ? kCanThreeSteps<Real, MODEL> && decltype(cols_c)::value == kThreeStepCols<Real, MODEL> &&
+				                                             !(sizeof(Real) == 4 && decltype(absorb_c)::value)  // (never launched: see above)
+				                                       : kCanTwoSteps) ? kSteps : 1;
+				constexpr bool kAbsorb = decltype(absorb_c)::value && kCanAbsorb;
+				auto go = [&](auto kernel) {
+					hipEvent_t e0 = first_launch ? c.start_event : nullptr, e1 = last_launch ? c.done_event : nullptr;
+					if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(a.nblocks), block(), 0, st, e0, e1, 0, s, a);
+					else kernel<<<a.nblocks, block(), 0, st>>>(s, a);
+					first_launch = false;
+				};
+				if constexpr (kLaunched == 3 && kCanWide<Real, MODEL, decltype(cols_c)::value, 3> && !kAbsorb) {
+					if (sw == kWideWaves) {
+						go(crd_rk4_fused_step_kernel<Real, MODEL, false, 0, 1, decltype(nt_c)::value, 3, kWideWaves>);
+						return;
+					}
+				}
+				if (sw > kMaxWavesPerBlock) {  // (configure and the band cut below keep the eight-wide blocks to their own kernel)
+					bad_width = true;
+					return;
+				}
+				go(crd_rk4_fused_step_kernel<Real, MODEL, kAbsorb, 0, decltype(cols_c)::value, decltype(nt_c)::value, kLaunched>);
 			};
 			auto with_steps = [&](auto absorb_c, auto cols_c, auto nt_c) {
 				if (steps == 3) with(absorb_c, cols_c, nt_c, std::integral_constant<int, 3>{});
@@ -1500,8 +1538,12 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 						else without[n_without][0] = cursor, without[n_without++][1] = end;
 					}
 				}
+				// (the eight-wide block strip has no body with the selects: those launches go out four wide, the select-free ones eight wide)
+				const int sw_bulk = sw;
 				if (!fits || n_with == 0) {
+					if (sw_bulk != sw_plain) set_width(sw_plain), layout();
 					launch(true);
+					if (sw_bulk != sw_plain) set_width(sw_bulk), layout();
 				} else {
 					auto issue = [&](int (*piece)[2], int count, bool selects, int item_rows, bool final_pieces) {
 						for (int q = 0; q < count; q += 2) {
@@ -1511,6 +1553,7 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 							R[2] = q + 1 < count ? piece[q + 1][0] : 0;
 							R[3] = q + 1 < count ? piece[q + 1][1] : 0;
 							chunk_override = item_rows;
+							set_width(selects ? sw_plain : sw_bulk);
 							layout();
 							launch(selects);
 						}
@@ -1520,11 +1563,13 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 					last_launch = true;
 					for (int q = 0; q < 4; q++) R[q] = want[q];
 					chunk_override = 0;
+					set_width(sw_bulk);
 					layout();
 				}
 			} else {
 				launch(steps >= 2 ? absorb12 : absorb1);
 			}
+			if (bad_width) return hipErrorInvalidConfiguration;
 		}
 		return launch_status();
 	};
@@ -1583,6 +1628,7 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 			t_best[k] = 0.f;
 			configure(kPlanCandidates[k].one_round, kPlanCandidates[k].remap, kPlanCandidates[k].cols, kPlanCandidates[k].nt, kPlanCandidates[k].steps);
 			live[k] = k == 0 || !(kPlanCandidates[k].one_round && a.chunk == fused_chunk_rows<Real, MODEL>(a.nstrips, rows, 0, cols, steps));  // (same as a 32-row plan)
+			if (live[k] && kPlanCandidates[k].one_round != plan_mode) live[k] = false;  // (chunk mode 3 where the eight-wide kernel does not run: that is mode 1's candidate)
 			if (live[k] && kPlanCandidates[k].steps != ((kPlanCandidates[k].steps == 3 ? three_steps_ok : two_steps_ok) ? steps : 1)) live[k] = false;  // (several steps per launch: plain steps)
 			if (live[k] && steps == 2 && cols == 2 && sizeof(Real) == 8) live[k] = false;  // (256 VGPRs, one wavefront per SIMD: measured 0.347 against 0.312 ms)
 			if (live[k] && kPlanCandidates[k].remap != a.remap) live[k] = false;  // (the mapping fell back to dispatch order)
@@ -1690,6 +1736,7 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 		g.chunks = a.nchunks;
 		g.blocks = a.nblocks;
 		g.waves_per_block = sw;
+		g.chunk_mode = plan_mode;
 		g.fill_iterations = 2 * apron;
 		g.iterations_per_trip = c.embed ? CRD_EMBED_SLOTS : 4;
 		g.lanes = kLanes;

@@ -78,6 +78,7 @@ struct FusedPlan {
 struct FusedGeometry {
 	int real_bytes, model, absorb, embed, cols, nt, steps;  // template arguments of the kernel
 	int strips, chunk_rows, chunks, blocks, waves_per_block, fill_iterations, iterations_per_trip, lanes, lanes_valid, mapping;
+	int chunk_mode;        // the plan's chunk mode as the launch resolved it (3, the eight-wide block strip, only where its kernel runs)
 	long wave_iterations;  // pipeline iterations of all wavefronts of the launch: strips x (rows + chunks x fill)
 };
 // One step kernel of this build as the assembler printed it (crd_kernel_table.cpp, generated at build time by tools/kernel_regs.py):
@@ -85,8 +86,9 @@ struct FusedGeometry {
 struct KernelStats {
 	int real_bytes, model, absorb, embed, cols, nt, steps, vgprs, sgprs, lds_bytes, scratch_bytes, wavefronts_per_simd, loop_valu, loop_salu, loop_vmem, loop_lds, loop_total;
 	int exec_skipped_vmem;  // vector-memory regions a wavefront can skip on its execution mask (multi-step kernels: 0, or the build stops)
+	int waves;              // wavefronts per block the instantiation is bound to (4; 8: the eight-wide three-step block strip)
 };
-const KernelStats *step_kernel_stats(int real_bytes, int model, int absorb, int embed, int cols, int nt, int steps);  // nullptr: the build has no table
+const KernelStats *step_kernel_stats(int real_bytes, int model, int absorb, int embed, int cols, int nt, int steps, int waves = 4);  // nullptr: the build has no table
 const char *step_kernel_table_digest();  // 16 hex digits over the table's rows ("" without a table): the build the profile tables are stamped with
 
 struct FusedCall {
@@ -134,6 +136,7 @@ int fused_default_columns(int precision, int nx);  // columns per lane of launch
 int fused_plan_candidates();                       // the plans the tuner times (crd_launch_plan_candidate)
 bool fused_plan_candidate(int index, int *chunk_mode, int *mapping, int *cols, int *nt, int *steps);
 bool fused_two_steps_supported(const SlabDesc &d);
+bool fused_wide_supported(int precision, const SlabDesc &d, int want_steps);  // chunk mode 3 (eight wavefronts per block strip) runs its own kernel on this slab
 int fused_steps_supported(int precision, const SlabDesc &d, int want);  // steps per launch a plan that asks for `want` gets on this slab
 int fused_max_items(const SlabDesc &d);
 

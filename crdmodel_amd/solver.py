@@ -640,14 +640,20 @@ class PinnedArray:
             pass
 
 
-def launch_plan_candidates():
-    """The plans the launch-plan measurement chooses among, as (chunk_mode, xcd_mapping, columns_per_lane, nontemporal_stores)."""
+def launch_plan_candidates(eight_wide=False):
+    """The plans the launch-plan measurement chooses among, as (chunk_mode, xcd_mapping, columns_per_lane, nontemporal_stores, steps per launch).
+
+    By default the plans whose kernel is named by (precision, model, columns, store hint, steps) alone -- how the profile records and
+    the kernel table are keyed.  eight_wide=True: the chunk-mode-3 plans (eight wavefronts per block strip) alone, whose kernel is a
+    further instantiation under the same five (the table rows with "waves": 8): their records carry that kernel's digest
+    (tests/test_block_strip_eight_host.py checks them)."""
     out, k = [], 0
     while True:
         lp = capi.LaunchPlan()
         if lib().crd_launch_plan_candidate(k, C.byref(lp)) != 0:
             return out
-        out.append((lp.one_round, lp.xcd_mapping, lp.columns_per_lane, lp.nontemporal_stores, lp.steps_per_launch))
+        if (lp.one_round == 3) == bool(eight_wide):
+            out.append((lp.one_round, lp.xcd_mapping, lp.columns_per_lane, lp.nontemporal_stores, lp.steps_per_launch))
         k += 1
 
 

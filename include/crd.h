@@ -443,7 +443,8 @@ const char *crd_dominant_kernel_name(const crd_ctx *ctx);
 typedef struct crd_launch_plan {
 	int32_t autotune;     /* measuring enabled (2: verbose) */
 	int32_t tuned;        /* a measurement has been made (or a plan pinned) */
-	int32_t one_round;    /* chunk mode: 0 = 32-row chunks, 1 = stretched so that all workgroups are resident at once, 2 = 64-row chunks */
+	int32_t one_round;    /* chunk mode: 0 = 32-row chunks, 1 = stretched so that all workgroups are resident at once, 2 = 64-row chunks,
+	                       * 3 = as 1 with eight wavefronts per block strip (the three-step fp64 FHN kernel; reported as 1 where that kernel does not run) */
 	int32_t xcd_mapping;  /* 0 theta-first dispatch order, 1 one contiguous band of the slab per XCD, 2 the same with succession in phi */
 	int32_t rows;         /* height of the launch it was measured on */
 	int32_t columns_per_lane; /* 1: a wavefront steps a strip of 64 columns (56 valid); 2: 128 columns (120 valid), two per lane -- packed
@@ -489,7 +490,7 @@ int crd_get_launch_geometry(crd_ctx *ctx, crd_launch_geometry *out);
  * columns_per_lane, nontemporal_stores and steps_per_launch of *out are set, the rest zero.  (tools/plan_sweep.py profiles every one of them;
  * tests/test_profiles.py checks that profiles/pmc_traffic.json has an entry for each.) */
 int crd_launch_plan_candidate(int index, crd_launch_plan *out);
-/* Use THIS plan (chunk mode 0..2, mapping 0..2, columns per lane 1..2, non-temporal stores 0..1, steps per launch 1..3) for the fixed-step kernel instead of measuring one -- a plan
+/* Use THIS plan (chunk mode 0..2, or 3 together with three steps per launch; mapping 0..2, columns per lane 1..2, non-temporal stores 0..1, steps per launch 1..3) for the fixed-step kernel instead of measuring one -- a plan
  * read back from an earlier context of the same shape on the same device (the measurement costs ~0.45 s per context at 8192^2), or
  * a profiling run in which every launch of the kernel should be the plan a previous run chose (`bench.py --launch-plan`).  A pinned
  * plan applies to launches of EVERY size (a measured one only to launches of the height it was measured on).  Where a choice cannot

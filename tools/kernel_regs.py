@@ -230,11 +230,12 @@ def table_digest(rows):
     plan_stats.json) carry the digest of the build they were measured on."""
     import hashlib
 
-    canon = json.dumps(sorted(rows, key=lambda r: (r["precision"], r["model"], r["absorb"], r["embed"], r["cols"], r["nt"], r["steps"])), sort_keys=True)
+    canon = json.dumps(sorted(rows, key=lambda r: (r["precision"], r["model"], r["absorb"], r["embed"], r["cols"], r["nt"], r["steps"], r.get("waves", 4))), sort_keys=True)
     return hashlib.sha256(canon.encode()).hexdigest()[:16]
 
 
-STEP_KERNEL = re.compile(r"crd_rk4_fused_step_kernel<(double|float), (\d+), (true|false), (\d+), (\d+), (true|false), (\d+)>")
+# (the eighth argument: wavefronts per block -- 4 everywhere but in the eight-wide three-step block strip)
+STEP_KERNEL = re.compile(r"crd_rk4_fused_step_kernel<(double|float), (\d+), (true|false), (\d+), (\d+), (true|false), (\d+)(?:, (\d+))?>")
 
 
 def check_only(kernels):
@@ -285,11 +286,13 @@ def main():
     for k in kernels:
         m = STEP_KERNEL.search(k["name"])
         if m:
-            real, model, absorb, embed, cols, nt, steps = m.groups()
+            real, model, absorb, embed, cols, nt, steps, waves = m.groups()
             rows.append({"precision": "f64" if real == "double" else "f32", "model": int(model), "absorb": int(absorb == "true"), "embed": int(embed), "cols": int(cols),
                          "nt": int(nt == "true"), "steps": int(steps), "vgprs": k["vgprs"], "sgprs": k["sgprs"], "lds_bytes": k["lds"], "scratch_bytes": k["scratch"],
                          "wavefronts_per_simd": k["occupancy"], "loop": k["loop"], "exec_skipped_vmem": k["exec_skipped_vmem"],
                          "async_lds_read_hazards": k["async_lds_read_hazards"]})
+            if int(waves or 4) != 4:  # (a row of the usual width carries no such key: its text, and the digests over it, are what they were)
+                rows[-1]["waves"] = int(waves)
     # The vmcnt contract of the multi-step pipelines (exec_skipped_vmem above) and the edge reads' registers (async_lds_read_hazards): a build
     # that breaks either does not go on -- checked before anything is written, so that no table of a violating build is left for the next
     # `make` to link.
@@ -316,9 +319,9 @@ def main():
             f.write("// generated by tools/kernel_regs.py from the assembly of this build's step kernels -- do not edit\n")
             for r in rows:
                 lp = r["loop"]
-                f.write("{%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d},\n" % (
+                f.write("{%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d},\n" % (
                     8 if r["precision"] == "f64" else 4, r["model"], r["absorb"], r["embed"], r["cols"], r["nt"], r["steps"], r["vgprs"], r["sgprs"], r["lds_bytes"],
-                    r["scratch_bytes"], r["wavefronts_per_simd"], lp["valu"], lp["salu"], lp["vmem"], lp["lds"], lp["total"], r["exec_skipped_vmem"]))
+                    r["scratch_bytes"], r["wavefronts_per_simd"], lp["valu"], lp["salu"], lp["vmem"], lp["lds"], lp["total"], r["exec_skipped_vmem"], r.get("waves", 4)))
             # the digest of the rows above: what profiles/*.json entries are stamped with (crd_kernel_table_digest, bench.py)
             f.write("#define CRD_KERNEL_TABLE_DIGEST \"%s\"\n" % table_digest(rows))
     if a.json:
