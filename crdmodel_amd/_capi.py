@@ -220,6 +220,10 @@ _SIGNATURES = {
     "crd_ensemble_upload": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "crd_ensemble_download": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "crd_ensemble_step_rk4": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64]),
+    "crd_ensemble_step_rk4_own": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_int64)]),
+    "crd_ensemble_step_rk4_own_dt": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "crd_ensemble_step_rk4_own_timed": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "crd_ensemble_own_steps": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int64)]),
     "crd_ensemble_step_rk4_timed": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_double)]),
     "crd_ensemble_set_steps_per_launch": (C.c_int, [_vp, C.c_int]),
     "crd_ensemble_get_steps_per_launch": (C.c_int, [_vp]),

@@ -62,6 +62,15 @@ struct crd_ensemble {
 	EnsembleOp *ops_dev = nullptr, *ops_host = nullptr;  // kOpSets x n entries each; ops_host page-locked
 	static constexpr int kOpSets = 3;          // batched launches enqueued between two waits, each with an operand set of its own
 
+	// Own step sizes (crd_ensemble_step_rk4_own): allocated at the first such call, empty before.  The slot table on the device holds
+	// one version at a time -- 2 (n + 1) entries: the active slots and the prefix's last entry, once per parity of the round -- and is
+	// rewritten in stream order; the host keeps kOwnVersions page-locked copies, so that a version is not overwritten while its copy
+	// may still be under way (after that many the stream is waited for), and beside each a copy of the member table for the call's end.
+	static constexpr int kOwnVersions = 16;
+	EnsembleOwnSlot *own_dev = nullptr, *own_host = nullptr;
+	EnsembleMember *own_members_host = nullptr;
+	int own_versions = 0;                      // versions written since the stream was last waited for
+
 	// Observer (crd_ensemble_observe_*): empty unless one is open.
 	struct Observer {
 		bool open = false;
@@ -188,6 +197,29 @@ void member_extents(const crd_ensemble *e, std::vector<int> *nx, std::vector<int
 		nx->push_back((int)g.nx);
 		ny->push_back((int)g.ny);
 	}
+}
+
+// The first own-steps call's allocations: the slot table and its page-locked versions.
+int ensure_own(crd_ensemble *e)
+{
+	if (e->own_dev) return CRD_OK;
+	const size_t entries = 2 * ((size_t)e->n + 1);
+	void *slots = nullptr, *members = nullptr, *dev = nullptr;  // (into locals: a failure leaves the ensemble without any of them)
+	hipError_t r = hipHostMalloc(&slots, crd_ensemble::kOwnVersions * entries * sizeof(EnsembleOwnSlot), hipHostMallocPortable);
+	if (r == hipSuccess) r = hipHostMalloc(&members, crd_ensemble::kOwnVersions * (size_t)e->n * sizeof(EnsembleMember), hipHostMallocPortable);
+	if (r == hipSuccess) r = hipMalloc(&dev, entries * sizeof(EnsembleOwnSlot));
+	if (r != hipSuccess) {
+		if (slots) (void)hipHostFree(slots);
+		if (members) (void)hipHostFree(members);
+		(void)hipGetLastError();
+		return efail(e, r == hipErrorOutOfMemory ? CRD_ENOMEM : CRD_EHIP, std::string("own-steps tables: ") + hipGetErrorString(r));
+	}
+	e->allocs.push_back(dev);
+	e->own_host = static_cast<EnsembleOwnSlot *>(slots);
+	e->own_members_host = static_cast<EnsembleMember *>(members);
+	e->own_dev = static_cast<EnsembleOwnSlot *>(dev);
+	e->own_versions = 0;
+	return CRD_OK;
 }
 
 // crd_ensemble_create (mixed_entry false: members of one geometry, today's refusals and messages) and crd_ensemble_create_mixed
@@ -349,7 +381,7 @@ void crd_ensemble_destroy(crd_ensemble *e)
 	for (void *q : e->allocs) (void)hipFree(q);
 	if (e->table) (void)hipFree(e->table);
 	if (e->max_host) (void)hipHostFree(e->max_host);
-	for (void *q : {(void *)e->sums_host, (void *)e->att_host, (void *)e->ops_host})
+	for (void *q : {(void *)e->sums_host, (void *)e->att_host, (void *)e->ops_host, (void *)e->own_host, (void *)e->own_members_host})
 		if (q) (void)hipHostFree(q);
 	for (hipEvent_t ev : {e->ev0, e->ev1})
 		if (ev) (void)hipEventDestroy(ev);
@@ -570,6 +602,200 @@ int crd_ensemble_max_abs(crd_ensemble *e, double *per_member)
 	ENS_TRY(e, hipMemcpyAsync(e->max_host, e->max_dev, (size_t)e->n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	for (int k = 0; k < e->n; k++) per_member[k] = e->max_host[k];
+	return CRD_OK;
+}
+
+int crd_ensemble_own_steps(const crd_ensemble *e, double t0, double t1, double dt_safety, int64_t *nsteps)
+{
+	if (!e) return CRD_EINVAL;
+	crd_ensemble *const w = const_cast<crd_ensemble *>(e);  // (the message only)
+	if (!nsteps) return efail(w, CRD_EINVAL, "crd_ensemble_own_steps: null nsteps");
+	if (!std::isfinite(t0) || !std::isfinite(t1)) return efail(w, CRD_EINVAL, "crd_ensemble_own_steps: t0 and t1 must be finite");
+	if (!(t1 > t0)) return efail(w, CRD_EINVAL, "crd_ensemble_own_steps: t1 must lie after t0");
+	if (!(dt_safety > 0.0) || !std::isfinite(dt_safety)) return efail(w, CRD_EINVAL, "crd_ensemble_own_steps: dt_safety must be positive and finite");
+	for (int k = 0; k < e->n; k++) {
+		const double n = std::ceil((t1 - t0) / (dt_safety * crd_stable_dt(&e->p[(size_t)k])) - 1e-12);  // crd_run's rule for a lone run
+		if (!(n < 0x1p62)) return efail(w, CRD_EINVAL, "crd_ensemble_own_steps: member " + std::to_string(k) + " would take too many steps");
+		nsteps[k] = n >= 1.0 ? (int64_t)n : 1;
+	}
+	return CRD_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// crd_ensemble_step_rk4_own (dt == nullptr: member k's step size formed here, (t1 - t0) / nsteps[k]) and crd_ensemble_step_rk4_own_dt
+// (given).  Everything is refused before anything is launched.
+int step_own(crd_ensemble *e, double t0, double t1, const double *dt, const int64_t *nsteps, const char *where)
+{
+	if (!e) return CRD_EINVAL;
+	const std::string w = std::string(where) + ": ";
+	if (!nsteps) return efail(e, CRD_EINVAL, w + "null nsteps");
+	if (!std::isfinite(t0) || !std::isfinite(t1)) return efail(e, CRD_EINVAL, w + "t0 and t1 must be finite");
+	if (!(t1 > t0)) return efail(e, CRD_EINVAL, w + "t1 must lie after t0");
+	const int B = e->n;
+	int64_t rounds = 0;
+	for (int k = 0; k < B; k++) {
+		if (nsteps[k] < 1)
+			return efail(e, CRD_EINVAL, w + "member " + std::to_string(k) + " has nsteps = " + std::to_string(nsteps[k]) + " (every member takes at least one step)");
+		if (dt && !(dt[k] > 0.0 && std::isfinite(dt[k]))) return efail(e, CRD_EINVAL, w + "member " + std::to_string(k) + " has a step size that is not positive and finite");
+		rounds = std::max(rounds, nsteps[k]);
+	}
+	crd_ensemble::Observer &ob = e->obs;
+	if (ob.open && ob.count >= ob.capacity) return efail(e, CRD_EINVAL, "the observer has no room for this call's sample");  // refused whole
+	TraceRange range(where);
+	ENS_TRY(e, hipSetDevice(e->device));
+	if (int rc = ensure_own(e)) return rc;
+	for (auto &a : e->adapt) a.dense.pending = a.ark.live = false;  // stepping on from the states handed back (run_steps)
+
+	// What the rounds share: the plan made for all B members when the ensemble was created (no re-planning as members finish).
+	EnsembleStep st{};
+	st.ka4 = std::pow(kGbKa, 4.0);  // pow(KA, p), src/GoldbeterModel_torus.cpp:695
+	st.nx = e->nx;
+	st.ny = e->ny;
+	st.nstrips = e->plan.nstrips;
+	st.sw = e->plan.sw;
+	st.nsb = e->plan.nsb;
+	st.chunk = e->plan.chunk;
+	st.nchunks = e->plan.nchunks;
+	st.member_blocks = st.nsb * st.nchunks;
+	// Per member, once: its step size and the constants formed from it as launch_fused_t forms them.
+	struct Own {
+		double dt, h[4];
+		float hf[4];
+		int blocks;
+	};
+	std::vector<Own> own((size_t)B);
+	for (int k = 0; k < B; k++) {
+		Own &m = own[(size_t)k];
+		m.dt = dt ? dt[k] : (t1 - t0) / (double)nsteps[k];
+		m.h[0] = m.dt;
+		m.h[1] = 0.5 * m.dt;
+		m.h[2] = m.dt / 3.0;
+		m.h[3] = m.dt / 6.0;
+		for (int q = 0; q < 4; q++) m.hf[q] = (float)m.h[q];
+		m.blocks = e->mixed ? e->shapes[(size_t)k].nsb * e->shapes[(size_t)k].nchunks : st.member_blocks;
+	}
+	const double cs[4] = {0.0, 0.5, 0.5, 1.0};
+	const bool can_absorb = e->model != dev::kModelDiffusionOnly;
+	const size_t version_entries = 2 * ((size_t)B + 1);
+	// Round s steps every member with nsteps[k] > s, in member order.  The slot table is rewritten only when that set, or a member's
+	// absorbing decision at one of its stages, differs from the round before: at most B + 1 + 3 B times a call.
+	std::vector<int> active, flags, now_active, now_flags;
+	bool absorb = false;
+	int version = -1;  // the page-locked copy the device table was last written from
+	int64_t launched = 0;  // rounds launched
+	auto run_rounds = [&]() -> int {
+	for (int64_t s = 0; s < rounds; s++) {
+		now_active.clear();
+		now_flags.clear();
+		bool now_absorb = false;
+		for (int k = 0; k < B; k++) {
+			if (nsteps[k] <= s) continue;
+			now_active.push_back(k);
+			const double t = t0 + (double)s * own[(size_t)k].dt;  // as run_steps forms it
+			for (int q = 0; q < 4; q++) {
+				const int f = (can_absorb && t + cs[q] * own[(size_t)k].dt < e->p[(size_t)k].t_boundary) ? 1 : 0;  // as make_fused_call forms it; strict <, absorbing() (crd_ctx.h)
+				now_flags.push_back(f);
+				now_absorb = now_absorb || f;
+			}
+		}
+		const int count = (int)now_active.size();
+		if (s == 0 || now_active != active || now_flags != flags) {
+			if (e->own_versions == crd_ensemble::kOwnVersions) {  // every page-locked copy may still be waiting to be read
+				ENS_TRY(e, hipStreamSynchronize(e->stream));
+				e->own_versions = 0;
+			}
+			version = e->own_versions++;
+			EnsembleOwnSlot *const host = e->own_host + (size_t)version * version_entries;
+			for (int parity = 0; parity < 2; parity++) {
+				EnsembleOwnSlot *const slots = host + (size_t)parity * ((size_t)count + 1);
+				int first = 0;
+				for (int i = 0; i < count; i++) {
+					const int k = now_active[(size_t)i];
+					const EnsembleMember &m = e->members[(size_t)k];
+					EnsembleOwnSlot &sl = slots[i];
+					sl = EnsembleOwnSlot{};
+					sl.in = m.u[e->cur ^ parity];  // every active member has taken s steps: one parity for the round
+					sl.out = m.u[e->cur ^ parity ^ 1];
+					for (int q = 0; q < 4; q++) {
+						sl.h[q] = own[(size_t)k].h[q];
+						sl.hf[q] = own[(size_t)k].hf[q];
+						sl.absorb[q] = now_flags[(size_t)(4 * i + q)];
+					}
+					sl.member = k;
+					sl.first_block = first;
+					first += own[(size_t)k].blocks;
+				}
+				slots[count] = EnsembleOwnSlot{};
+				slots[count].first_block = first;
+			}
+			ENS_TRY(e, hipMemcpyAsync(e->own_dev, host, 2 * ((size_t)count + 1) * sizeof(EnsembleOwnSlot), hipMemcpyHostToDevice, e->stream));
+			st.nblocks = host[count].first_block;
+			active.swap(now_active);
+			flags.swap(now_flags);
+			absorb = now_absorb;
+		}
+		ENS_TRY(e, launch_ensemble_own_step(e->precision, e->model, e->plan.cols, absorb, e->table, e->mixed ? e->shapes_dev : nullptr,
+		                                    e->own_dev + (size_t)(s & 1) * ((size_t)count + 1), count, st, e->stream));
+		launched = s + 1;
+	}
+	return CRD_OK;
+	};
+	const int rounds_rc = run_rounds();
+	// A member that took an odd number of steps ends in its other buffer: re-point its descriptor, so that buffer e->cur is every
+	// member's current state (nothing is copied; the error-controlled path does the same).  Where a round failed to launch, for the
+	// steps each member did take: the descriptors still name every member's latest state, though the members are at different times.
+	bool repoint = false;
+	for (int k = 0; k < B; k++)
+		if (std::min(nsteps[k], launched) & 1) {
+			EnsembleMember &m = e->members[(size_t)k];
+			std::swap(m.u[0], m.u[1]);
+			std::swap(m.v[0], m.v[1]);
+			repoint = true;
+		}
+	hipError_t table_r = hipSuccess;
+	if (repoint) {  // (version >= 0: a round was launched)
+		EnsembleMember *const host = e->own_members_host + (size_t)version * (size_t)B;  // (beside the call's last slot version: not rewritten before the stream is waited for)
+		std::copy(e->members.begin(), e->members.end(), host);
+		table_r = hipMemcpyAsync(e->table, host, (size_t)B * sizeof(EnsembleMember), hipMemcpyHostToDevice, e->stream);
+	}
+	if (rounds_rc != CRD_OK) {
+		const std::string cause = e->err;
+		return efail(e, rounds_rc, w + cause + "; " + std::to_string(launched) + " of " + std::to_string(rounds) + " rounds were launched: member k has taken min(nsteps[k], " +
+		                               std::to_string(launched) + ") steps, the members no longer share a time -- upload every member before stepping on" +
+		                               (table_r != hipSuccess ? std::string("; the member table could not be rewritten (") + hipGetErrorString(table_r) + "): destroy the ensemble" : std::string()));
+	}
+	ENS_TRY(e, table_r);
+	if (ob.open)
+		if (int rc = observer_sample(e, t1)) return rc;  // one sample per call, at t1 (crd_ensemble_integrate_adaptive's rule); the stride's count does not move
+	return CRD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crd_ensemble_step_rk4_own(crd_ensemble *e, double t0, double t1, const int64_t *nsteps) { return step_own(e, t0, t1, nullptr, nsteps, "crd_ensemble_step_rk4_own"); }
+
+int crd_ensemble_step_rk4_own_dt(crd_ensemble *e, double t0, double t1, const double *dt, const int64_t *nsteps)
+{
+	if (e && !dt) return efail(e, CRD_EINVAL, "crd_ensemble_step_rk4_own_dt: null dt");
+	return step_own(e, t0, t1, dt, nsteps, "crd_ensemble_step_rk4_own_dt");
+}
+
+int crd_ensemble_step_rk4_own_timed(crd_ensemble *e, double t0, double t1, const int64_t *nsteps, double *ms_total)
+{
+	if (!e) return CRD_EINVAL;
+	ENS_TRY(e, hipSetDevice(e->device));
+	ENS_TRY(e, hipEventRecord(e->ev0, e->stream));
+	if (int rc = crd_ensemble_step_rk4_own(e, t0, t1, nsteps)) return rc;
+	ENS_TRY(e, hipEventRecord(e->ev1, e->stream));
+	ENS_TRY(e, hipEventSynchronize(e->ev1));
+	float ms = 0.f;
+	ENS_TRY(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
+	if (ms_total) *ms_total = ms;
 	return CRD_OK;
 }
 

@@ -109,6 +109,30 @@ hipError_t launch_ensemble_pair_mixed(int precision, int model, int cols, bool a
                                       const EnsemblePair &e, hipStream_t s);
 
 
+// ---- every member at its own step size (crd_ensemble_own.hip; crd_ensemble.cpp: crd_ensemble_step_rk4_own) ----
+
+// One active member's step of a round: an entry of a table in device memory, written by the host whenever the set of active members
+// or one of their absorbing decisions changes, and read through the constant address space.  What crd_ensemble_step_kernel takes from
+// the launch's arguments for all members alike -- buffers, step size, absorbing stages -- is here per slot.  A launch over `count`
+// slots reads count + 1 entries: first_block is the prefix of the active members' block counts (members of different shape only), the
+// last entry's the launch's block count (its other fields are zero).
+struct EnsembleOwnSlot {
+	const void *in;         // the member's input: a state buffer (u plane, then v plane), row 0 first, no ghost rows
+	void *out;              // ... and the buffer its step writes
+	double h[4];            // dt_k, dt_k/2, dt_k/3, dt_k/6 formed in double as launch_fused_t forms them (fp64 kernels)
+	float hf[4];            // ... rounded to fp32 on the host (fp32 kernels)
+	int member;             // index into the member table (and the shape table)
+	int absorb[4];          // t_stage < tBoundary at the member's own t + (0, 1/2, 1/2, 1) dt_k
+	int first_block;
+	int reserved[2];
+};
+// One RK4 step of each of slots[0 .. count): e gives the plan (members of one shape, shapes == nullptr: all of EnsembleStep's
+// geometry, nblocks = member_blocks * count; of different shape: sw, chunk and nblocks = slots[count].first_block, strips and chunks
+// from shapes[member]) and ka4; its step constants, stage times and src are not read.  absorb: some slot has a flag set.
+hipError_t launch_ensemble_own_step(int precision, int model, int cols, bool absorb, const EnsembleMember *table, const EnsembleShape *shapes, const EnsembleOwnSlot *slots,
+                                    int count, const EnsembleStep &e, hipStream_t s);
+
+
 // ---- error-controlled integration (crd_ensemble_adaptive.hip; crd_ensemble.cpp: crd_ensemble_integrate_adaptive) ----
 
 // One member's attempt of a round: an entry of a table in device memory, written by the host before each round's launch and read

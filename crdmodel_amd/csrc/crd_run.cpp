@@ -42,6 +42,7 @@ struct Options {
 	// --ensemble KEY=v1,v2,...: members that differ in one or more parameters, zipped over the lists (run_ensemble)
 	std::vector<std::pair<std::string, std::vector<double>>> ensemble;
 	int ensemble_steps = 0;  // --ensemble-steps 1|2: RK4 steps per launch of the ensemble (crd_ensemble_set_steps_per_launch); 0: not given
+	bool ensemble_own_dt = false;  // --ensemble-own-dt: every member at its own dtSafety x stable dt (crd_ensemble_step_rk4_own)
 	// --observe STRIDE [--probe i,j]... [--observe-maps THRESHOLD]: the ensemble's observer (crd_ensemble_observe_*)
 	bool observe = false, observe_maps = false;
 	long long observe_stride = 0;
@@ -62,12 +63,14 @@ struct Options {
 		          << " --model fhn|goldbeter --surface torus|flat [--gpus G] [--devices D] [--dt DT] [--stepper auto|staged|fused]\n"
 		             "       [--precision 64|32] [--adaptive|--adaptive-rk43|--fixed] [--binary|--binary-only] [--ref-steady-state] [--decomp D0xD1|mpi [--block-contexts]]\n"
 		             "       [--outdir DIR] [--quiet] [--ensemble beta|betaMin|betaMax|diffusion|tBoundary|surfaceLength|surfaceWidth|xMesh|surface=V1,V2,... (repeatable)]\n"
-		             "       [--ensemble-steps 1|2]\n"
+		             "       [--ensemble-steps 1|2] [--ensemble-own-dt]\n"
 		             "       [--observe STRIDE [--probe I,J (repeatable)] [--observe-maps THRESHOLD]\n"
 		             "                         [--section row:J|column:I|theta-mean|phi-mean (repeatable)] [--observe-cycles THRESHOLD]]\n"
 		             "       <Config file path>\n"
 		             "  --ensemble: fixed-step RK4, or error-controlled (each member its own ARKode-style steps) when the ini asks for [Solver] adaptive = 1\n"
 		             "  --ensemble-steps: fixed steps one launch takes (2: pairs, the same bits as single steps; members of at least 9 rows; not with adaptive = 1)\n"
+		             "  --ensemble-own-dt: every member steps at its own dtSafety x stable dt instead of the smallest member's (member files as a lone run of\n"
+		             "             that member's ini writes them; one observer sample per output; not with adaptive = 1, a pinned [Solver] dt / --dt or --ensemble-steps 2)\n"
 		             "  --observe: with --ensemble, member_<k>/observables.txt -- time, min / max / sum / sum of squares of both fields and the probes' values\n"
 		             "             after every STRIDE-th step (error-controlled: at every output), recorded on the GPU; --observe-maps: also\n"
 		             "             amplitude_map.npy and activation_time.npy (first sample with var0 >= THRESHOLD); --section: also\n"
@@ -153,6 +156,7 @@ void check_ensemble_options(const Options &o)
 {
 	if (o.ensemble.empty()) {
 		if (o.ensemble_steps) usage_error("--ensemble-steps sets an ensemble's steps per launch: it needs --ensemble");
+		if (o.ensemble_own_dt) usage_error("--ensemble-own-dt steps an ensemble's members at their own step sizes: it needs --ensemble");
 		if (o.observe) usage_error("--observe records an ensemble's members: it needs --ensemble");
 		if (!o.probes.empty()) usage_error("--probe belongs to --observe, which needs --ensemble");
 		if (o.observe_maps) usage_error("--observe-maps belongs to --observe, which needs --ensemble");
@@ -168,6 +172,8 @@ void check_ensemble_options(const Options &o)
 	if (o.observe && o.observe_stride < 1) usage_error("--observe takes a stride of at least 1 (got " + std::to_string(o.observe_stride) + ")");
 	if ((int)o.probes.size() > CRD_OBSERVE_MAX_PROBES) usage_error("--probe: at most " + std::to_string(CRD_OBSERVE_MAX_PROBES) + " probes");
 	if (o.adaptive == 1 || o.adaptive == 2) usage_error("--ensemble steps fixed-step RK4 only: not with --adaptive / --adaptive-rk43");
+	if (o.ensemble_own_dt && o.ensemble_steps == 2) usage_error("--ensemble-own-dt takes single steps (pairs of own steps are not built): not with --ensemble-steps 2");
+	if (o.ensemble_own_dt && o.dt > 0) usage_error("--ensemble-own-dt gives every member its own step size: not with --dt, which pins one for all");
 	if (o.gpus > 1) usage_error("--ensemble runs on one GPU: not with --gpus " + std::to_string(o.gpus));
 	if (o.d0 > 0 || o.decomp_mpi) usage_error("--ensemble members are single slabs: not with --decomp");
 	if (o.block_contexts) usage_error("--ensemble members are single slabs: not with --block-contexts");
@@ -368,6 +374,9 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 	const bool adaptive = cfg.adaptive == 1;
 	if (adaptive && o.ensemble_steps)
 		usage_error("--ensemble-steps sets the steps of a fixed-step launch: the ini asks for [Solver] adaptive = 1, which takes attempts, not steps (pass --fixed)");
+	const bool own_dt = o.ensemble_own_dt;
+	if (own_dt && adaptive) usage_error("--ensemble-own-dt sets the steps of the fixed-step path: the ini asks for [Solver] adaptive = 1, where every member takes its own steps already (pass --fixed)");
+	if (own_dt && cfg.dt > 0) usage_error("--ensemble-own-dt gives every member its own step size: the ini pins [Solver] dt = " + std::to_string(cfg.dt) + " for all (set dt = 0)");
 	if (cfg.n_gpus > 1) usage_error("--ensemble runs on one GPU: the ini asks for [Solver] gpus = " + std::to_string(cfg.n_gpus) + " (pass --gpus 1)");
 	const int B = (int)o.ensemble[0].second.size();
 	std::vector<crd_run_config> mc((size_t)B, cfg);
@@ -428,6 +437,18 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		crd_ensemble_destroy(ens);
 		return 1;
 	}
+	// --ensemble-own-dt: member k takes own_n[k] steps of dTout / own_n[k] per output, a lone run's count and step size for its ini.
+	// The step sizes are handed over as formed here (crd_ensemble_step_rk4_own_dt): (t + dTout) - t need not be dTout.
+	std::vector<int64_t> own_n((size_t)B, 0);
+	std::vector<double> own_step((size_t)B, 0.0);
+	if (own_dt) {
+		if ((rc = crd_ensemble_own_steps(ens, 0.0, dTout, cfg.dt_safety, own_n.data())) != CRD_OK) {
+			std::cerr << "\nCRD_ERROR: --ensemble-own-dt: " << crd_ensemble_last_error(ens) << "\n\n";
+			crd_ensemble_destroy(ens);
+			return 1;
+		}
+		for (int k = 0; k < B; k++) own_step[(size_t)k] = dTout / (double)own_n[(size_t)k];
+	}
 	crd_grid g;
 	crd_ensemble_info(ens, nullptr, &g);
 	if (!o.quiet) {
@@ -443,7 +464,10 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		if (adaptive)
 			std::cout << "   integrator = ARKode-style ERK on GPU (Zonneveld 5(3)4, PID controller), each member its own steps\n   rtol = " << cfg.rtol
 			          << "\n   atol = " << cfg.atol << "\n";
-		else
+		else if (own_dt) {
+			std::cout << "   integrator = classical RK4 on GPU, every member at its own dtSafety x stable dt (single steps, one launch per round)\n";
+			for (int k = 0; k < B; k++) std::cout << "   member " << k << ": dt = " << own_step[(size_t)k] << " (" << own_n[(size_t)k] << " steps per output)\n";
+		} else
 			std::cout << "   integrator = classical RK4 on GPU, dt = " << dt << " (" << steps_per_output << " steps per output; "
 			          << (dt_member < 0 ? std::string("from [Solver] dt / --dt") : "the smallest member's dtSafety x stable dt: member " + std::to_string(dt_member)) << ")\n"
 			          << (crd_ensemble_get_steps_per_launch(ens) == 2 ? "   two steps per launch\n" : "");
@@ -490,7 +514,7 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		oo.threshold = o.observe_threshold;
 		// fixed steps: every stride-th step of the run -- floor(total steps / stride), the count the library itself reaches, since its
 		// step count carries over the calls; error-controlled: one sample per output
-		const int64_t capacity = adaptive ? Nt : std::max<int64_t>(1, steps_per_output * Nt / oo.stride);
+		const int64_t capacity = (adaptive || own_dt) ? Nt : std::max<int64_t>(1, steps_per_output * Nt / oo.stride);
 		crd_observe_extras ex{};
 		ex.n_sections = (int32_t)o.sections.size();
 		for (size_t q = 0; q < o.sections.size(); q++) {
@@ -538,6 +562,9 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 			}
 			for (int k = 0; k < B && rc == CRD_OK; k++)
 				if (!failed_at[(size_t)k] && !blown_at[(size_t)k]) accepted[(size_t)k] += as[(size_t)k].accepted, rejected[(size_t)k] += as[(size_t)k].rejected;
+		} else if (own_dt) {
+			// (the time given is the observer sample's alone: the output time as the error-controlled branch forms it)
+			rc = crd_ensemble_step_rk4_own_dt(ens, t, (iout + 1 == Nt) ? cfg.t_final : (iout + 1) * dTout, own_step.data(), own_n.data());
 		} else {
 			rc = crd_ensemble_step_rk4(ens, t, dt, steps_per_output);
 		}
@@ -585,6 +612,15 @@ int run_ensemble(const Options &o, crd_run_config cfg)
 		long long attempts = 0;
 		for (int k = 0; k < B; k++) attempts += accepted[(size_t)k] + rejected[(size_t)k];
 		std::printf("   rate: %d members, %lld attempts in %.6f s of stepping = %.1f attempts/s\n", B, attempts, stepping_s, (double)attempts / stepping_s);
+		std::cout << "   ----------------------\n";
+	} else if (!o.quiet && own_dt && stepping_s > 0.0) {
+		double point_steps = 0.0;  // sum over the members of points x steps per output
+		long long most = 0;
+		for (int k = 0; k < B; k++) {
+			point_steps += (double)mg[(size_t)k].nx * (double)mg[(size_t)k].ny * (double)own_n[(size_t)k];
+			most = std::max(most, (long long)own_n[(size_t)k]);
+		}
+		std::printf("\n   rate: %d members at their own step sizes, %lld rounds in %.6f s of stepping = %.4g grid-point-steps/s\n", B, most * Nt, stepping_s, point_steps * Nt / stepping_s);
 		std::cout << "   ----------------------\n";
 	} else if (!o.quiet && stepping_s > 0.0) {
 		double points = 0.0;  // (every member's own grid: they may differ in shape)
@@ -659,6 +695,7 @@ int main(int argc, char *argv[])
 			else if (s == "--ref-steady-state") o.ref_steady_state = true;
 			else if (s == "--block-contexts") o.block_contexts = true;
 			else if (s == "--ensemble") parse_ensemble(next(), &o);
+			else if (s == "--ensemble-own-dt") o.ensemble_own_dt = true;
 			else if (s == "--ensemble-steps") {
 				const std::string v = next();
 				o.ensemble_steps = v == "1" ? 1 : v == "2" ? 2 : 0;

@@ -482,6 +482,39 @@ class Ensemble:
         self._check(lib().crd_ensemble_step_rk4_timed(self._h, t0, dt, nsteps, C.byref(ms)), "crd_ensemble_step_rk4_timed")
         return ms.value
 
+    def own_steps(self, t0, t1, dt_safety=0.8):
+        """The steps each member takes from t0 to t1 at its own bound (crd_ensemble_own_steps): per member
+        ceil((t1 - t0) / (dt_safety * stable_dt(params)) - 1e-12), at least 1 -- a lone crd_run's rule per output interval."""
+        n = (C.c_int64 * self.n_members)()
+        self._check(lib().crd_ensemble_own_steps(self._h, t0, t1, dt_safety, n), "crd_ensemble_own_steps")
+        return list(n)
+
+    def step_rk4_own(self, t0, t1, nsteps=None, dt_safety=0.8, sync=True, dt=None):
+        """Every member from t0 to t1 at its own step size (crd_ensemble_step_rk4_own): member k takes nsteps[k] RK4 steps of
+        (t1 - t0) / nsteps[k], bit-identical to a Slab of its params taking them alone; one launch per round for the members that still
+        have steps left.  nsteps=None: own_steps(t0, t1, dt_safety).  With an observer open, one sample at t1.  dt: the members' step
+        sizes given instead of formed (crd_ensemble_step_rk4_own_dt; t1 is then the sample's time only).  Returns the counts used."""
+        counts = self.own_steps(t0, t1, dt_safety) if nsteps is None else [int(n) for n in nsteps]
+        if len(counts) != self.n_members:
+            raise ValueError("nsteps needs one count per member (%d), got %d" % (self.n_members, len(counts)))
+        arr = (C.c_int64 * self.n_members)(*counts)
+        if dt is None:
+            self._check(lib().crd_ensemble_step_rk4_own(self._h, t0, t1, arr), "crd_ensemble_step_rk4_own")
+        else:
+            if len(dt) != self.n_members:
+                raise ValueError("dt needs one step size per member (%d), got %d" % (self.n_members, len(dt)))
+            self._check(lib().crd_ensemble_step_rk4_own_dt(self._h, t0, t1, (C.c_double * self.n_members)(*[float(h) for h in dt]), arr), "crd_ensemble_step_rk4_own_dt")
+        if sync:
+            self.synchronize()
+        return counts
+
+    def step_rk4_own_timed(self, t0, t1, nsteps):
+        """step_rk4_own bracketed by events: device time of the call in ms (blocks until done)."""
+        arr = (C.c_int64 * self.n_members)(*[int(n) for n in nsteps])
+        ms = C.c_double()
+        self._check(lib().crd_ensemble_step_rk4_own_timed(self._h, t0, t1, arr, C.byref(ms)), "crd_ensemble_step_rk4_own_timed")
+        return ms.value
+
     def synchronize(self):
         self._check(lib().crd_ensemble_synchronize(self._h), "crd_ensemble_synchronize")
 

@@ -572,6 +572,37 @@ int crd_ensemble_synchronize(crd_ensemble *e);
 #define CRD_ENSEMBLE_PAIR_MIN_ROWS 9
 int crd_ensemble_set_steps_per_launch(crd_ensemble *e, int steps);
 int crd_ensemble_get_steps_per_launch(const crd_ensemble *e); /* 1 or 2; CRD_EINVAL (negative) for NULL */
+/* Every member at its OWN step size to a common time: member k goes from t0 to t1 in nsteps[k] classical RK4 steps of
+ * dt_k = (t1 - t0) / nsteps[k] -- what crd_step_rk4(ctx_k, t0, dt_k, nsteps[k]) does to a lone one-launch context of member k's
+ * parameters, bit for bit, stage q of its step s at (t0 + s dt_k) + c_q dt_k and its absorbing rows on while that time is < its own
+ * tBoundary.  Rounds: round s is ONE launch for all members with nsteps[k] > s, so the launches shrink as members finish (the set
+ * need not stay a prefix of the member list); which rounds a member steps in moves no bit.  A scan over diffusion, or of curved
+ * against flat surfaces, then costs the sum of the members' own work instead of every member stepping at the smallest member's bound.
+ * Serves ensembles of crd_ensemble_create and of crd_ensemble_create_mixed (members of different shape included).  Asynchronous on
+ * the ensemble's stream.  Afterwards every call above and below finds each member's state where it expects it (a member that took an
+ * odd number of steps has its two buffers re-labelled; nothing is copied); as crd_ensemble_step_rk4, the call ends every member's
+ * error-controlled carry-over.
+ *   Steps per launch: the call takes single steps whatever crd_ensemble_set_steps_per_launch says; the setting keeps governing
+ *   crd_ensemble_step_rk4.
+ *   Observer: with one open the call records ONE sample at its end, at time t1, of every member (crd_ensemble_integrate_adaptive's
+ *   rule); the stride's count of fixed steps does not move.  A call for which there is no room is refused whole.
+ * CRD_EINVAL, crd_ensemble_last_error naming the cause (and the member where there is one), nothing launched and the ensemble as it
+ * was: a NULL argument, a non-finite t0 or t1, t1 <= t0, any nsteps[k] < 1.  A HIP failure while the rounds are being launched
+ * (CRD_EHIP) leaves the members at different times: each has taken the steps of the rounds launched, its descriptor names that
+ * state, and crd_ensemble_last_error says how many rounds those were; upload every member before stepping on. */
+int crd_ensemble_step_rk4_own(crd_ensemble *e, double t0, double t1, const int64_t *nsteps);
+/* ... with member k's step size GIVEN, dt[k], instead of formed from t1: what crd_step_rk4(ctx_k, t0, dt[k], nsteps[k]) does, bit for
+ * bit; t1 is the time of the observer's sample and nothing else.  For a caller whose interval is not a machine number apart from t0
+ * (the driver's t + dTout: (t + dTout) - t need not be dTout, and a lone run steps at dTout / n exactly).  Refusals as above, and for
+ * a dt[k] that is not positive and finite. */
+int crd_ensemble_step_rk4_own_dt(crd_ensemble *e, double t0, double t1, const double *dt, const int64_t *nsteps);
+/* crd_ensemble_step_rk4_own bracketed by events on the ensemble's stream, as crd_ensemble_step_rk4_timed: blocks until done;
+ * ms_total: device time of all rounds, the table copies between them and -- an observer open -- the sample. */
+int crd_ensemble_step_rk4_own_timed(crd_ensemble *e, double t0, double t1, const int64_t *nsteps, double *ms_total);
+/* The driver's rule for those counts, per member: nsteps[k] = ceil((t1 - t0) / (dt_safety * crd_stable_dt(member k)) - 1e-12), at
+ * least 1 -- the steps a lone run of member k's ini takes over one output interval.  No device work.  CRD_EINVAL for a NULL argument,
+ * a non-finite t0 or t1, t1 <= t0, or a dt_safety that is not positive and finite. */
+int crd_ensemble_own_steps(const crd_ensemble *e, double t0, double t1, double dt_safety, int64_t *nsteps);
 /* max |var0| of every member, per_member[0 .. n_members) (non-finite for a member that blew up; synchronises).  The blow-up guard of
  * each member's run (its ARKode call's failure, src/FHNmodel_torus.cpp:424-435). */
 int crd_ensemble_max_abs(crd_ensemble *e, double *per_member);

@@ -23,7 +23,20 @@ two-uniform / mixed per --steps-per-launch setting (default 1,2).  --root DIR im
 of the parent commit (no mixed entry point) only the two uniform ensembles are timed -- the same-visit check that nothing existing moved.
 
     python tools/ensemble_rate.py --mixed [--batches 11] [--root ../parent-build] [--json OUT]
+
+--own-dt measures every member at its own step size (Ensemble.step_rk4_own) against the common step, all to one fixed t1, in fp64:
+16 members of the shipped FHN grid with diffusion 0.06 / 0.12 / 0.24, the --mixed members (torus 80/20 against 40/20), and 16 members
+of the shipped Goldbeter grid with the ini's diffusion times 0.5 / 1 / 2.  t1 is --own-steps (default 100) steps of the member with
+the largest bound.  (a) step_rk4 at the smallest member's step, t1 / max_k n_k; (b) step_rk4_own with the counts of the driver's rule,
+n_k = ceil(t1 / (0.8 stable_dt_k) - 1e-12).  One process: after a warm-up, --batches batches (at least 9) of each, interleaved, every
+batch from the same uploaded states and timed by events on the ensemble's stream (step_rk4_timed, step_rk4_own_timed: (b)'s time holds
+its table copies between the rounds).  Reports the counts, the ratio of grid-point-steps (the arithmetic expectation) and the ratio of
+the medians.  --root DIR: with a build of the parent commit only (a) is timed; --common-only times only (a) on this build too, so that
+two builds run the same sequence of work when they are compared.
+
+    python tools/ensemble_rate.py --own-dt [--batches 9] [--own-steps 100] [--common-only] [--root ../parent-build] [--json OUT]
 """
+import math
 import argparse
 import json
 import os
@@ -250,6 +263,71 @@ def main_mixed(a):
             json.dump({"device": "MI355X", "rows": [row]}, f, indent=1)
 
 
+def own_dt_cases():
+    """name -> (members, mixed)."""
+    def scan(case, model, scale):
+        p = crd.load_ini(os.path.join(INI, "%s_shipped.ini" % case), model, "torus").params
+        out = []
+        for k in range(16):
+            q = crd._capi.Params.from_buffer_copy(p)
+            q.diffusion, q.t_boundary = scale[k % 3] * (1.0 if case == "fhn" else p.diffusion), 0.0
+            out.append(q)
+        return out
+    return {"fhn 16 x 400x1600, diffusion 0.06 / 0.12 / 0.24": (scan("fhn", "fhn", (0.06, 0.12, 0.24)), False),
+            "fhn 8 x 400x1600 (torus 80/20) + 8 x 400x800 (torus 40/20)": (mixed_members(), True),
+            "goldbeter 16 x 100x400, diffusion x 0.5 / 1 / 2": (scan("goldbeter", "goldbeter", (0.5, 1.0, 2.0)), False)}
+
+
+def main_own_dt(a):
+    if a.batches < 9:
+        sys.exit("--batches: at least 9")
+    has_own = hasattr(crd.Ensemble, "step_rk4_own_timed") and not a.common_only
+    rows = []
+    for name, (members, mixed) in own_dt_cases().items():
+        bound = [0.8 * crd.stable_dt(m) for m in members]
+        t1 = a.own_steps * max(bound)
+        counts = [max(1, math.ceil(t1 / b - 1e-12)) for b in bound]
+        points = [crd.grid_of(m).nx * crd.grid_of(m).ny for m in members]
+        n_max = max(counts)
+        with (crd.Ensemble(members, mixed=True) if mixed else crd.Ensemble(members)) as e:
+            if hasattr(crd.Ensemble, "own_steps"):
+                assert e.own_steps(0.0, t1) == counts, (e.own_steps(0.0, t1), counts)
+            y0 = [crd.initial_conditions(crd.run_config(m)) for m in members]
+
+            def reset():  # every batch from the same states: the work does not depend on the batch
+                for k, y in enumerate(y0):
+                    e.upload(k, y)
+
+            arrangements = {"common": lambda: e.step_rk4_timed(0.0, t1 / n_max, n_max)}
+            if has_own:
+                arrangements["own"] = lambda: e.step_rk4_own_timed(0.0, t1, counts)
+            t_end = time.perf_counter() + a.window
+            while time.perf_counter() < t_end:
+                for fn in arrangements.values():
+                    reset()
+                    fn()
+            ms = {k: [] for k in arrangements}
+            for _ in range(a.batches):
+                for k, fn in arrangements.items():
+                    reset()
+                    ms[k].append(fn())
+            finite = all(np.isfinite(v) for v in e.max_abs())
+        work_common, work_own = n_max * sum(points), sum(p * n for p, n in zip(points, counts))
+        row = {"case": name, "precision": 64, "t1": t1, "counts": counts, "rounds": n_max, "point_steps_common": work_common, "point_steps_own": work_own,
+               "point_step_ratio": work_common / work_own, "batches": a.batches, "root": ROOT, "own_entry_point": has_own, "finite": finite, "ms": {}}
+        for k, v in ms.items():
+            row["ms"][k] = {"median": float(np.median(v)), "min": min(v), "max": max(v)}
+        rows.append(row)
+        print("%s\n   t1 = %.6g, counts %s\n   grid-point-steps: common %d, own %d, ratio x%.3f" % (name, t1, counts, work_common, work_own, row["point_step_ratio"]))
+        print("   " + "  ".join("%s %.3f ms (%.3f .. %.3f)" % (k, q["median"], q["min"], q["max"]) for k, q in row["ms"].items())
+              + ("  common / own x%.3f" % (row["ms"]["common"]["median"] / row["ms"]["own"]["median"]) if has_own else "  (own steps not timed)")
+              + "  [%d batches, event-timed]%s" % (a.batches, "" if finite else "  NON-FINITE STATE"), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump({"device": "MI355X", "rows": rows}, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--members", default="1,4,16,64")
@@ -260,8 +338,13 @@ def main():
     ap.add_argument("--precision", type=int, choices=(64, 32), default=64)
     ap.add_argument("--batches", type=int, default=11)
     ap.add_argument("--mixed", action="store_true", help="a mixed-geometry ensemble against the same members as two uniform ensembles in sequence")
+    ap.add_argument("--own-dt", action="store_true", help="every member at its own step size against the common step, to one fixed t1")
+    ap.add_argument("--common-only", action="store_true", help="--own-dt: time the common step alone (what a build without the entry point times)")
+    ap.add_argument("--own-steps", type=int, default=100, help="--own-dt: steps of the member with the largest bound to t1")
     ap.add_argument("--root", default=None, help="import crdmodel_amd from this checkout (a build of another commit)")
     a = ap.parse_args()
+    if a.own_dt:
+        return main_own_dt(a)
     if a.mixed:
         return main_mixed(a)
     if a.steps_per_launch:
