@@ -113,6 +113,23 @@ int efail(crd_ensemble *e, int code, const std::string &msg)
 			return efail((e), r_ == hipErrorOutOfMemory ? CRD_ENOMEM : CRD_EHIP, std::string(#expr) + ": " + hipGetErrorString(r_)); \
 	} while (0)
 
+// The geometry a launch over `count` members (slots, attempts) takes from a plan: G is EnsembleStep or EnsembleAttemptLaunch.  shapes:
+// the plan's shape table where the members differ in shape -- strips and chunks are then the members' own (the plan's are zero) and
+// the launch's block count is the table's last entry.
+template <typename G>
+void plan_geometry(G &g, const crd_ensemble *e, const EnsemblePlan &plan, int count, const std::vector<EnsembleShape> *shapes = nullptr)
+{
+	g.nx = e->nx;
+	g.ny = e->ny;
+	g.nstrips = plan.nstrips;
+	g.sw = plan.sw;
+	g.nsb = plan.nsb;
+	g.chunk = plan.chunk;
+	g.nchunks = plan.nchunks;
+	g.member_blocks = plan.nsb * plan.nchunks;
+	g.nblocks = shapes ? (*shapes)[(size_t)count].first_block : g.member_blocks * count;
+}
+
 // The first field in which member k differs from member 0 where members must agree, or nullptr.
 const char *disagreement(const crd_params &a, const crd_grid &ga, const crd_params &b, const crd_grid &gb)
 {
@@ -458,28 +475,12 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 	st.h3 = dt / 3.0;
 	st.h6 = dt / 6.0;
 	st.ka4 = std::pow(kGbKa, 4.0);  // pow(KA, p), src/GoldbeterModel_torus.cpp:695
-	st.nx = e->nx;
-	st.ny = e->ny;
-	st.nstrips = e->plan.nstrips;
-	st.sw = e->plan.sw;
-	st.nsb = e->plan.nsb;
-	st.chunk = e->plan.chunk;
-	st.nchunks = e->plan.nchunks;
-	st.member_blocks = st.nsb * st.nchunks;
-	st.nblocks = st.member_blocks * e->n;
-	if (e->mixed) st.nblocks = e->shapes[(size_t)e->n].first_block;  // (strips and chunks are the members' own: the shape table's)
+	plan_geometry(st, e, e->plan, e->n, e->mixed ? &e->shapes : nullptr);
 	const bool pairs = e->steps_per_launch == 2;
 	EnsemblePair pr{};  // the same constants on the pair launches' own plan
 	if (pairs) {
 		pr.step = st;
-		pr.step.nstrips = e->pair_plan.nstrips;
-		pr.step.sw = e->pair_plan.sw;
-		pr.step.nsb = e->pair_plan.nsb;
-		pr.step.chunk = e->pair_plan.chunk;
-		pr.step.nchunks = e->pair_plan.nchunks;
-		pr.step.member_blocks = pr.step.nsb * pr.step.nchunks;
-		pr.step.nblocks = pr.step.member_blocks * e->n;
-		if (e->mixed) pr.step.nblocks = e->pair_shapes[(size_t)e->n].first_block;
+		plan_geometry(pr.step, e, e->pair_plan, e->n, e->mixed ? &e->pair_shapes : nullptr);
 	}
 	const double cs[4] = {0.0, 0.5, 0.5, 1.0};
 	double latest_boundary = -INFINITY;  // the absorbing rows are on at stage time t exactly when t < some member's tBoundary
@@ -652,14 +653,7 @@ int step_own(crd_ensemble *e, double t0, double t1, const double *dt, const int6
 	// What the rounds share: the plan made for all B members when the ensemble was created (no re-planning as members finish).
 	EnsembleStep st{};
 	st.ka4 = std::pow(kGbKa, 4.0);  // pow(KA, p), src/GoldbeterModel_torus.cpp:695
-	st.nx = e->nx;
-	st.ny = e->ny;
-	st.nstrips = e->plan.nstrips;
-	st.sw = e->plan.sw;
-	st.nsb = e->plan.nsb;
-	st.chunk = e->plan.chunk;
-	st.nchunks = e->plan.nchunks;
-	st.member_blocks = st.nsb * st.nchunks;
+	plan_geometry(st, e, e->plan, 0);  // (nblocks: the active slots', set with each slot table)
 	// Per member, once: its step size and the constants formed from it as launch_fused_t forms them.
 	struct Own {
 		double dt, h[4];
@@ -1039,14 +1033,7 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 	l.atol = o.atol;
 	l.ka4 = ka4;
 	l.partials = e->partials;
-	l.nx = e->nx;
-	l.ny = e->ny;
-	l.nstrips = pl.nstrips;
-	l.sw = pl.sw;
-	l.nsb = pl.nsb;
-	l.chunk = pl.chunk;
-	l.nchunks = pl.nchunks;
-	l.member_blocks = pl.nsb * pl.nchunks;
+	plan_geometry(l, e, pl, 0);  // (nblocks: the active members', set with each round)
 	l.member_items = pl.nstrips * pl.nchunks;
 	const double cs[5] = {0.0, 0.5, 0.5, 1.0, 0.75};  // stage times: make_fused_call's four, then Zonneveld's fifth (launch_attempt)
 	std::vector<int> slot_member;

@@ -81,6 +81,7 @@ struct EnsembleShape {
 	int nstrips, nsb, nchunks;  // strips of columns, blocks across one chunk of rows, chunks of rows: the member's own
 	int first_block;
 };
+typedef const __attribute__((address_space(4))) EnsembleShape ConstShape;  // (as the kernels read the table)
 // Both plans below mark a prefix that leaves 32 bits with first_block = -1 from the first member past it on (the last entry too);
 // such a plan must not be launched.  The member at which the block ids overflow, or -1 where they fit.
 inline int mixed_overflow_member(const EnsembleShape *shapes, int members)

@@ -3,24 +3,23 @@
 // one-step body of the single-slab kernel (crd_fused_impl.h), on that member's planes and tables, so every point of a member goes
 // through the arithmetic it goes through in a context stepped alone: the results are bit-identical to crd_step_rk4 with the one-launch
 // stepper, under any plan.  The members' descriptors are read through the constant address space (scalar loads); what the members
-// share -- step size, stage times, geometry, chunking -- comes in the kernel arguments.  DESIGN.md, "Ensembles".
+// share -- step size, stage times, geometry, chunking -- comes in the kernel arguments.  The work item is set up by
+// crd_ensemble_item.h, as in every ensemble step unit.  DESIGN.md, "Ensembles".
 #include "crd_ensemble.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
 #pragma clang diagnostic pop
+#include "crd_ensemble_item.h"
 
 namespace crd {
 
 namespace {
 
-typedef const __attribute__((address_space(4))) EnsembleMember ConstMember;
-
-// What a launch passes to the kernel: EnsembleStep with the step's constants in the kernel's precision, rounded on the host as
-// launch_fused_t rounds them (a conversion in the kernel would be a vector instruction, its result held in vector registers).
+// What a launch passes to the kernel: the step's constants in the kernel's precision and EnsembleStep.
 template <typename Real>
 struct EnsembleArgs {
-	Real h1, h2, h3, h6, ka4;
+	StepConstants<Real> k;
 	EnsembleStep e;
 };
 
@@ -41,56 +40,14 @@ crd_ensemble_step_kernel(const EnsembleMember *members, EnsembleArgs<Real> ea)
 	if (strip >= e.nstrips) return;  // (a barrier waits for the surviving wavefronts of the workgroup only)
 	ConstMember *const m = (ConstMember *)members + member;
 
-	Slab<Real> s;
-	s.cE = static_cast<const Real *>(m->cE);
-	s.cWn = static_cast<const Real *>(m->cWn);
-	s.cP = static_cast<const Real *>(m->cP);
-	s.brow = static_cast<const Real *>(m->brow) + kGhost;  // index by row
-	s.ka4 = ea.ka4;
-	s.nx = e.nx;
-	s.nyl = e.ny;
-	s.wrap = 1;  // a member is a single slab: phi wraps inside it
-	s.has_row0 = s.has_rowN = 1;
-	s.just_diffusion = MODEL == kModelDiffusionOnly;
-	s.wrap_x = 1;
+	const Slab<Real> s = member_slab<Real, MODEL>(m, ea.k.ka4, e.nx, e.ny);
 	FusedArgs<Real> a{};
-	a.in_u = static_cast<const Real *>(m->u[e.src]);
-	a.in_v = static_cast<const Real *>(m->v[e.src]);
-	a.out_u = static_cast<Real *>(m->u[1 - e.src]);
-	a.out_v = static_cast<Real *>(m->v[1 - e.src]);
-	a.h1 = ea.h1;
-	a.h2 = ea.h2;
-	a.h3 = ea.h3;
-	a.h6 = ea.h6;
+	member_planes(a, m, e.src);
+	step_sizes(a, ea.k);
 	bool absorbs = false;
-	if constexpr (ABSORB) {
-		const double tb = m->t_boundary;
-		for (int k = 0; k < 4; k++) {
-			a.absorb[k] = e.t_stage[k] < tb ? 1 : 0;  // strict <, as absorbing() (crd_ctx.h)
-			absorbs = absorbs || a.absorb[k];
-		}
-	}
-	a.js = 0;
-	a.ny = e.ny;
-	a.r_begin[0] = a.r_begin[1] = 0;
-	a.r_end[0] = a.r_end[1] = e.ny;
-	a.chunk = e.chunk;
-	a.first2 = a.nchunks = e.nchunks;
-	a.nstrips = e.nstrips;
-	a.nitems = e.nstrips * e.nchunks;
-	a.nblocks = e.nblocks;
-	a.sw = e.sw;
-	if constexpr (ABSORB) {
-		// The selects only where this member absorbs at some stage AND the chunk's pipeline -- rows [j0 - kApron, j1 + kApron) -- can
-		// meet global row 0 or ny - 1 (the single-slab kernel's per-chunk rule, crd_rk4_fused_step_kernel; with js = 0 and ny >= 8 the
-		// rows reach row 0 exactly when j0 - kApron <= 0 and row ny - 1 exactly when j1 + kApron >= ny).
-		const int j0 = chunk * e.chunk, j1 = (j0 + e.chunk < e.ny) ? j0 + e.chunk : e.ny;
-		if (absorbs && (j0 - kApron <= 0 || j1 + kApron >= e.ny)) {
-			fused_item<Real, MODEL, true, 0, COLS, false>(s, a, strip, chunk);
-			return;
-		}
-	}
-	fused_item<Real, MODEL, false, 0, COLS, false>(s, a, strip, chunk);
+	if constexpr (ABSORB) absorbs = stage_absorbs(a, e.t_stage, m->t_boundary);
+	item_geometry(a, e.ny, e.nstrips, e.nchunks, e.nstrips * e.nchunks, e.chunk, e.sw, e.nblocks);
+	step_item<Real, MODEL, ABSORB, COLS>(s, a, absorbs, strip, chunk);
 }
 
 template <typename Src, typename Real>
@@ -111,96 +68,15 @@ __global__ void __launch_bounds__(256) crd_ensemble_planes_to_aos_kernel(const R
 	}
 }
 
-// blockIdx.y = member; NaN propagates (the blow-up guard of crd_max_abs_kernel, crd_kernels.hip)
+// blockIdx.y = member
 template <typename Real>
 __global__ void __launch_bounds__(256) crd_ensemble_max_abs_kernel(const EnsembleMember *members, int src, size_t n, double *out)
 {
-	__shared__ double part[4];
 	ConstMember *const mem = (ConstMember *)members + blockIdx.y;
-	const Real *const u = static_cast<const Real *>(mem->u[src]);
-	double m = 0.0;
-	for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) {
-		const double a = fabs((double)u[q]);
-		m = (a > m || a != a) ? a : m;
-	}
-	for (int off = 32; off > 0; off >>= 1) {
-		const double o = __shfl_down(m, off, 64);
-		m = (o > m || o != o) ? o : m;
-	}
-	if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		for (int w = 1; w < 4; w++) m = (part[w] > m || part[w] != part[w]) ? part[w] : m;
-		// non-negative doubles order like their bit patterns; NaN (0x7ff8...) sorts above every finite value
-		atomicMax(reinterpret_cast<unsigned long long *>(out + blockIdx.y), (unsigned long long)__double_as_longlong(m));
-	}
+	member_max_abs(static_cast<const Real *>(mem->u[src]), n, out);
 }
 
 inline int grid_for(size_t n, size_t cap = 2048) { return (int)((n + 255) / 256 < cap ? (n + 255) / 256 : cap); }
-
-template <typename Real, int MODEL, bool ABSORB, int COLS>
-void fire(const EnsembleMember *table, const EnsembleStep &e, hipStream_t s)
-{
-	EnsembleArgs<Real> a;
-	a.h1 = (Real)e.h1;
-	a.h2 = (Real)e.h2;
-	a.h3 = (Real)e.h3;
-	a.h6 = (Real)e.h6;
-	a.ka4 = (Real)e.ka4;
-	a.e = e;
-	crd_ensemble_step_kernel<Real, MODEL, ABSORB, COLS><<<e.nblocks, kLanes * e.sw, 0, s>>>(table, a);
-}
-
-template <typename Real, int MODEL>
-hipError_t launch_model(int cols, bool absorb, const EnsembleMember *table, const EnsembleStep &e, hipStream_t s)
-{
-	// (the diffusion-only variant skips the reaction block, absorbing rows included: no instantiation with the selects)
-	constexpr bool kCanAbsorb = MODEL != kModelDiffusionOnly;
-	if (cols == 2) {
-		if constexpr (sizeof(Real) == 4) {
-			if (kCanAbsorb && absorb) fire<Real, MODEL, kCanAbsorb, 2>(table, e, s);
-			else fire<Real, MODEL, false, 2>(table, e, s);
-			return hipSuccess;
-		}
-		return hipErrorInvalidValue;  // (fp64: one column per lane)
-	}
-	if (kCanAbsorb && absorb) fire<Real, MODEL, kCanAbsorb, 1>(table, e, s);
-	else fire<Real, MODEL, false, 1>(table, e, s);
-	return hipSuccess;
-}
-
-template <typename Real>
-hipError_t launch_real(int model, int cols, bool absorb, const EnsembleMember *table, const EnsembleStep &e, hipStream_t s)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: return launch_model<Real, CRD_MODEL_FHN>(cols, absorb, table, e, s);
-	case CRD_MODEL_GOLDBETER: return launch_model<Real, CRD_MODEL_GOLDBETER>(cols, absorb, table, e, s);
-	default: return launch_model<Real, kModelDiffusionOnly>(cols, absorb, table, e, s);
-	}
-}
-
-template <typename Real, int MODEL>
-int resident_blocks_per_cu(int cols, int sw)
-{
-	int per_cu = 0;
-	hipError_t r;
-	if constexpr (sizeof(Real) == 4)
-		if (cols == 2) r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_step_kernel<Real, MODEL, false, 2>, kLanes * sw, 0);
-		else r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_step_kernel<Real, MODEL, false, 1>, kLanes * sw, 0);
-	else
-		r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_step_kernel<Real, MODEL, false, 1>, kLanes * sw, 0);
-	return (r == hipSuccess && per_cu >= 1) ? per_cu : 1;
-}
-
-template <typename Real>
-int resident_blocks_per_cu(int model, int cols, int sw)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: return resident_blocks_per_cu<Real, CRD_MODEL_FHN>(cols, sw);
-	case CRD_MODEL_GOLDBETER: return resident_blocks_per_cu<Real, CRD_MODEL_GOLDBETER>(cols, sw);
-	default: return resident_blocks_per_cu<Real, kModelDiffusionOnly>(cols, sw);
-	}
-}
 
 }  // namespace
 
@@ -209,20 +85,15 @@ hipError_t ensemble_plan(int precision, int model, int nx, int ny, int members, 
 	clear_launch_status();
 	const bool f64 = precision == CRD_PRECISION_F64;
 	plan->cols = (!f64 && nx % 2 == 0) ? 2 : 1;  // fused_default_columns: the packed arithmetic for fp32 where the pairs do not straddle the seam
-	const int valid = plan->cols * kLanes - 2 * kApron;
-	plan->nstrips = (nx + valid - 1) / valid;
-	plan->sw = std::min(kWavesPerBlock, plan->nstrips);  // (a block of narrow members: no wavefronts that only return)
-	plan->nsb = (plan->nstrips + plan->sw - 1) / plan->sw;
-	const int per_cu = f64 ? resident_blocks_per_cu<double>(model, plan->cols, plan->sw) : resident_blocks_per_cu<float>(model, plan->cols, plan->sw);
+	cut_strips(nx, ny, plan->cols, kApron, false, plan);
+	const int per_cu = resident_blocks_per_cu(precision, model, plan->cols, plan->sw, [](auto k) {
+		using K = decltype(k);
+		return crd_ensemble_step_kernel<typename K::Real, K::kModel, K::kAbsorb, K::kCols>;
+	});
 	plan->resident_blocks = (long)device_cus() * per_cu;
-	// Rows per work item, a fixed rule ("Ensembles"): 32 -- the single slab's chunk where a launch fills the device -- halved
-	// while all members together would not give two rounds of resident blocks, down to 8; 4 where even 8-row chunks leave half the CUs
-	// without a block (fused_chunk_rows' rule for tiny launches).
+	// 32 rows -- the single slab's chunk where a launch fills the device -- under the ensembles' halving rule
 	auto blocks = [&](int chunk) { return (long)members * plan->nsb * ((ny + chunk - 1) / chunk); };
-	int chunk = 32;
-	while (chunk > 8 && blocks(chunk) < 2 * plan->resident_blocks) chunk /= 2;
-	if (chunk == 8 && blocks(8) < device_cus() / 2) chunk = 4;
-	plan->chunk = std::min(chunk, ny);
+	plan->chunk = std::min(ensemble_chunk_rows(32, blocks, plan->resident_blocks, device_cus() / 2), ny);
 	plan->nchunks = (ny + plan->chunk - 1) / plan->chunk;
 	return launch_status();
 }
@@ -231,7 +102,11 @@ hipError_t launch_ensemble_step(int precision, int model, int cols, bool absorb,
 {
 	clear_launch_status();
 	if (e.nblocks <= 0) return hipSuccess;
-	const hipError_t r = precision == CRD_PRECISION_F64 ? launch_real<double>(model, cols, absorb, table, e, s) : launch_real<float>(model, cols, absorb, table, e, s);
+	const hipError_t r = with_instantiation(precision, model, cols, absorb, [&](auto k) {
+		using K = decltype(k);
+		const EnsembleArgs<typename K::Real> a{StepConstants<typename K::Real>(e), e};
+		crd_ensemble_step_kernel<typename K::Real, K::kModel, K::kAbsorb, K::kCols><<<e.nblocks, kLanes * e.sw, 0, s>>>(table, a);
+	});
 	return r != hipSuccess ? r : launch_status();
 }
 

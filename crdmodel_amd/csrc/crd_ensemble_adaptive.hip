@@ -3,18 +3,20 @@
 // counterparts of the element-wise operations a context's integrator runs for arkHin and the dense output.  Every member goes through
 // the arithmetic a lone single-slab context goes through: the attempt runs fused_item with EMBED = 2 (the body of a context's attempt),
 // the RHS calls rhs_point_values with the stage kernel's operands, and the element-wise operations and the ydd norm are those of
-// crd_kernels.hip, per member.  Only the attempt's error norm is summed over another partition of work items.  DESIGN.md, "Ensembles".
+// crd_kernels.hip, per member.  Only the attempt's error norm is summed over another partition of work items.  The attempt kernel
+// sets its work item up itself (hand-written, as crd_ensemble_item.h's header explains); its instantiation ladder and its plan are
+// that header's.  DESIGN.md, "Ensembles".
 #include "crd_ensemble.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
 #pragma clang diagnostic pop
+#include "crd_ensemble_item.h"
 
 namespace crd {
 
 namespace {
 
-typedef const __attribute__((address_space(4))) EnsembleMember ConstMember;
 typedef const __attribute__((address_space(4))) EnsembleAttempt ConstAttempt;
 typedef const __attribute__((address_space(4))) EnsembleOp ConstOp;
 
@@ -42,6 +44,8 @@ crd_ensemble_attempt_kernel(const EnsembleMember *members, const EnsembleAttempt
 	ConstAttempt *const at = (ConstAttempt *)attempts + slot;
 	const int member = at->member;
 	ConstMember *const m = (ConstMember *)members + member;
+	// (written out, not through crd_ensemble_item.h's helpers: timed against the hand-written kernel this one lay outside the noise of the
+	// measurement in one case, profiles/ensemble/refactor_ab.txt, and the rule is then the hand-written form)
 	const size_t plane = (size_t)l.nx * (size_t)l.ny;
 
 	Slab<Real> s;
@@ -268,54 +272,6 @@ __global__ void __launch_bounds__(256) crd_ensemble_hermite_kernel(const Ensembl
 
 inline unsigned grid_for(size_t n, size_t cap = 2048) { return (unsigned)((n + 255) / 256 < cap ? (n + 255) / 256 : cap); }
 
-template <typename Real, int MODEL, bool ABSORB>
-void fire_attempts(const EnsembleMember *table, const EnsembleAttempt *attempts, const EnsembleAttemptLaunch &l, hipStream_t s)
-{
-	AttemptArgs<Real> a;
-	a.rtol = (Real)l.rtol;
-	a.atol = (Real)l.atol;
-	a.ka4 = (Real)l.ka4;
-	a.l = l;
-	crd_ensemble_attempt_kernel<Real, MODEL, ABSORB><<<l.nblocks, kLanes * l.sw, 0, s>>>(table, attempts, a);
-}
-
-template <typename Real, int MODEL>
-void attempts_model(bool absorb, const EnsembleMember *table, const EnsembleAttempt *attempts, const EnsembleAttemptLaunch &l, hipStream_t s)
-{
-	// (the diffusion-only variant skips the reaction block, absorbing rows included: no instantiation with the selects)
-	constexpr bool kCanAbsorb = MODEL != kModelDiffusionOnly;
-	if (kCanAbsorb && absorb) fire_attempts<Real, MODEL, kCanAbsorb>(table, attempts, l, s);
-	else fire_attempts<Real, MODEL, false>(table, attempts, l, s);
-}
-
-template <typename Real>
-void attempts_real(int model, bool absorb, const EnsembleMember *table, const EnsembleAttempt *attempts, const EnsembleAttemptLaunch &l, hipStream_t s)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: attempts_model<Real, CRD_MODEL_FHN>(absorb, table, attempts, l, s); break;
-	case CRD_MODEL_GOLDBETER: attempts_model<Real, CRD_MODEL_GOLDBETER>(absorb, table, attempts, l, s); break;
-	default: attempts_model<Real, kModelDiffusionOnly>(absorb, table, attempts, l, s); break;
-	}
-}
-
-template <typename Real, int MODEL>
-int attempt_blocks_per_cu(int sw)
-{
-	int per_cu = 0;
-	const hipError_t r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_attempt_kernel<Real, MODEL, false>, kLanes * sw, 0);
-	return (r == hipSuccess && per_cu >= 1) ? per_cu : 1;
-}
-
-template <typename Real>
-int attempt_blocks_per_cu(int model, int sw)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: return attempt_blocks_per_cu<Real, CRD_MODEL_FHN>(sw);
-	case CRD_MODEL_GOLDBETER: return attempt_blocks_per_cu<Real, CRD_MODEL_GOLDBETER>(sw);
-	default: return attempt_blocks_per_cu<Real, kModelDiffusionOnly>(sw);
-	}
-}
-
 template <typename Real>
 void rhs_real(int model, const EnsembleMember *table, const EnsembleOp *ops, int count, int nx, int ny, Real ka4, hipStream_t s)
 {
@@ -332,20 +288,16 @@ void rhs_real(int model, const EnsembleMember *table, const EnsembleOp *ops, int
 hipError_t ensemble_attempt_plan(int precision, int model, int nx, int ny, int members, EnsemblePlan *plan)
 {
 	clear_launch_status();
-	const bool f64 = precision == CRD_PRECISION_F64;
 	plan->cols = 1;  // (the embedded pairs run one column per lane)
-	const int valid = kLanes - 2 * (kApron + 1);
-	plan->nstrips = (nx + valid - 1) / valid;
-	plan->sw = std::min(kWavesPerBlock, plan->nstrips);
-	plan->nsb = (plan->nstrips + plan->sw - 1) / plan->sw;
-	const int per_cu = f64 ? attempt_blocks_per_cu<double>(model, plan->sw) : attempt_blocks_per_cu<float>(model, plan->sw);
+	cut_strips(nx, ny, 1, kApron + 1, false, plan);  // the embedded apron: 54 valid columns per wavefront
+	const int per_cu = resident_blocks_per_cu(precision, model, 1, plan->sw, [](auto k) {
+		using K = decltype(k);
+		return crd_ensemble_attempt_kernel<typename K::Real, K::kModel, K::kAbsorb>;
+	});
 	plan->resident_blocks = (long)device_cus() * per_cu;
 	// ensemble_plan's chunk rule, over all B members
 	auto blocks = [&](int chunk) { return (long)members * plan->nsb * ((ny + chunk - 1) / chunk); };
-	int chunk = 32;
-	while (chunk > 8 && blocks(chunk) < 2 * plan->resident_blocks) chunk /= 2;
-	if (chunk == 8 && blocks(8) < device_cus() / 2) chunk = 4;
-	plan->chunk = std::min(chunk, ny);
+	plan->chunk = std::min(ensemble_chunk_rows(32, blocks, plan->resident_blocks, device_cus() / 2), ny);
 	plan->nchunks = (ny + plan->chunk - 1) / plan->chunk;
 	return launch_status();
 }
@@ -356,8 +308,11 @@ hipError_t launch_ensemble_attempts(int precision, int model, bool absorb, const
 	clear_launch_status();
 	if (count <= 0) return hipSuccess;
 	if (l.nblocks != l.member_blocks * count) return hipErrorInvalidValue;
-	if (precision == CRD_PRECISION_F64) attempts_real<double>(model, absorb, table, attempts, l, s);
-	else attempts_real<float>(model, absorb, table, attempts, l, s);
+	(void)with_instantiation(precision, model, 1, absorb, [&](auto k) {
+		using Real = typename decltype(k)::Real;
+		const AttemptArgs<Real> a{(Real)l.rtol, (Real)l.atol, (Real)l.ka4, l};  // rounded on the host as launch_fused_t rounds them
+		crd_ensemble_attempt_kernel<Real, decltype(k)::kModel, decltype(k)::kAbsorb><<<l.nblocks, kLanes * l.sw, 0, s>>>(table, attempts, a);
+	});
 	crd_ensemble_sum_partials_kernel<<<count, 256, 0, s>>>(attempts, l.partials, l.member_items, sums_dev);
 	return launch_status();
 }

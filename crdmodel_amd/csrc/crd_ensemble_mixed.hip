@@ -1,28 +1,25 @@
 // crd_ensemble_mixed.hip -- the ensemble step over members of DIFFERENT shape (surface, nx, ny): one classical RK4 step of B members
-// in one launch (crd_ensemble.cpp drives it; crd_ensemble_create_mixed).  The body of crd_ensemble_step_kernel (crd_ensemble.hip) with
-// every size taken from the member's entry of a second device table (EnsembleShape): a block finds its member by a scalar search of the
-// prefix of block counts, the rest of the mapping is the uniform kernel's arithmetic on the member's own nsb and nchunks.  The work
-// item runs fused_item on that member's planes and tables, so the results stay bit-identical to a context stepped alone, under any
-// plan.  A unit of its own: the uniform kernels (crd_ensemble.hip) keep their code and registers and stay the path of every ensemble
-// whose members share nx and ny.  DESIGN.md, "Ensembles" (mixed geometry).
+// in one launch (crd_ensemble.cpp drives it; crd_ensemble_create_mixed).  crd_ensemble_step_kernel (crd_ensemble.hip) with every size
+// taken from the member's entry of a second device table (EnsembleShape): a block finds its member by a scalar search of the prefix
+// of block counts, the rest of the mapping is the uniform kernel's arithmetic on the member's own nsb and nchunks.  The work item's
+// set-up is written out here (crd_ensemble_item.h's header explains why); the search, the ladder and the plan are that header's.  A unit of its own: the uniform kernels keep their code and registers and stay the path of every
+// ensemble whose members share nx and ny.  DESIGN.md, "Ensembles" (mixed geometry).
 #include "crd_ensemble.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
 #pragma clang diagnostic pop
-#include "crd_ensemble_mixed.h"
+#include "crd_ensemble_item.h"
 
 namespace crd {
 
 namespace {
 
-typedef const __attribute__((address_space(4))) EnsembleMember ConstMember;
-
 // What a launch passes to the kernel: crd_ensemble.hip's EnsembleArgs and the member count (the length of the prefix).  Of e, the
 // kernel reads src, the stage times, sw, chunk and nblocks: what the launch shares; the geometry is the member's.
 template <typename Real>
 struct EnsembleMixedArgs {
-	Real h1, h2, h3, h6, ka4;
+	StepConstants<Real> k;
 	EnsembleStep e;
 	int members;
 };
@@ -35,7 +32,7 @@ crd_ensemble_step_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	const EnsembleStep &e = ea.e;
 	// member-major block order through xcd_remap, as crd_ensemble_step_kernel: a member's blocks share one L2
 	const int blk = xcd_remap((int)blockIdx.x, e.nblocks);
-	const int member = mixed_member((ConstShape *)shapes, ea.members, blk);
+	const int member = prefix_entry((ConstShape *)shapes, ea.members, blk);
 	ConstShape *const sh = (ConstShape *)shapes + member;
 	const int nx = sh->nx, ny = sh->ny, nstrips = sh->nstrips, nsb = sh->nsb, nchunks = sh->nchunks;
 	const int rest = blk - sh->first_block;
@@ -45,12 +42,14 @@ crd_ensemble_step_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	if (strip >= nstrips) return;  // (surplus wavefronts of a member narrower than the block; a barrier waits for the survivors only)
 	ConstMember *const m = (ConstMember *)members + member;
 
+	// (written out, not through crd_ensemble_item.h's helpers: timed against the hand-written kernel this one lay outside the noise of the
+	// measurement in one case, profiles/ensemble/refactor_ab.txt, and the rule is then the hand-written form)
 	Slab<Real> s;
 	s.cE = static_cast<const Real *>(m->cE);
 	s.cWn = static_cast<const Real *>(m->cWn);
 	s.cP = static_cast<const Real *>(m->cP);
 	s.brow = static_cast<const Real *>(m->brow) + kGhost;  // index by row
-	s.ka4 = ea.ka4;
+	s.ka4 = ea.k.ka4;
 	s.nx = nx;
 	s.nyl = ny;
 	s.wrap = 1;  // a member is a single slab: phi wraps inside it
@@ -62,10 +61,10 @@ crd_ensemble_step_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	a.in_v = static_cast<const Real *>(m->v[e.src]);
 	a.out_u = static_cast<Real *>(m->u[1 - e.src]);
 	a.out_v = static_cast<Real *>(m->v[1 - e.src]);
-	a.h1 = ea.h1;
-	a.h2 = ea.h2;
-	a.h3 = ea.h3;
-	a.h6 = ea.h6;
+	a.h1 = ea.k.h1;
+	a.h2 = ea.k.h2;
+	a.h3 = ea.k.h3;
+	a.h6 = ea.k.h6;
 	bool absorbs = false;
 	if constexpr (ABSORB) {
 		const double tb = m->t_boundary;
@@ -96,96 +95,13 @@ crd_ensemble_step_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	fused_item<Real, MODEL, false, 0, COLS, false>(s, a, strip, chunk);
 }
 
-// blockIdx.y = member, over its own nx * ny points; NaN propagates (crd_ensemble_max_abs_kernel)
+// blockIdx.y = member, over its own nx * ny points
 template <typename Real>
 __global__ void __launch_bounds__(256) crd_ensemble_max_abs_mixed_kernel(const EnsembleMember *members, const EnsembleShape *shapes, int src, double *out)
 {
-	__shared__ double part[4];
 	ConstMember *const mem = (ConstMember *)members + blockIdx.y;
 	ConstShape *const sh = (ConstShape *)shapes + blockIdx.y;
-	const size_t n = (size_t)sh->nx * (size_t)sh->ny;
-	const Real *const u = static_cast<const Real *>(mem->u[src]);
-	double m = 0.0;
-	for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) {
-		const double a = fabs((double)u[q]);
-		m = (a > m || a != a) ? a : m;
-	}
-	for (int off = 32; off > 0; off >>= 1) {
-		const double o = __shfl_down(m, off, 64);
-		m = (o > m || o != o) ? o : m;
-	}
-	if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		for (int w = 1; w < 4; w++) m = (part[w] > m || part[w] != part[w]) ? part[w] : m;
-		// non-negative doubles order like their bit patterns; NaN (0x7ff8...) sorts above every finite value
-		atomicMax(reinterpret_cast<unsigned long long *>(out + blockIdx.y), (unsigned long long)__double_as_longlong(m));
-	}
-}
-
-template <typename Real, int MODEL, bool ABSORB, int COLS>
-void fire(const EnsembleMember *table, const EnsembleShape *shapes, int members, const EnsembleStep &e, hipStream_t s)
-{
-	EnsembleMixedArgs<Real> a;
-	a.h1 = (Real)e.h1;
-	a.h2 = (Real)e.h2;
-	a.h3 = (Real)e.h3;
-	a.h6 = (Real)e.h6;
-	a.ka4 = (Real)e.ka4;
-	a.e = e;
-	a.members = members;
-	crd_ensemble_step_mixed_kernel<Real, MODEL, ABSORB, COLS><<<e.nblocks, kLanes * e.sw, 0, s>>>(table, shapes, a);
-}
-
-template <typename Real, int MODEL>
-hipError_t launch_model(int cols, bool absorb, const EnsembleMember *table, const EnsembleShape *shapes, int members, const EnsembleStep &e, hipStream_t s)
-{
-	// (the diffusion-only variant skips the reaction block, absorbing rows included: no instantiation with the selects)
-	constexpr bool kCanAbsorb = MODEL != kModelDiffusionOnly;
-	if (cols == 2) {
-		if constexpr (sizeof(Real) == 4) {
-			if (kCanAbsorb && absorb) fire<Real, MODEL, kCanAbsorb, 2>(table, shapes, members, e, s);
-			else fire<Real, MODEL, false, 2>(table, shapes, members, e, s);
-			return hipSuccess;
-		}
-		return hipErrorInvalidValue;  // (fp64: one column per lane)
-	}
-	if (kCanAbsorb && absorb) fire<Real, MODEL, kCanAbsorb, 1>(table, shapes, members, e, s);
-	else fire<Real, MODEL, false, 1>(table, shapes, members, e, s);
-	return hipSuccess;
-}
-
-template <typename Real>
-hipError_t launch_real(int model, int cols, bool absorb, const EnsembleMember *table, const EnsembleShape *shapes, int members, const EnsembleStep &e, hipStream_t s)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: return launch_model<Real, CRD_MODEL_FHN>(cols, absorb, table, shapes, members, e, s);
-	case CRD_MODEL_GOLDBETER: return launch_model<Real, CRD_MODEL_GOLDBETER>(cols, absorb, table, shapes, members, e, s);
-	default: return launch_model<Real, kModelDiffusionOnly>(cols, absorb, table, shapes, members, e, s);
-	}
-}
-
-template <typename Real, int MODEL>
-int resident_blocks_per_cu(int cols, int sw)
-{
-	int per_cu = 0;
-	hipError_t r;
-	if constexpr (sizeof(Real) == 4)
-		if (cols == 2) r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_step_mixed_kernel<Real, MODEL, false, 2>, kLanes * sw, 0);
-		else r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_step_mixed_kernel<Real, MODEL, false, 1>, kLanes * sw, 0);
-	else
-		r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_step_mixed_kernel<Real, MODEL, false, 1>, kLanes * sw, 0);
-	return (r == hipSuccess && per_cu >= 1) ? per_cu : 1;
-}
-
-template <typename Real>
-int resident_blocks_per_cu(int model, int cols, int sw)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: return resident_blocks_per_cu<Real, CRD_MODEL_FHN>(cols, sw);
-	case CRD_MODEL_GOLDBETER: return resident_blocks_per_cu<Real, CRD_MODEL_GOLDBETER>(cols, sw);
-	default: return resident_blocks_per_cu<Real, kModelDiffusionOnly>(cols, sw);
-	}
+	member_max_abs(static_cast<const Real *>(mem->u[src]), (size_t)sh->nx * (size_t)sh->ny, out);
 }
 
 }  // namespace
@@ -203,15 +119,15 @@ hipError_t ensemble_plan_mixed(int precision, int model, const int *nx, const in
 		min_ny = std::min(min_ny, ny[k]);
 	}
 	// strips per member, as ensemble_plan cuts them; one block size per launch
-	plan->sw = std::min(kWavesPerBlock, mixed_cut_strips(nx, ny, members, plan->cols * kLanes - 2 * kApron, shapes));
-	for (int k = 0; k < members; k++) shapes[k].nsb = (shapes[k].nstrips + plan->sw - 1) / plan->sw;
-	const int per_cu = f64 ? resident_blocks_per_cu<double>(model, plan->cols, plan->sw) : resident_blocks_per_cu<float>(model, plan->cols, plan->sw);
+	plan->sw = cut_strips(nx, ny, members, plan->cols, kApron, false, shapes);
+	const int per_cu = resident_blocks_per_cu(precision, model, plan->cols, plan->sw, [](auto k) {
+		using K = decltype(k);
+		return crd_ensemble_step_mixed_kernel<typename K::Real, K::kModel, K::kAbsorb, K::kCols>;
+	});
 	plan->resident_blocks = (long)device_cus() * per_cu;
 	// ensemble_plan's rule for the rows per work item, over the blocks of all members together; one height for the launch
-	int chunk = 32;
-	while (chunk > 8 && mixed_blocks(shapes, members, chunk) < 2 * plan->resident_blocks) chunk /= 2;
-	if (chunk == 8 && mixed_blocks(shapes, members, 8) < device_cus() / 2) chunk = 4;
-	plan->chunk = std::min(chunk, min_ny);
+	auto blocks = [&](int chunk) { return mixed_blocks(shapes, members, chunk); };
+	plan->chunk = std::min(ensemble_chunk_rows(32, blocks, plan->resident_blocks, device_cus() / 2), min_ny);
 	mixed_fill_prefix(plan->chunk, members, shapes);
 	return launch_status();
 }
@@ -222,8 +138,11 @@ hipError_t launch_ensemble_step_mixed(int precision, int model, int cols, bool a
 	clear_launch_status();
 	if (e.nblocks <= 0) return hipSuccess;
 	if (members < 1 || !shapes || e.sw < 1 || e.sw > kMaxWavesPerBlock || e.chunk < 1) return hipErrorInvalidValue;
-	const hipError_t r = precision == CRD_PRECISION_F64 ? launch_real<double>(model, cols, absorb, table, shapes, members, e, s)
-	                                                    : launch_real<float>(model, cols, absorb, table, shapes, members, e, s);
+	const hipError_t r = with_instantiation(precision, model, cols, absorb, [&](auto k) {
+		using K = decltype(k);
+		const EnsembleMixedArgs<typename K::Real> a{StepConstants<typename K::Real>(e), e, members};
+		crd_ensemble_step_mixed_kernel<typename K::Real, K::kModel, K::kAbsorb, K::kCols><<<e.nblocks, kLanes * e.sw, 0, s>>>(table, shapes, a);
+	});
 	return r != hipSuccess ? r : launch_status();
 }
 

@@ -1,32 +1,26 @@
 // crd_ensemble_mixed_multi.hip -- the ensemble pair over members of DIFFERENT shape: TWO classical RK4 steps of B members in one
-// launch (crd_ensemble.cpp drives it; crd_ensemble_create_mixed with crd_ensemble_set_steps_per_launch(e, 2)).  The body of
+// launch (crd_ensemble.cpp drives it; crd_ensemble_create_mixed with crd_ensemble_set_steps_per_launch(e, 2)).
 // crd_ensemble_pair_kernel (crd_ensemble_multi.hip) with every size taken from the member's entry of the shape table, the block found
-// by crd_ensemble_mixed.h's scalar search.  The block size is the launch's: where the block is the strip (Goldbeter in fp64) a narrow
-// member's block has wavefronts wholly beyond its nx, as the uniform kernel's last block has -- they run on (every member's strip
-// count is a multiple of sw there), so the stores' vmcnt contract and the barrier hold.  A unit of its own, its device assembly kept
-// and checked by tools/kernel_regs.py --check before libcrd.so links, as crd_ensemble_multi.hip's.  DESIGN.md, "Ensembles".
+// by the scalar search of crd_ensemble_item.h, which also sets the work item up.  The block size is the launch's: where the block is
+// the strip (Goldbeter in fp64) a narrow member's block has wavefronts wholly beyond its nx, as the uniform kernel's last block has --
+// they run on (every member's strip count is a multiple of sw there), so the stores' vmcnt contract and the barrier hold.  A unit of
+// its own, its device assembly kept and checked by tools/kernel_regs.py --check before libcrd.so links, as crd_ensemble_multi.hip's.
+// DESIGN.md, "Ensembles".
 #include "crd_ensemble.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
 #pragma clang diagnostic pop
-#include "crd_ensemble_mixed.h"
+#include "crd_ensemble_item.h"
 
 #ifndef CRD_NO_ENSEMBLE_PAIRS  // (make KERNEL_TABLE=0: nothing checks this unit's assembly, so it ships no kernel; Makefile)
 namespace crd {
 
 namespace {
 
-typedef const __attribute__((address_space(4))) EnsembleMember ConstMember;
-
-// Rows per work item the plan starts from: crd_ensemble_multi.hip's.
-#ifndef CRD_ENSEMBLE_PAIR_CHUNK
-#define CRD_ENSEMBLE_PAIR_CHUNK 128
-#endif
-
 template <typename Real>
 struct EnsembleMixedPairArgs {
-	Real h1, h2, h3, h6, ka4;
+	StepConstants<Real> k;
 	EnsemblePair e;
 	int members;
 };
@@ -39,7 +33,7 @@ crd_ensemble_pair_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	const EnsembleStep &e = ea.e.step;
 	// block id -> (member, chunk, strip block): crd_ensemble_step_mixed_kernel's mapping
 	const int blk = xcd_remap((int)blockIdx.x, e.nblocks);
-	const int member = mixed_member((ConstShape *)shapes, ea.members, blk);
+	const int member = prefix_entry((ConstShape *)shapes, ea.members, blk);
 	ConstShape *const sh = (ConstShape *)shapes + member;
 	const int nx = sh->nx, ny = sh->ny, nstrips = sh->nstrips, nsb = sh->nsb, nchunks = sh->nchunks;
 	const int rest = blk - sh->first_block;
@@ -50,12 +44,14 @@ crd_ensemble_pair_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	if (strip >= nstrips) return;  // (never where the block is the strip; a barrier waits for the surviving wavefronts only)
 	ConstMember *const m = (ConstMember *)members + member;
 
+	// member_slab's fill (crd_ensemble_item.h), written out: behind the helper one instantiation of this kernel -- fp32 Goldbeter,
+	// absorbing, two columns -- keeps one scalar value fewer in vector lanes, and the resource rows are held equal
 	Slab<Real> s;
 	s.cE = static_cast<const Real *>(m->cE);
 	s.cWn = static_cast<const Real *>(m->cWn);
 	s.cP = static_cast<const Real *>(m->cP);
 	s.brow = static_cast<const Real *>(m->brow) + kGhost;  // index by row (kGhost >= 2 kApron entries either side: the pair's aprons)
-	s.ka4 = ea.ka4;
+	s.ka4 = ea.k.ka4;
 	s.nx = nx;
 	s.nyl = ny;
 	s.wrap = 1;  // a member is a single slab: phi wraps inside it
@@ -63,14 +59,8 @@ crd_ensemble_pair_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	s.just_diffusion = MODEL == kModelDiffusionOnly;
 	s.wrap_x = 1;
 	FusedArgs<Real> a{};
-	a.in_u = static_cast<const Real *>(m->u[e.src]);
-	a.in_v = static_cast<const Real *>(m->v[e.src]);
-	a.out_u = static_cast<Real *>(m->u[1 - e.src]);
-	a.out_v = static_cast<Real *>(m->v[1 - e.src]);
-	a.h1 = ea.h1;
-	a.h2 = ea.h2;
-	a.h3 = ea.h3;
-	a.h6 = ea.h6;
+	member_planes(a, m, e.src);
+	step_sizes(a, ea.k);
 	bool absorbs = false;
 	if constexpr (ABSORB) {
 		const double tb = m->t_boundary;
@@ -80,16 +70,7 @@ crd_ensemble_pair_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 			absorbs = absorbs || a.absorb[k] || a.absorb2[k];
 		}
 	}
-	a.js = 0;
-	a.ny = ny;
-	a.r_begin[0] = a.r_begin[1] = 0;
-	a.r_end[0] = a.r_end[1] = ny;
-	a.chunk = e.chunk;
-	a.first2 = a.nchunks = nchunks;
-	a.nstrips = nstrips;
-	a.nitems = nstrips * nchunks;
-	a.nblocks = e.nblocks;
-	a.sw = e.sw;
+	item_geometry(a, ny, nstrips, nchunks, nstrips * nchunks, e.chunk, e.sw, e.nblocks);
 	// the rings (and, the block as the strip, the edge area) of this block's wavefronts: sized as crd_ensemble_pair_kernel sizes them
 	__shared__ __attribute__((aligned(16))) char rings[kRingBytes<Real, COLS, 2>];
 	lds_char *const block_rings = (lds_char *)rings;
@@ -112,71 +93,6 @@ crd_ensemble_pair_mixed_kernel(const EnsembleMember *members, const EnsembleShap
 	}
 }
 
-template <typename Real, int MODEL, bool ABSORB, int COLS>
-void fire(const EnsembleMember *table, const EnsembleShape *shapes, int members, const EnsemblePair &e, hipStream_t s)
-{
-	EnsembleMixedPairArgs<Real> a;
-	a.h1 = (Real)e.step.h1;
-	a.h2 = (Real)e.step.h2;
-	a.h3 = (Real)e.step.h3;
-	a.h6 = (Real)e.step.h6;
-	a.ka4 = (Real)e.step.ka4;
-	a.e = e;
-	a.members = members;
-	crd_ensemble_pair_mixed_kernel<Real, MODEL, ABSORB, COLS><<<e.step.nblocks, kLanes * e.step.sw, 0, s>>>(table, shapes, a);
-}
-
-template <typename Real, int MODEL>
-hipError_t launch_model(int cols, bool absorb, const EnsembleMember *table, const EnsembleShape *shapes, int members, const EnsemblePair &e, hipStream_t s)
-{
-	// (the diffusion-only variant skips the reaction block, absorbing rows included: no instantiation with the selects)
-	constexpr bool kCanAbsorb = MODEL != kModelDiffusionOnly;
-	if (cols == 2) {
-		if constexpr (sizeof(Real) == 4) {
-			if (kCanAbsorb && absorb) fire<Real, MODEL, kCanAbsorb, 2>(table, shapes, members, e, s);
-			else fire<Real, MODEL, false, 2>(table, shapes, members, e, s);
-			return hipSuccess;
-		}
-		return hipErrorInvalidValue;  // (fp64: one column per lane)
-	}
-	if (kCanAbsorb && absorb) fire<Real, MODEL, kCanAbsorb, 1>(table, shapes, members, e, s);
-	else fire<Real, MODEL, false, 1>(table, shapes, members, e, s);
-	return hipSuccess;
-}
-
-template <typename Real>
-hipError_t launch_real(int model, int cols, bool absorb, const EnsembleMember *table, const EnsembleShape *shapes, int members, const EnsemblePair &e, hipStream_t s)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: return launch_model<Real, CRD_MODEL_FHN>(cols, absorb, table, shapes, members, e, s);
-	case CRD_MODEL_GOLDBETER: return launch_model<Real, CRD_MODEL_GOLDBETER>(cols, absorb, table, shapes, members, e, s);
-	default: return launch_model<Real, kModelDiffusionOnly>(cols, absorb, table, shapes, members, e, s);
-	}
-}
-
-template <typename Real, int MODEL>
-int resident_blocks_per_cu(int cols, int sw)
-{
-	int per_cu = 0;
-	hipError_t r;
-	if constexpr (sizeof(Real) == 4)
-		if (cols == 2) r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_pair_mixed_kernel<Real, MODEL, false, 2>, kLanes * sw, 0);
-		else r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_pair_mixed_kernel<Real, MODEL, false, 1>, kLanes * sw, 0);
-	else
-		r = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, crd_ensemble_pair_mixed_kernel<Real, MODEL, false, 1>, kLanes * sw, 0);
-	return (r == hipSuccess && per_cu >= 1) ? per_cu : 1;
-}
-
-template <typename Real>
-int resident_blocks_per_cu(int model, int cols, int sw)
-{
-	switch (model) {
-	case CRD_MODEL_FHN: return resident_blocks_per_cu<Real, CRD_MODEL_FHN>(cols, sw);
-	case CRD_MODEL_GOLDBETER: return resident_blocks_per_cu<Real, CRD_MODEL_GOLDBETER>(cols, sw);
-	default: return resident_blocks_per_cu<Real, kModelDiffusionOnly>(cols, sw);
-	}
-}
-
 }  // namespace
 
 hipError_t ensemble_pair_plan_mixed(int precision, int model, const int *nx, const int *ny, int members, EnsemblePlan *plan, EnsembleShape *shapes)
@@ -193,24 +109,17 @@ hipError_t ensemble_pair_plan_mixed(int precision, int model, const int *nx, con
 		if (nx[k] % 2 != 0) plan->cols = 1;
 		min_ny = std::min(min_ny, ny[k]);
 	}
-	// 48 columns per wavefront, 112 with two columns per lane; one block size per launch
-	plan->sw = std::min(kWavesPerBlock, mixed_cut_strips(nx, ny, members, plan->cols * kLanes - 2 * kPairApron, shapes));
-	for (int k = 0; k < members; k++) {
-		shapes[k].nsb = (shapes[k].nstrips + plan->sw - 1) / plan->sw;
-		if (f64 && model == CRD_MODEL_GOLDBETER) {
-			// kCoop: the block as the strip, one apron around its sw wavefronts; every member's strips a multiple of sw
-			const int block_valid = plan->sw * kLanes - 2 * kPairApron;
-			shapes[k].nsb = (nx[k] + block_valid - 1) / block_valid;
-			shapes[k].nstrips = plan->sw * shapes[k].nsb;
-		}
-	}
-	const int per_cu = f64 ? resident_blocks_per_cu<double>(model, plan->cols, plan->sw) : resident_blocks_per_cu<float>(model, plan->cols, plan->sw);
+	// 48 columns per wavefront, 112 with two columns per lane; one block size per launch; Goldbeter in fp64: the block as the strip
+	plan->sw = cut_strips(nx, ny, members, plan->cols, kPairApron, f64 && model == CRD_MODEL_GOLDBETER, shapes);
+	const int per_cu = resident_blocks_per_cu(precision, model, plan->cols, plan->sw, [](auto k) {
+		using K = decltype(k);
+		return crd_ensemble_pair_mixed_kernel<typename K::Real, K::kModel, K::kAbsorb, K::kCols>;
+	});
 	plan->resident_blocks = (long)device_cus() * per_cu;
 	// ensemble_pair_plan's rule over the blocks of all members together; never more than the body allows on the shortest member
 	// (chunk + 16 < 2 ny)
-	int chunk = CRD_ENSEMBLE_PAIR_CHUNK;
-	while (chunk > 8 && mixed_blocks(shapes, members, chunk) < 2 * plan->resident_blocks) chunk /= 2;
-	chunk = std::min(chunk, 2 * min_ny - 4 * kApron - 1);
+	auto blocks = [&](int chunk) { return mixed_blocks(shapes, members, chunk); };
+	const int chunk = std::min(ensemble_chunk_rows(CRD_ENSEMBLE_PAIR_CHUNK, blocks, plan->resident_blocks, 0), 2 * min_ny - 4 * kApron - 1);
 	plan->chunk = std::min(chunk, min_ny);
 	mixed_fill_prefix(plan->chunk, members, shapes);
 	return launch_status();
@@ -223,8 +132,11 @@ hipError_t launch_ensemble_pair_mixed(int precision, int model, int cols, bool a
 	if (e.step.nblocks <= 0) return hipSuccess;
 	if (members < 1 || !shapes || e.step.sw < 1 || e.step.sw > kMaxWavesPerBlock || e.step.chunk < 1) return hipErrorInvalidValue;
 	if (min_ny < kEnsemblePairMinRows || e.step.chunk + 4 * kApron >= 2 * min_ny) return hipErrorInvalidValue;
-	const hipError_t r = precision == CRD_PRECISION_F64 ? launch_real<double>(model, cols, absorb, table, shapes, members, e, s)
-	                                                    : launch_real<float>(model, cols, absorb, table, shapes, members, e, s);
+	const hipError_t r = with_instantiation(precision, model, cols, absorb, [&](auto k) {
+		using K = decltype(k);
+		const EnsembleMixedPairArgs<typename K::Real> a{StepConstants<typename K::Real>(e.step), e, members};
+		crd_ensemble_pair_mixed_kernel<typename K::Real, K::kModel, K::kAbsorb, K::kCols><<<e.step.nblocks, kLanes * e.step.sw, 0, s>>>(table, shapes, a);
+	});
 	return r != hipSuccess ? r : launch_status();
 }
 

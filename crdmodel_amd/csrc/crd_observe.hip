@@ -17,7 +17,6 @@
 // DESIGN.md, "Ensembles" (observers).
 #include "crd_device.h"
 #include "crd_ensemble.h"
-#include "crd_ensemble_mixed.h"
 
 namespace crd {
 

@@ -236,3 +236,26 @@ def test_driver_stops_a_blown_up_member_alone(gpu_device, tmp_path):
         r = crd_run(["--dt", "0.02", "--outdir", str(lone_dir), write_ini(tmp_path / ("m%d.ini" % k), diffusion=d)], tmp_path)
         assert r.returncode == (0 if k == 0 else 1), r.stderr
         same_files(str(tmp_path / "ens" / ("member_%d" % k)), str(lone_dir))
+
+
+def two_small_members(model, precision, nx, ny, tb_in_dt):
+    """Two members of the smallest shapes that reach every branch of the work-item set-up: one absorbs until tb_in_dt steps into the
+    call, one never does, so one launch runs both bodies and later launches take the select-free kernel.  Returns (members, dt)."""
+    if model == "fhn":
+        base = crd.make_params("fhn", "torus", nx, 80.0, 20.0, 0.12, 1.25, ny=ny, beta_min=0.7, beta_max=1.7, precision=precision)
+    else:
+        base = crd.make_params("goldbeter", "torus", nx, 80.0, 20.0, 0.12, 0.4, ny=ny, precision=precision, just_diffusion=int(model == "diffusion_only"))
+    dt = 0.8 * crd.stable_dt(base)
+    return [params_like(base, t_boundary=tb_in_dt * dt), params_like(base, beta=0.9 * base.beta, t_boundary=0.0)], dt
+
+
+SMALL_CASES = [(m, p, nx) for m in ("fhn", "goldbeter", "diffusion_only") for p, nx in (("f64", 131), ("f32", 131), ("f32", 244))]
+
+
+@pytest.mark.parametrize("model,precision,nx", SMALL_CASES)
+def test_smallest_shapes_of_the_shared_setup(gpu_device, model, precision, nx):
+    """crd_ensemble_step_kernel on nx = 131 (three strips of 56, the last partial, one column per lane) or 244 (fp32: three strips of
+    120, two columns per lane) by ny = 21: six 4-row chunks, chunk 2 wholly interior, chunks 0 and 5 at the boundary.  tBoundary = 1.5 dt:
+    steps 1 and 2 launch the absorbing instantiation, step 3 the plain one."""
+    members, dt = two_small_members(model, precision, nx, 21, 1.5)
+    check_ensemble(members, 0.0, dt, [(0, 3)], plans=((0, 0, 1, 0, 1),))

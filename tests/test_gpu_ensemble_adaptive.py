@@ -110,6 +110,17 @@ def test_members_follow_lone_contexts(gpu_device, nx, h_max):
         assert rejected >= 1  # error control alone on a diffusion-limited grid: the error test does fail now and then
 
 
+@pytest.mark.parametrize("just_diffusion", [0, 1], ids=["goldbeter", "diffusion-only"])
+def test_fp32_goldbeter_and_diffusion_only(gpu_device, just_diffusion):
+    """The fp32 attempt kernels of Goldbeter (plain and absorbing) and of the diffusion-only variant on 131 x 21: three strips of 54
+    valid columns, the last partial, six 4-row chunks.  One member absorbs until t = 0.02, inside the first call, one never does: the
+    first rounds launch the absorbing instantiation with both bodies, the later ones the plain one."""
+    p = crd.make_params("goldbeter", "torus", 131, 80.0, 20.0, 0.12, 0.5, ny=21, t_boundary=0.02, precision="f32", just_diffusion=just_diffusion)
+    members = [p, params_like(p, beta=0.3, t_boundary=0.0), params_like(p, diffusion=0.2, t_boundary=0.0)]
+    # (fp32: the tolerance test_other_models_and_precisions uses for fp32 states)
+    check_members(members, [(0.0, 0.05), (0.05, 0.0501)], state_tol=1e-5, h_max=0.0)
+
+
 @pytest.mark.parametrize("kind", ["goldbeter", "diffusion_only", "flat", "fp32"])
 def test_other_models_and_precisions(gpu_device, kind):
     calls = [(0.0, 0.05), (0.05, 0.0501), (0.0501, 0.3)]

@@ -8,6 +8,7 @@ import copy
 import filecmp
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -294,3 +295,32 @@ def test_driver_members_write_what_lone_runs_write(gpu_device, tmp_path, keys, l
         r = crd_run(surface, ["--dt", "0.02", "--outdir", str(lone_dir), write_ini(tmp_path / ("m%d.ini" % k), **overrides)], tmp_path)
         assert r.returncode == 0, r.stderr
         same_files(str(tmp_path / "ens" / ("member_%d" % k)), str(lone_dir))
+
+
+def small_mixed_set(model, precision, even):
+    """131 x 41 (three strips), 60 x 25 (one strip: narrower than the block, surplus wavefronts), 131 x 9 (the pair kernels' minimum
+    height); even: 132 wide, so that fp32 takes two columns per lane.  The first member absorbs until 1.5 DT, the others never."""
+    w = 132 if even else 131
+    def mk(nx, ny, beta, tb):
+        if model == "fhn":
+            return crd.make_params("fhn", "torus", nx, 80.0, 20.0, 0.12, beta, ny=ny, beta_min=0.7, beta_max=1.7, precision=precision, t_boundary=tb)
+        return crd.make_params("goldbeter", "torus", nx, 80.0, 20.0, 0.12, 0.4 * beta, ny=ny, precision=precision, t_boundary=tb, just_diffusion=int(model == "diffusion_only"))
+    return [mk(w, 41, 1.25, 1.5 * DT), mk(60, 25, 1.0, 0.0), mk(w, 9, 0.9, 0.0)]
+
+
+SMALL_MIXED_CASES = [(m, p, e) for m in ("fhn", "goldbeter", "diffusion_only") for p, e in (("f64", False), ("f32", False), ("f32", True))]
+
+
+@pytest.mark.parametrize("spl", [1, 2])
+@pytest.mark.parametrize("model,precision,even", SMALL_MIXED_CASES)
+def test_smallest_shapes_of_the_shared_setup(gpu_device, monkeypatch, model, precision, even, spl):
+    """crd_ensemble_step_mixed_kernel (spl = 1) and crd_ensemble_pair_mixed_kernel (spl = 2): the first launches take the absorbing
+    instantiation with both bodies in one launch, the later ones the plain one.  Goldbeter's kinetics bound the RK4 step of these grids
+    at 0.0066 (crd.stable_dt), so its members step at 0.005: five steps at this module's 0.02 would overflow fp32."""
+    if model == "goldbeter":
+        monkeypatch.setattr(sys.modules[__name__], "DT", 0.005)
+    members = small_mixed_set(model, precision, even)
+    ys = [start_state(p, 70 + k) for k, p in enumerate(members)]
+    got = run_mixed(members, ys, CALLS[5], spl)
+    for k, p in enumerate(members):
+        assert np.array_equal(got[k], lone(p, ys[k], CALLS[5])), ("member", k)

@@ -470,3 +470,32 @@ def test_driver_observes_once_per_output(gpu_device, tmp_path):
     for k in range(2):
         rows = [l for l in open(tmp_path / ("member_%d" % k) / "observables.txt").read().splitlines() if l.strip() and not l.lstrip().startswith("#")]
         assert len(rows) == 3, rows  # outputTimestep = 3
+
+
+# ---- 9: every instantiation of crd_ensemble_own_kernel on the smallest shapes that reach every branch of the shared set-up ----
+
+def small_own_set(model, precision, even, mixed, tb):
+    """Uniform: two members of 131 (132) x 21; mixed: 131 x 41, 60 x 25, 131 x 9.  The first member absorbs until tb, the others never."""
+    w = 132 if even else 131
+    def mk(nx, ny, beta, tb):
+        if model == "fhn":
+            return fhn(nx, ny, precision=precision, beta=beta, t_boundary=tb)
+        return crd.make_params("goldbeter", "torus", nx, 80.0, 20.0, 0.12, 0.4 * beta, ny=ny, precision=precision, t_boundary=tb, just_diffusion=int(model == "diffusion_only"))
+    if mixed:
+        return [mk(w, 41, 1.25, tb), mk(60, 25, 1.0, 0.0), mk(w, 9, 0.9, 0.0)], (3, 1, 2)
+    return [mk(w, 21, 1.25, tb), mk(w, 21, 0.9, 0.0)], (3, 1)
+
+
+SMALL_OWN_CASES = [(m, p, e, x) for x in (False, True) for m in ("fhn", "goldbeter", "diffusion_only") for p, e in (("f64", False), ("f32", False), ("f32", True))]
+
+
+@pytest.mark.parametrize("model,precision,even,mixed", SMALL_OWN_CASES)
+def test_smallest_shapes_of_the_shared_setup(gpu_device, model, precision, even, mixed):
+    """Over [0, t1] with tBoundary = t1 / 2: the three-step member absorbs through its first step and at the first stage of its second,
+    beside members that never absorb; the last round launches the plain instantiation.  t1 = 0.06; 0.015 for Goldbeter, whose kinetics
+    bound the RK4 step of these grids at 0.0066 (crd.stable_dt): three steps of 0.02 would overflow fp32."""
+    t1 = 0.015 if model == "goldbeter" else 0.06
+    members, counts = small_own_set(model, precision, even, mixed, 0.5 * t1)
+    ys = [start_state(p, 90 + k) for k, p in enumerate(members)]
+    segments = [(0.0, t1, counts)]
+    check_members(members, ys, run_own(members, ys, segments, mixed=mixed), segments)

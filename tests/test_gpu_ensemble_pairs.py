@@ -11,7 +11,7 @@ import pytest
 
 import crdmodel_amd as crd
 from conftest import ROOT
-from test_gpu_ensemble import crd_run, lone, params_like, same_files, start_state, write_ini
+from test_gpu_ensemble import crd_run, lone, params_like, same_files, start_state, two_small_members, write_ini
 
 pytestmark = pytest.mark.gpu
 
@@ -297,3 +297,15 @@ def test_driver_pairs_write_the_files_single_steps_write(gpu_device, tmp_path):
     r = subprocess.run([os.path.join(ROOT, "crdmodel_amd", "bin", "crd_run"), "--model", "fhn", "--surface", "torus", "--ensemble", "beta=0.9,1.25", "--ensemble-steps", "2", "--dt",
                         "0.02", "--outdir", str(tmp_path / "two"), ini], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "two steps per launch" in r.stdout, (r.stdout, r.stderr)
+
+
+SMALL_CASES = [(m, p, nx) for m in ("fhn", "goldbeter", "diffusion_only") for p, nx in (("f64", 131), ("f32", 131), ("f32", 244))]
+
+
+@pytest.mark.parametrize("model,precision,nx", SMALL_CASES)
+def test_smallest_shapes_of_the_shared_setup(gpu_device, model, precision, nx):
+    """crd_ensemble_pair_kernel on nx = 131 / 244 by ny = 41: 8-row chunks, chunk 2 clear of the 8-row apron on both sides.  tBoundary =
+    1.5 dt: the pair (0, 1) launches the absorbing instantiation with a member that never absorbs beside one that does, the pair (2, 3)
+    the plain one."""
+    members, dt = two_small_members(model, precision, nx, 41, 1.5)
+    check_pairs(members, 0.0, dt, [(0, 5)])
