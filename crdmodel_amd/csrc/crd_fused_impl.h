@@ -250,6 +250,19 @@ __device__ __forceinline__ void edge_exchange(unsigned con, double2r (&e)[6])
 	             : "v"(con), "s"(kEdgeLanes), "n"(OFF), "n"(OFF + 16), "n"(OFF + 32), "n"(OFF + 48), "n"(OFF + 64), "n"(OFF + 80)
 	             : "memory");
 }
+// ... of the read-ahead form (kReadAhead above): the wait in front of the barrier is also what retires the read of the NEXT row, issued
+// earlier in the same iteration (ring_read_ahead).  The row's registers are operands of THIS statement, so that they are tied to the place
+// where they land: behind it the next iteration publishes the row and starts its fill at once, while the edge reads are still in flight.
+template <int OFF>
+__device__ __forceinline__ void edge_exchange(unsigned con, double2r (&e)[6], double &u, double &v)
+{
+	asm volatile("s_waitcnt lgkmcnt(0)\n\t" CRD_EDGE_BARRIER "\n\ts_mov_b64 exec, %9\n\tds_read_b128 %0, %8 offset:%10\n\tds_read_b128 %1, %8 offset:%11\n\t"
+	             "ds_read_b128 %2, %8 offset:%12\n\tds_read_b128 %3, %8 offset:%13\n\tds_read_b128 %4, %8 offset:%14\n\tds_read_b128 %5, %8 offset:%15\n\t"
+	             "s_mov_b64 exec, -1"
+	             : "=&v"(e[0]), "=&v"(e[1]), "=&v"(e[2]), "=&v"(e[3]), "=&v"(e[4]), "=&v"(e[5]), "+v"(u), "+v"(v)
+	             : "v"(con), "s"(kEdgeLanes), "n"(OFF), "n"(OFF + 16), "n"(OFF + 32), "n"(OFF + 48), "n"(OFF + 64), "n"(OFF + 80)
+	             : "memory");
+}
 
 // f(integral_constant<int, 0>{}), f(integral_constant<int, 1>{}), ... in order: a compile-time unrolled loop.
 template <typename F, int... Is>
@@ -707,16 +720,26 @@ __device__ __forceinline__ void ring_read_ahead(unsigned lds_lane, double &u, do
 {
 	asm volatile("s_waitcnt vmcnt(%3)\n\tds_read_b64 %0, %2 offset:%4\n\tds_read_b64 %1, %2 offset:%5" : "=&v"(u), "=&v"(v) : "v"(lds_lane), "n"(VMCNT), "n"(OFF_U), "n"(OFF_V) : "memory");
 }
-// ... and the top of the next iteration: the wait is for the edge reads in flight (edge_exchange).  The row's data landed at the previous
-// iteration's barrier wait already; its registers are operands here only so that they stay live, and tied to this place, up to it.
-__device__ __forceinline__ void ring_row_landed(double &u, double &v, double2r (&e)[6])
+// ... and the next iteration's wait for the edge reads in flight (edge_exchange), in front of its first stage.  The row's data landed at the
+// previous iteration's barrier wait, where its registers are operands; here only the six edge registers are, and nothing that reads them
+// may sit above this statement.
+__device__ __forceinline__ void ring_row_landed(double2r (&e)[6])
 {
-	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(u), "+v"(v), "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]) : : "memory");
+	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]) : : "memory");
+}
+// (the first row, read in front of the loop: no barrier wait has seen it)
+__device__ __forceinline__ void ring_first_row_landed(double &u, double &v)
+{
+	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(u), "+v"(v) : : "memory");
 }
 template <int VMCNT, int OFF_U, int OFF_V, typename V>
 __device__ __forceinline__ void ring_read_ahead(unsigned, V &, V &) {}  // (kReadAhead is fp64, one column per lane, three steps)
-template <typename V, int N>
-__device__ __forceinline__ void ring_row_landed(V &, V &, double2r (&)[N]) {}
+template <int N>
+__device__ __forceinline__ void ring_row_landed(double2r (&)[N]) {}
+template <typename V>
+__device__ __forceinline__ void ring_first_row_landed(V &, V &) {}
+template <int OFF, typename V, int N>
+__device__ __forceinline__ void edge_exchange(unsigned, double2r (&)[N], V &, V &) {}
 // LDS bytes of a block's rings
 template <typename Real, int COLS, int STEPS = 2, int WAVES = kMaxWavesPerBlock>
 constexpr int kRingBytes = WAVES * kRingRowsOf<typename LaneValue<Real, COLS>::type, STEPS> * 2 * kLanes * COLS * (int)sizeof(Real);
@@ -770,6 +793,12 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	constexpr bool AHEAD = kReadAhead<Real, MODEL, COLS, STEPS>;
 	constexpr int kWaitAhead = kWaitFill + 2 * (kRingRows - 1);
 	static_assert(kWaitAhead <= 63, "vmcnt is six bits");
+	// (kReadAhead, the fill in the shadow of the edge reads) Publish, fill and row scalars of an iteration sit between the reads the previous
+	// iteration's barrier released (edge_exchange) and the wait for them (ring_row_landed) instead of behind that wait.  The fill was the
+	// first vector-memory operation of its iteration before and is so now, the stores the last: a wavefront's sequence -- fill q, stores q,
+	// fill q + 1 -- is what it was, and so are both counts above.  Re-derived for the read ahead of iteration p: behind the fill of its slot
+	// (iteration p + 1 - kRingRows) lie that iteration's stores, fills and stores of iterations p + 2 - kRingRows .. p - 1 and the fill of
+	// iteration p, kRingRows - 1 fills and kRingRows - 1 store pairs = kWaitAhead; nothing moved across a vector-memory operation.
 	const int lane = threadIdx.x & (kLanes - 1);
 	const int nx = s.nx;
 	// column of lane 0 (before wrapping), and this lane's place in what the apron surrounds: the wavefront's 64 lanes -- or the block's
@@ -879,6 +908,8 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	unsigned ring_trip = ring_lane;
 	// (the rows that come out of the last pipeline at iteration m: row jbase + m - 4 STEPS)
 	Real *out_row_u = a.out_u + (ptrdiff_t)(jbase - APRON) * nx, *out_row_v = a.out_v + (ptrdiff_t)(jbase - APRON) * nx;
+	// (kReadAhead) ... and have landed here: the first iteration publishes the row before it waits for anything
+	if constexpr (AHEAD) ring_first_row_landed(P[0].u0[0], P[0].v0[0]);
 
 	// Stages 1..4 of one step on the pipeline P whose newest row is `p` (slot S0): new state of row p - 4 in (nu, nv).
 	// flag_bit: where the step's four stage flags start in amask; b4: b(j) of row p - 4 (read by the caller before row p took over its slot).
@@ -955,12 +986,31 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		// row p out of its ring slot (filled kRingRows iterations ago) ...
 		if (!AHEAD && m < FILL + kRingRows) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitFill) : "memory");  // (fewer operations in flight while no rows come out yet)
 		V E[STEPS][4];
+		// b(j) of row p into its slot, row p + kRingRows into the ring slot row p came out of, and the row the next fill takes
+		auto take_row = [&]() {
+			P[0].bq[S0] = uniform(pb);
+#ifndef CRD_PROBE_NOLOAD  // (probe builds, tools/build_variant.sh: what a launch costs without its row reads / its later steps / its stores)
+			fill(jn, trip_byte + S0 * SLOT);  // ... and row p + kRingRows into it
+#endif
+			jn = (jn < jlast) ? jn + 1 : jlast;
+		};
 		if constexpr (AHEAD) {
-			// ... which the previous iteration read ahead (landed at its barrier wait); the wait is for the neighbours' edge values
-			ring_row_landed(P[0].u0[S0], P[0].v0[S0], edge);
+			// ... which the previous iteration read ahead: it landed at that iteration's barrier wait (edge_exchange), and behind the barrier the
+			// reads of the neighbours' edge values went out.  What this iteration can do without them sits HERE, between those reads and the
+			// wait for them -- the publish of this row, its fill and the next fill's row: LDS, memory and scalar issue, which a wavefront fresh
+			// out of a barrier issues at full rate, in the time the edge reads of the block's eight (or four) wavefronts take to come back from
+			// the one LDS.  (The row's stores stay in front of the barrier; deferring them to this place was measured and not kept,
+			// profiles/r09/edge_shadow_ab.txt.)
+			edge_publish<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_pub, P[0].u0[S0]);
+			take_row();
+			if constexpr (K == M - 1) next_trip();  // (the read ahead below is the next trip's first slot)
+			// ... and only now the wait for the neighbours' edge values
+			ring_row_landed(edge);
+			// The scalar load of the next b(j) goes out BEHIND that wait: it returns on the same counter as the edge reads, and in front of the
+			// wait the wavefront would stand for its latency as well.  The barrier's wait is the next to see it, a whole iteration later.
+			pb = brow[(p < jlast) ? p + 1 : jlast];
 #pragma unroll
 			for (int n = 0; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
-			edge_publish<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_pub, P[0].u0[S0]);
 		} else if constexpr (COOP) {
 			// ... together with the neighbours' edge values, whose reads the previous iteration issued behind its barrier
 			ring_read_with_edges<kWaitSteady, S0 * SLOT, S0 * SLOT + RB>(ring_trip, P[0].u0[S0], P[0].v0[S0], edge);
@@ -972,13 +1022,10 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 #pragma unroll
 			for (int n = 0; n < STEPS; n++) E[n][0] = E[n][1] = E[n][2] = E[n][3] = zero_v;
 		}
-		P[0].bq[S0] = uniform(pb);
-#ifndef CRD_PROBE_NOLOAD  // (probe builds, tools/build_variant.sh: what a launch costs without its row reads / its later steps / its stores)
-		fill(jn, trip_byte + S0 * SLOT);  // ... and row p + kRingRows into it
-#endif
-		jn = (jn < jlast) ? jn + 1 : jlast;
-		pb = brow[(p < jlast) ? p + 1 : jlast];
-		if constexpr (AHEAD && K == M - 1) next_trip();  // (the read ahead below is the next trip's first slot)
+		if constexpr (!AHEAD) {
+			take_row();
+			pb = brow[(p < jlast) ? p + 1 : jlast];
+		}
 		V nu, nv;
 		if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);  // (see the stores below)
 		// (kReadAhead) Row p + 1 out of its ring slot -- the next one of this trip, or the first of the next -- straight into the registers it
@@ -1044,7 +1091,9 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		out_row_v += nx;
 		// (COOP) what the block's wavefronts published during this iteration is complete beyond the barrier; the reads of what the next
 		// iteration needs of it go out at once and land while that iteration waits for its row
-		if constexpr (COOP) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge);
+		// (kReadAhead: ... and its wait retires the read of the next row, whose registers it names)
+		if constexpr (AHEAD) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge, P[0].u0[(K + 1) % M], P[0].v0[(K + 1) % M]);
+		else if constexpr (COOP) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge);
 	};
 	int m = 0;
 	for_sequence(  // the pipeline fills (a chunk has at least one row: FILL iterations and more)
