@@ -243,6 +243,16 @@ _SIGNATURES = {
     "crd_ensemble_observe_read_section": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, _vp]),
     "crd_ensemble_observe_cycles": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "crd_state_section": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "crd_recorder_open": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(ObserveOptions), C.POINTER(ObserveExtras), C.c_int64, C.POINTER(_vp)]),
+    "crd_recorder_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "crd_recorder_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(ObserveOptions), C.POINTER(ObserveExtras),
+                                    C.POINTER(C.c_int64)]),
+    "crd_recorder_read": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "crd_recorder_section_info": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "crd_recorder_read_section": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int64, _vp]),
+    "crd_recorder_maps": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "crd_recorder_cycles": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "crd_recorder_close": (C.c_int, [_vp]),
 }
 
 _lib = None

@@ -278,6 +278,7 @@ int crd_create_block(const crd_params *p, int c0, int d0, int c1, int d1, int de
 void crd_destroy(crd_ctx *c)
 {
 	if (!c) return;
+	recorder_detach(c);  // a recorded context takes its group's recorder with it
 	if (c->streams) (void)hipSetDevice(c->device);  // a context refused at creation (e.g. bad device ordinal) owns nothing on any device
 	(void)hipGetLastError();
 	if (c->compute) (void)hipStreamSynchronize(c->compute);

@@ -97,6 +97,8 @@ struct StreamSet {
 	}
 };
 
+struct crd_recorder;  // crd_recorder.cpp
+
 struct crd_ctx {
 	crd_params p{};
 	crd_grid g{};
@@ -197,6 +199,8 @@ struct crd_ctx {
 	GroupBarrier *bar = nullptr;   // set while several host threads issue for the group (crd_group_step_rk4)
 	ncclComm_t nccl = nullptr;
 
+	crd_recorder *recorder = nullptr;  // the run recorder open on this context (crd_recorder_open), shared by every slab of its group
+
 	std::string err;
 
 	crd::Planes planes(int k) const { return crd::Planes{plane[k][0], plane[k][1]}; }
@@ -236,7 +240,16 @@ int prime_halo(crd_ctx *const *cs, int n, int plane_index, int depth, bool with_
 
 // crd_steppers.cpp
 FusedCall make_fused_call(const crd_ctx *c, double t, double dt, int src, int dst);
-int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, int *timed_launches);
+int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, int *timed_launches, crd_recorder *rec = nullptr);
 void decide_cycle_start(crd_ctx *const *all, int n_all);  // call once per stepping call, before run_steps (and before any issuing thread starts)
+
+// crd_recorder.cpp: what the stepping calls ask of a run recorder
+int recorder_of_call(crd_ctx *const *cs, int n, crd_recorder **out);  // the recorder of the call's contexts (or null); CRD_ESTATE unless the call covers its whole group
+int64_t recorder_stride(const crd_recorder *r);
+int64_t recorder_steps(const crd_recorder *r);                        // fixed steps taken since it was opened
+void recorder_advance(crd_recorder *r, int64_t nsteps);
+int recorder_room(crd_recorder *r, int64_t samples);                  // CRD_EINVAL when `samples` more do not fit
+int recorder_sample(crd_recorder *r, int plane_index, double t);      // one sample of state plane `plane_index` of every slab, enqueued behind its steps
+void recorder_detach(crd_ctx *c);                                     // crd_destroy: closes the recorder of the context's group
 
 }  // namespace crd

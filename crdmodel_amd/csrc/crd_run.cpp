@@ -71,6 +71,8 @@ struct Options {
 		             "  --ensemble-steps: fixed steps one launch takes (2: pairs, the same bits as single steps; members of at least 9 rows; not with adaptive = 1)\n"
 		             "  --ensemble-own-dt: every member steps at its own dtSafety x stable dt instead of the smallest member's (member files as a lone run of\n"
 		             "             that member's ini writes them; one observer sample per output; not with adaptive = 1, a pinned [Solver] dt / --dt or --ensemble-steps 2)\n"
+		             "  --observe without --ensemble (with at least one of --probe / --section / --observe-maps / --observe-cycles): the same files in the output\n"
+		             "             directory itself, recorded while a lone run or its in-process phi-slabs step (not with --decomp / --block-contexts; phi-mean: one slab)\n"
 		             "  --observe: with --ensemble, member_<k>/observables.txt -- time, min / max / sum / sum of squares of both fields and the probes' values\n"
 		             "             after every STRIDE-th step (error-controlled: at every output), recorded on the GPU; --observe-maps: also\n"
 		             "             amplitude_map.npy and activation_time.npy (first sample with var0 >= THRESHOLD); --section: also\n"
@@ -157,11 +159,23 @@ void check_ensemble_options(const Options &o)
 	if (o.ensemble.empty()) {
 		if (o.ensemble_steps) usage_error("--ensemble-steps sets an ensemble's steps per launch: it needs --ensemble");
 		if (o.ensemble_own_dt) usage_error("--ensemble-own-dt steps an ensemble's members at their own step sizes: it needs --ensemble");
-		if (o.observe) usage_error("--observe records an ensemble's members: it needs --ensemble");
-		if (!o.probes.empty()) usage_error("--probe belongs to --observe, which needs --ensemble");
-		if (o.observe_maps) usage_error("--observe-maps belongs to --observe, which needs --ensemble");
-		if (!o.sections.empty()) usage_error("--section belongs to --observe, which needs --ensemble");
-		if (o.observe_cycles) usage_error("--observe-cycles belongs to --observe, which needs --ensemble");
+		if (!o.observe) {
+			if (!o.probes.empty()) usage_error("--probe belongs to --observe, which needs --ensemble");
+			if (o.observe_maps) usage_error("--observe-maps belongs to --observe, which needs --ensemble");
+			if (!o.sections.empty()) usage_error("--section belongs to --observe, which needs --ensemble");
+			if (o.observe_cycles) usage_error("--observe-cycles belongs to --observe, which needs --ensemble");
+			return;
+		}
+		// --observe without --ensemble: the run recorder (crd_recorder_*) of a lone run or of its in-process slabs.  A bare --observe
+		// STRIDE, naming nothing to record, keeps the refusal it has always had here (tests/test_observe_host.py pins it).
+		if (o.probes.empty() && !o.observe_maps && o.sections.empty() && !o.observe_cycles)
+			usage_error("--observe records an ensemble's members: it needs --ensemble (a run without one names what to record besides the statistics: --probe, --section, --observe-maps or "
+			            "--observe-cycles)");
+		if (o.observe_stride < 1) usage_error("--observe takes a stride of at least 1 (got " + std::to_string(o.observe_stride) + ")");
+		if ((int)o.sections.size() > CRD_OBSERVE_MAX_SECTIONS) usage_error("--section: at most " + std::to_string(CRD_OBSERVE_MAX_SECTIONS) + " sections");
+		if ((int)o.probes.size() > CRD_OBSERVE_MAX_PROBES) usage_error("--probe: at most " + std::to_string(CRD_OBSERVE_MAX_PROBES) + " probes");
+		if (o.d0 > 0 || o.decomp_mpi) usage_error("--observe records phi-slabs: not with --decomp (2-D block files and contexts are not recorded)");
+		if (o.block_contexts) usage_error("--observe records phi-slabs: not with --block-contexts");
 		return;
 	}
 	if (!o.observe && !o.sections.empty()) usage_error("--section belongs to --observe STRIDE");
@@ -354,6 +368,63 @@ int write_observations(const Options &o, crd_ensemble *ens, int B)
 		if ((rc = crd_ensemble_observe_maps(ens, k, lo.data(), hi.data(), ta.data())) != CRD_OK) return rc;
 		for (size_t q = 0; q < points; q++) hi[q] -= lo[q];
 		if (!write_npy_2d(dir + "/amplitude_map.npy", hi, g.ny, g.nx) || !write_npy_2d(dir + "/activation_time.npy", ta, g.ny, g.nx)) return CRD_EIO;
+	}
+	return CRD_OK;
+}
+
+// What --observe leaves in <outdir> itself for a run without --ensemble: the files a member's directory gets, in the same formats, read
+// from the run recorder (crd_recorder_*) -- whole-grid planes whatever the number of slabs.
+int write_recording(const Options &o, crd_recorder *rec, const crd_grid &g)
+{
+	int64_t n = 0;
+	int rc = crd_recorder_count(rec, &n);
+	const size_t P = o.probes.size(), points = (size_t)(g.nx * g.ny);
+	std::vector<double> t((size_t)n), stats((size_t)n * 8), pv((size_t)n * P * 2);
+	if (rc == CRD_OK) rc = crd_recorder_read(rec, 0, n, t.data(), stats.data(), pv.data());
+	if (rc != CRD_OK) return rc;
+	FILE *f = std::fopen((o.outdir + "/observables.txt").c_str(), "w");
+	if (!f) return CRD_EIO;
+	std::fprintf(f, "# t min0 max0 sum0 sumsq0 min1 max1 sum1 sumsq1");
+	for (const auto &q : o.probes) std::fprintf(f, " var0(%lld,%lld) var1(%lld,%lld)", q.first, q.second, q.first, q.second);
+	std::fprintf(f, "\n");
+	for (size_t q = 0; q < o.sections.size(); q++) {
+		std::fprintf(f, "# section_%zu.npy: %s", q, section_name(o.sections[q].first));
+		if (o.sections[q].first == CRD_SECTION_ROW || o.sections[q].first == CRD_SECTION_COLUMN) std::fprintf(f, " %lld", o.sections[q].second);
+		std::fprintf(f, ", [sample, length, 2]; sample s at the time t of line s below\n");
+	}
+	if (!o.sections.empty()) {
+		std::fprintf(f, "# sample times:");
+		for (size_t s = 0; s < (size_t)n; s++) std::fprintf(f, " %.16e", t[s]);
+		std::fprintf(f, "\n");
+	}
+	for (size_t s = 0; s < (size_t)n; s++) {
+		std::fprintf(f, "%.16e", t[s]);
+		for (int c = 0; c < 8; c++) std::fprintf(f, " %.16e", stats[s * 8 + (size_t)c]);
+		for (size_t c = 0; c < 2 * P; c++) std::fprintf(f, " %.16e", pv[s * 2 * P + c]);
+		std::fprintf(f, "\n");
+	}
+	if (std::fclose(f) != 0) return CRD_EIO;
+	for (size_t q = 0; q < o.sections.size(); q++) {
+		int64_t length = 0;
+		if ((rc = crd_recorder_section_info(rec, (int)q, nullptr, nullptr, &length, nullptr)) != CRD_OK) return rc;
+		std::vector<double> lines((size_t)n * (size_t)length * 2);
+		if (n > 0 && (rc = crd_recorder_read_section(rec, (int)q, 0, n, lines.data())) != CRD_OK) return rc;
+		if (!write_npy(o.outdir + "/section_" + std::to_string(q) + ".npy", lines.data(), lines.size() * sizeof(double), "<f8", std::to_string(n) + ", " + std::to_string(length) + ", 2")) return CRD_EIO;
+	}
+	if (o.observe_cycles) {
+		std::vector<int32_t> count(points);
+		std::vector<double> tf(points), tl(points), period(points, std::nan(""));
+		if ((rc = crd_recorder_cycles(rec, count.data(), tf.data(), tl.data())) != CRD_OK) return rc;
+		for (size_t q = 0; q < points; q++)
+			if (count[q] >= 2) period[q] = (tl[q] - tf[q]) / (double)(count[q] - 1);
+		const std::string shape = std::to_string(g.ny) + ", " + std::to_string(g.nx);
+		if (!write_npy(o.outdir + "/activation_count.npy", count.data(), points * sizeof(int32_t), "<i4", shape) || !write_npy_2d(o.outdir + "/period_map.npy", period, g.ny, g.nx)) return CRD_EIO;
+	}
+	if (o.observe_maps) {
+		std::vector<double> lo(points), hi(points), ta(points);
+		if ((rc = crd_recorder_maps(rec, lo.data(), hi.data(), ta.data())) != CRD_OK) return rc;
+		for (size_t q = 0; q < points; q++) hi[q] -= lo[q];
+		if (!write_npy_2d(o.outdir + "/amplitude_map.npy", hi, g.ny, g.nx) || !write_npy_2d(o.outdir + "/activation_time.npy", ta, g.ny, g.nx)) return CRD_EIO;
 	}
 	return CRD_OK;
 }
@@ -805,6 +876,17 @@ int main(int argc, char *argv[])
 		return 1;
 	}
 	const int ndev = o.devices > 0 ? o.devices : G;
+	if (o.observe) {  // (refused before any device is asked for)
+		for (const auto &q : o.probes)
+			if (q.first < 0 || q.first >= g.nx || q.second < 0 || q.second >= g.ny)
+				usage_error("--probe " + std::to_string(q.first) + "," + std::to_string(q.second) + " is outside the " + std::to_string(g.nx) + " x " + std::to_string(g.ny) + " grid");
+		for (const auto &q : o.sections) {
+			if ((q.first == CRD_SECTION_ROW && (q.second < 0 || q.second >= g.ny)) || (q.first == CRD_SECTION_COLUMN && (q.second < 0 || q.second >= g.nx)))
+				usage_error(std::string("--section ") + section_name(q.first) + ":" + std::to_string(q.second) + " is outside the " + std::to_string(g.nx) + " x " + std::to_string(g.ny) + " grid");
+			if (q.first == CRD_SECTION_PHI_MEAN && G > 1)
+				usage_error("--section phi-mean is not recorded on more than one slab (a column's sum crosses the slabs): this run has " + std::to_string(G) + " (pass --gpus 1)");
+		}
+	}
 
 	double s0 = 0, s1 = 0;  // banner only, and only printed for a constant beta (src/FHNmodel_torus.cpp:268-271)
 	if (cfg.params.vary_beta == 0 && (rc = crd_steady_state_as_printed(cfg.params.model, cfg.params.beta, cfg.steady_state_decimals, &s0, &s1)) != CRD_OK)
@@ -959,6 +1041,34 @@ int main(int argc, char *argv[])
 			            lp.xcd_mapping, lp.columns_per_lane, lp.nontemporal_stores ? "non-temporal" : "plain", lp.steps_per_launch);
 	}
 
+	crd_recorder *rec = nullptr;  // (closed by crd_destroy of its contexts: cleanup)
+	if (o.observe) {
+		crd_observe_options oo{};
+		oo.stride = o.observe_stride;
+		oo.n_probes = (int32_t)o.probes.size();
+		for (size_t q = 0; q < o.probes.size(); q++) {
+			oo.probe_i[q] = (int32_t)o.probes[q].first;
+			oo.probe_j[q] = (int32_t)o.probes[q].second;
+		}
+		oo.maps = o.observe_maps ? 1 : 0;
+		oo.threshold = o.observe_threshold;
+		crd_observe_extras ex{};
+		ex.n_sections = (int32_t)o.sections.size();
+		for (size_t q = 0; q < o.sections.size(); q++) {
+			ex.kind[q] = o.sections[q].first;
+			ex.index[q] = (int32_t)o.sections[q].second;
+		}
+		ex.cycles = o.observe_cycles ? 1 : 0;
+		ex.cycle_threshold = o.cycle_threshold;
+		// fixed steps: every stride-th step of the run; error-controlled: one sample per output
+		const int64_t capacity = cfg.adaptive ? Nt : std::max<int64_t>(1, steps_per_output * Nt / oo.stride);
+		if ((rc = crd_recorder_open(ctx.data(), G, &oo, &ex, capacity, &rec)) != CRD_OK) {
+			die("crd_recorder_open", rc, ctx[0]);
+			cleanup();
+			return 1;
+		}
+	}
+
 	int status = 0;
 	double adaptive_h = 0.0;
 	long long adaptive_steps = 0, adaptive_rejected = 0;
@@ -1048,6 +1158,7 @@ int main(int argc, char *argv[])
 	}
 	if (writer.joinable()) writer.join();
 	if (writer_rc != CRD_OK && status == 0) status = die("crd_writer_write_row", writer_rc, nullptr);
+	if (rec && (rc = write_recording(o, rec, g)) != CRD_OK && status == 0) status = die("writing the recording", rc, ctx[0]);
 	if (!o.quiet && cfg.adaptive) std::cout << "\n   steps = " << adaptive_steps << " (+" << adaptive_rejected << " rejected)";
 	if (!o.quiet && steps_taken > 0 && stepping_s > 0.0) {
 		// compulsory-byte model of a step: both fields read once and written once (the one-launch stepper's traffic; the four

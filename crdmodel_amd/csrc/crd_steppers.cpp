@@ -326,10 +326,19 @@ FusedCall make_fused_call(const crd_ctx *c, double t, double dt, int src, int ds
 }
 
 // The stepping loop shared by crd_step_rk4 / crd_step_rk4_timed / the group call.
-int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, int *timed_launches)
+int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, int *timed_launches, crd_recorder *rec)
 {
 	crd_ctx *lead = cs[0];
 	if (nsteps < 0 || !(dt > 0.0) || !std::isfinite(t0)) return fail(lead, CRD_EINVAL, "bad t0 / dt / nsteps");
+	// A run recorder (crd_recorder_open) takes a sample behind every step whose count since it was opened is a multiple of its stride.
+	// Only the grouping of steps into launches changes: no pair, triple or deferred launch straddles a sample -- `lim(s)` is where the
+	// steps that may share a launch with step s end.  Times are formed from t0 and the step's index in the call as ever.  A call that
+	// would overrun the recorder is refused whole, before anything is launched.
+	const int64_t rec_stride = rec ? recorder_stride(rec) : 0, rec_steps = rec ? recorder_steps(rec) : 0;
+	if (rec)
+		if (int rc = recorder_room(rec, (rec_steps + nsteps) / rec_stride - rec_steps / rec_stride)) return rc;
+	auto lim = [&](int64_t s) { return rec ? std::min<int64_t>(nsteps, s + (rec_stride - (rec_steps + s) % rec_stride)) : nsteps; };
+	auto sample_due = [&](int64_t s) { return rec && s > 0 && (rec_steps + s) % rec_stride == 0; };  // s: steps of this call taken so far
 	const int stepper = resolve_stepper(lead);
 	if (stepper < 0) return fail(lead, CRD_EINVAL, "fused stepper not available for this configuration");
 	for (int k = 0; k < n; k++) cs[k]->dense.pending = cs[k]->ark.live = false;  // stepping on from the state handed back, not from the integrator's internal one
@@ -368,8 +377,9 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 			const int per_launch = (stepper == CRD_STEPPER_FUSED && c->plan.tuned) ? fused_steps_supported(c->p.precision, c->desc, c->plan.steps) : 1;
 			const bool pairing = per_launch >= 2;
 			// (a three-step plan: triples while three steps are left, then a pair or a single step)
-			const bool triple = per_launch == 3 && s + 3 <= nsteps && triple_is_exact(c, t0, s, dt) && (c->p.precision == CRD_PRECISION_F64 || !triple_absorbs(c, t, dt));
-			int rc, took = triple ? 3 : (pairing && s + 2 <= nsteps && pair_is_exact(c, t0, s, dt)) ? 2 : 1;
+			const int64_t end = lim(s);
+			const bool triple = per_launch == 3 && s + 3 <= end && triple_is_exact(c, t0, s, dt) && (c->p.precision == CRD_PRECISION_F64 || !triple_absorbs(c, t, dt));
+			int rc, took = triple ? 3 : (pairing && s + 2 <= end && pair_is_exact(c, t0, s, dt)) ? 2 : 1;
 			// every fourth step at most: an event pair around EVERY launch of a short run would sit inside the region being timed.  Only
 			// launches of the plan's own kind are timed (a pairing plan's odd last step, or a pair stepped singly, goes out as a one-step
 			// launch: another kernel, which must not enter the average; runs too short to hold a pair time what there is).
@@ -391,6 +401,8 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 			}
 			if (rc) return rc;
 			s += took;
+			if (sample_due(s))
+				if (int rs = recorder_sample(rec, stepper == CRD_STEPPER_STAGED ? (int)crd_ctx::Y : cur, t0 + (double)s * dt)) return rs;
 		}
 		if (cur != crd_ctx::Y) {  // odd number of fused steps: the result sits in SA; swap the plane pointers
 			std::swap(c->plane[crd_ctx::Y][0], c->plane[crd_ctx::SA][0]);
@@ -445,9 +457,10 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 			const double t_s = t0 + (double)s * dt;
 			// (a launch is the cycle's first -- which waits for the halo -- or its last -- which sends the next --, never both: at E = 3 a
 			// triple from q = 0 would be; found by tests/long_oracle_sweep.py)
-			const int nsub = (triples && s + 3 <= nsteps && q + 3 <= E && (q > 0 || E > 3) && triple_is_exact(lead, t0, s, dt) && !triple_absorbs(lead, t_s, dt))
+			const int64_t end = lim(s);
+			const int nsub = (triples && s + 3 <= end && q + 3 <= E && (q > 0 || E > 3) && triple_is_exact(lead, t0, s, dt) && !triple_absorbs(lead, t_s, dt))
 			                     ? 3
-			                     : (pairs && s + 2 <= nsteps && q + 2 <= E && pair_is_exact(lead, t0, s, dt)) ? 2 : 1;
+			                     : (pairs && s + 2 <= end && q + 2 <= E && pair_is_exact(lead, t0, s, dt)) ? 2 : 1;
 			// time one launch of the dominant kernel mid-run (fused: a launch of the cycle that is one full-height sweep, i.e. neither
 			// the split first nor the split last one, nor the one that finishes a first whose ghost readers were deferred -- whatever
 			// the two launches take, one step or two)
@@ -458,7 +471,7 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 			const double t = t0 + (double)s * dt;
 			if (fused) {
 				const int dst = (cur == crd_ctx::Y) ? crd_ctx::SA : crd_ctx::Y;
-				if (int rc = fused_launch_multi(cs, n, t, dt, cur, dst, q, nsub, timed_step, s + nsub == nsteps, triples ? 3 : 2)) return rc;
+				if (int rc = fused_launch_multi(cs, n, t, dt, cur, dst, q, nsub, timed_step, s + nsub == end, triples ? 3 : 2)) return rc;
 				cur = dst;
 			} else if (int rc = staged_step_multi(cs, n, t, dt, timed_step)) {
 				return rc;
@@ -481,6 +494,10 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 					s = 0;
 				}
 			}
+			// (the sample reads owned rows, which only this compute stream writes: it is behind the cycle's last step wherever that step
+			// was split around an exchange, and the exchange itself -- the second stream -- writes ghost rows only)
+			if (sample_due(s))
+				if (int rs = recorder_sample(rec, fused ? cur : (int)crd_ctx::Y, t0 + (double)s * dt)) return rs;
 		}
 		// (several issuing threads: the neighbours read this thread's plane pointers while they enqueue their pulls)
 		if (lead->bar && !lead->bar->wait()) return fail(lead, CRD_ESTATE, "another slab's issuing thread failed");
@@ -499,6 +516,7 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 			for (int k = 0; k < n; k++) cs[k]->cycle_pos = (int)((q0 + nsteps) % E);
 	}
 	if (timed_launches) *timed_launches = timed;
+	if (rec) recorder_advance(rec, nsteps);
 	return CRD_OK;
 }
 
@@ -527,9 +545,11 @@ int crd_step_rk4(crd_ctx *c, double t0, double dt, int64_t nsteps)
 	if (c->halo < 0) return fail(c, CRD_ESTATE, "multi-slab context is not wired (crd_comm_attach_local / crd_comm_init_rccl)");
 	if (c->halo == CRD_HALO_LOCAL) return fail(c, CRD_ESTATE, "LOCAL groups step through crd_group_step_rk4");
 	crd_ctx *one[1] = {c};
+	crd_recorder *rec = nullptr;
+	if (int rc = recorder_of_call(one, 1, &rec)) return rc;
 	decide_cycle_start(one, 1);
 	TraceRange range("crd_step_rk4");
-	return run_steps(one, 1, t0, dt, nsteps, nullptr);
+	return run_steps(one, 1, t0, dt, nsteps, nullptr, rec);
 }
 
 // LOCAL groups spread over several devices get one issuing thread per device: a single thread that enqueues every launch, event
@@ -539,6 +559,9 @@ int crd_step_rk4(crd_ctx *c, double t0, double dt, int64_t nsteps)
 // how the tests exercise the rendezvous on a one-GPU box), k = 1 the single-thread path.
 static int group_step(crd_ctx *const *ctxs, int n, double t0, double dt, int64_t nsteps, bool timed)
 {
+	crd_recorder *rec = nullptr;
+	if (ctxs && n >= 1 && ctxs[0])
+		if (int rc = recorder_of_call(ctxs, n, &rec)) return rc;  // (a recorded group steps whole: CRD_ESTATE for a part of it)
 	if (int rc = check_group(ctxs, n)) return rc;
 	if (n > 1)
 		for (int k = 0; k < n; k++)
@@ -554,11 +577,12 @@ static int group_step(crd_ctx *const *ctxs, int n, double t0, double dt, int64_t
 			if (ctxs[k]->device != ctxs[k - 1]->device) first.push_back(k);
 	}
 	if (ctxs[0]->d0 > 1) first.assign(1, 0);  // theta-blocks: one issuing thread
+	if (rec) first.assign(1, 0);              // a recorded group: one thread issues the steps and, between them, the samples
 	const int nthreads = (int)first.size();
 	decide_cycle_start(ctxs, n);
 	TraceRange range("crd_group_step_rk4");
 	std::vector<int> timed_of((size_t)nthreads, 0);
-	if (nthreads <= 1 || nsteps <= 0) return run_steps(ctxs, n, t0, dt, nsteps, timed ? &timed_of[0] : nullptr);
+	if (nthreads <= 1 || nsteps <= 0) return run_steps(ctxs, n, t0, dt, nsteps, timed ? &timed_of[0] : nullptr, rec);
 	first.push_back(n);
 	GroupBarrier bar;
 	bar.members = nthreads;
@@ -1061,13 +1085,25 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 	return rc;
 }
 
+// With a run recorder open: one sample per call, at tout, of the state handed back (plane Y) -- the ensembles' rule; a call for which
+// there is no room is refused before any work.
+static int integrate_adaptive_recorded(crd_ctx *const *cs, int n, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats)
+{
+	crd_recorder *rec = nullptr;
+	if (int rc = recorder_of_call(cs, n, &rec)) return rc;
+	if (rec)
+		if (int rc = recorder_room(rec, 1)) return rc;
+	if (int rc = integrate_adaptive_impl(cs, n, t0, tout, opt, stats)) return rc;
+	return rec ? recorder_sample(rec, crd_ctx::Y, tout) : CRD_OK;
+}
+
 int crd_integrate_adaptive(crd_ctx *c, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats)
 {
 	if (!c) return CRD_EINVAL;
 	if (c->halo < 0) return fail(c, CRD_ESTATE, "multi-slab context is not wired (crd_comm_attach_local / crd_comm_init_rccl)");
 	if (c->halo == CRD_HALO_LOCAL) return fail(c, CRD_ESTATE, "LOCAL groups integrate through crd_group_integrate_adaptive");
 	crd_ctx *one[1] = {c};
-	return integrate_adaptive_impl(one, 1, t0, tout, opt, stats);
+	return integrate_adaptive_recorded(one, 1, t0, tout, opt, stats);
 }
 
 int crd_group_integrate_adaptive(crd_ctx *const *ctxs, int n, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats)
@@ -1076,7 +1112,7 @@ int crd_group_integrate_adaptive(crd_ctx *const *ctxs, int n, double t0, double 
 	if (n > 1)
 		for (int k = 0; k < n; k++)
 			if (ctxs[k]->halo != CRD_HALO_LOCAL) return fail(ctxs[0], CRD_ESTATE, "group is not attached");
-	return integrate_adaptive_impl(ctxs, n, t0, tout, opt, stats);
+	return integrate_adaptive_recorded(ctxs, n, t0, tout, opt, stats);
 }
 
 int crd_plan_launches(crd_ctx *c)
@@ -1193,6 +1229,8 @@ int crd_step_rk4_timed(crd_ctx *c, double t0, double dt, int64_t nsteps, double 
 			c->ev_diag.push_back(e);
 		}
 	crd_ctx *one[1] = {c};
+	crd_recorder *rec = nullptr;
+	if (int rc = recorder_of_call(one, 1, &rec)) return rc;
 	decide_cycle_start(one, 1);
 	int timed = 0;
 	c->timed_rows = c->timed_steps = 0;
@@ -1201,7 +1239,7 @@ int crd_step_rk4_timed(crd_ctx *c, double t0, double dt, int64_t nsteps, double 
 	c->timing = crd_step_timing{};
 	HIP_TRY(c, hipEventRecord(c->ev_t0, c->compute));
 	trace_push("crd_step_rk4_timed");
-	const int rc_steps = run_steps(one, 1, t0, dt, nsteps, &timed);
+	const int rc_steps = run_steps(one, 1, t0, dt, nsteps, &timed, rec);
 	trace_pop();
 	c->diag_active = false;
 	if (rc_steps) return rc_steps;

@@ -815,3 +815,105 @@ class LocalGroup:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class Recorder:
+    """The run recorder (crd_recorder_open) of a Slab or of a LocalGroup: while the target steps, statistics, probes, sections, maps
+    and cycle maps are recorded on the device -- a sample after every stride-th fixed step (the count carries over calls), one per
+    integrate_adaptive call at tout.  Probes (i, j), ("row", j) and ("column", i) are indices on the global grid.  Every recorded bit is
+    the same for a lone Slab and for any LocalGroup cut of the same grid.  The state steps exactly as without a recorder.  A context
+    manager; closing the target closes the recorder too."""
+
+    def __init__(self, target, stride=1, probes=(), maps=False, threshold=0.0, sections=(), cycles=False, cycle_threshold=0.0, capacity=1024):
+        self._h = None
+        self._slabs = list(target.slabs) if hasattr(target, "slabs") else [target]
+        self.grid = self._slabs[0].grid
+        probes = list(probes)
+        if len(probes) > capi.OBSERVE_MAX_PROBES:
+            raise ValueError("at most %d probes" % capi.OBSERVE_MAX_PROBES)
+        sections = [tuple(s) if isinstance(s, (tuple, list)) else (s,) for s in sections]
+        if len(sections) > capi.OBSERVE_MAX_SECTIONS:
+            raise ValueError("at most %d sections" % capi.OBSERVE_MAX_SECTIONS)
+        opt = capi.ObserveOptions()
+        opt.stride, opt.n_probes, opt.maps, opt.threshold = int(stride), len(probes), 1 if maps else 0, float(threshold)
+        for q, (i, j) in enumerate(probes):
+            opt.probe_i[q], opt.probe_j[q] = int(i), int(j)
+        ex = capi.ObserveExtras()
+        ex.n_sections, ex.cycles, ex.cycle_threshold = len(sections), 1 if cycles else 0, float(cycle_threshold)
+        for q, sec in enumerate(sections):
+            ex.kind[q], ex.index[q] = _section_kind(sec[0]), int(sec[1]) if len(sec) > 1 else 0
+        n = len(self._slabs)
+        arr = (C.c_void_p * n)(*[s.handle for s in self._slabs])
+        h = C.c_void_p()
+        check(lib().crd_recorder_open(arr, n, C.byref(opt), C.byref(ex), int(capacity), C.byref(h)), "crd_recorder_open", self._slabs[0].handle)
+        self._h = h
+        self.n_probes, self.n_sections = len(probes), len(sections)
+
+    def _check(self, rc, where):
+        check(rc, where, self._slabs[0].handle)
+
+    def _alive(self):
+        if not self._h or any(s.handle is None for s in self._slabs):  # (crd_destroy of a recorded context has closed it)
+            self._h = None
+            raise RuntimeError("the recorder is closed")
+        return self._h
+
+    def close(self):
+        if self._h and all(s.handle is not None for s in self._slabs):
+            lib().crd_recorder_close(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def count(self):
+        n = C.c_int64()
+        self._check(lib().crd_recorder_count(self._alive(), C.byref(n)), "crd_recorder_count")
+        return n.value
+
+    def info(self):
+        """additions: D of the statistics' bound, |sum - exact| <= D 2^-53 sum|x| (sums of squares: D + 1); values_per_field; slabs;
+        stride, n_probes, maps, n_sections, cycles, capacity."""
+        d, values, slabs, cap = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+        opt, ex = capi.ObserveOptions(), capi.ObserveExtras()
+        self._check(lib().crd_recorder_info(self._alive(), C.byref(d), C.byref(values), C.byref(slabs), C.byref(opt), C.byref(ex), C.byref(cap)), "crd_recorder_info")
+        return {"additions": d.value, "values_per_field": values.value, "slabs": slabs.value, "stride": opt.stride, "n_probes": opt.n_probes, "maps": opt.maps,
+                "threshold": opt.threshold, "n_sections": ex.n_sections, "cycles": ex.cycles, "cycle_threshold": ex.cycle_threshold, "capacity": cap.value}
+
+    def read(self, first=0, count=None):
+        """(t[count], stats[count, 2, 4], probes[count, n_probes, 2]): min, max, sum, sum of squares per field.  Synchronises."""
+        if count is None:
+            count = self.count() - first
+        t, stats, probes = np.empty(count), np.empty((count, 2, 4)), np.empty((count, self.n_probes, 2))
+        self._check(lib().crd_recorder_read(self._alive(), first, count, t.ctypes.data, stats.ctypes.data, probes.ctypes.data), "crd_recorder_read")
+        return t, stats, probes
+
+    def section_info(self, section):
+        kind, index, length, additions = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._check(lib().crd_recorder_section_info(self._alive(), int(section), C.byref(kind), C.byref(index), C.byref(length), C.byref(additions)), "crd_recorder_section_info")
+        return {"kind": kind.value, "index": index.value, "length": length.value, "additions": additions.value}
+
+    def section(self, section, first=0, count=None):
+        """The recorded lines of section `section`, [sample, length, 2] (default: every sample).  Synchronises; one copy."""
+        length = self.section_info(section)["length"]
+        if count is None:
+            count = self.count() - first
+        v = np.empty((count, length, 2))
+        self._check(lib().crd_recorder_read_section(self._alive(), int(section), first, count, v.ctypes.data), "crd_recorder_read_section")
+        return v
+
+    def maps(self):
+        """(min, max, activation time) of var0 over the samples so far, whole-grid [ny, nx] planes gathered from the slabs."""
+        out = [np.empty((self.grid.ny, self.grid.nx)) for _ in range(3)]
+        self._check(lib().crd_recorder_maps(self._alive(), *[a.ctypes.data for a in out]), "crd_recorder_maps")
+        return tuple(out)
+
+    def cycles(self):
+        """(count, t_first, t_last) of the upward crossings of cycle_threshold, whole-grid [ny, nx] planes."""
+        count = np.empty((self.grid.ny, self.grid.nx), dtype=np.int32)
+        t_first, t_last = np.empty((self.grid.ny, self.grid.nx)), np.empty((self.grid.ny, self.grid.nx))
+        self._check(lib().crd_recorder_cycles(self._alive(), count.ctypes.data, t_first.ctypes.data, t_last.ctypes.data), "crd_recorder_cycles")
+        return count, t_first, t_last

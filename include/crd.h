@@ -636,7 +636,8 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
  * ensemble of 1 and of 64.  Statistics accumulate in double whatever the ensemble's precision.  min and max are exact; a sum differs
  * from the exact sum of the n = nx ny values by at most D u sum|x| (sums of squares: (D + 1) u sum x^2), u = 2^-53,
  * D = ceil(n / (256 blocks_per_member)) + 8 + blocks_per_member: no value passes through more additions than that.  A field that
- * holds a NaN reports NaN for its min, max and both sums.  No observers on multi-slab runs. */
+ * holds a NaN reports NaN for its min, max and both sums.  This observer serves ensembles; a single context and the slabs of a LOCAL
+ * group are recorded by the run recorder (crd_recorder_open, below), whose partition is by rows and survives a cut into slabs. */
 #define CRD_OBSERVE_MAX_PROBES 16
 typedef struct crd_observe_options {
 	int64_t stride;         /* >= 1: crd_ensemble_step_rk4 records a sample after every stride-th step since crd_ensemble_observe_begin */
@@ -745,6 +746,71 @@ int crd_ensemble_observe_cycles(crd_ensemble *e, int member, int32_t *count, dou
  * one holding that state: the axial profile of a large run without downloading it.  CRD_EINVAL for an unknown kind, a row or column
  * outside the grid, or a context that is one of several slabs. */
 int crd_state_section(crd_ctx *ctx, int kind, int index, double *values);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Run recorder: the observer of a single-slab context or of ALL contexts of one LOCAL group (crd_comm_attach_local), sampling inside
+ * the stepping calls.  What the ensemble observer gives a scan -- statistics, probes, sections, amplitude / activation maps, cycle maps,
+ * read off the device without downloading the state -- for the runs a context exists for: one large grid, whole or cut into phi-slabs.
+ * No reference counterpart (the reference writes every output time to text files, src/FHNmodel_torus.cpp:438-455, and reads them back
+ * in util/Plotting).  crd_observe_options and crd_observe_extras keep their documented meaning; probes, rows and columns are indices
+ * on the GLOBAL grid.
+ *
+ * One sample is, per slab, two launches on the slab's compute stream behind the step it samples -- a row pass that reads the state
+ * ONCE whatever is recorded, and a small gather of the exact values -- and one finishing launch on slab 0's device behind an event of
+ * every slab's stream (the other slabs' row records and line parts arrive by at most two peer copies per slab and sample).  No host wait.
+ *   Row pass: one wavefront per owned row.  Group c of V consecutive columns (V = 2 in fp64, 4 in fp32: a 16-byte load, or the same
+ *   columns element by element where the row does not sit on 16 bytes) belongs to lane c mod 64; element e of a lane's groups is added
+ *   in rising order into its accumulator e (squares: fma(x, x, q)); the V accumulators are folded pairwise, the 64 lanes by a shuffle
+ *   tree -- the theta-mean section's partition.  Per row: min, max, sum, sum of squares of both fields, and the row's theta-mean,
+ *   sum / nx.  With maps / cycles on, the same pass folds var0 into the slab's map / cycle planes by the rules above.
+ *   Finish: one workgroup of 256 lanes; lane l folds the records of GLOBAL rows l, l + 256, ... in rising order, then a fixed tree
+ *   128 ... 1 in LDS.  No floating-point atomics.
+ * A row belongs to exactly one slab and rows are combined by global index: statistics, theta-mean, rows, columns, probes, maps and cycle
+ * maps are THE SAME BITS for one slab and for any cut into slabs, and from run to run.  This partition differs from crd_state_observe's
+ * and the ensemble observer's on purpose (theirs is defined on the flat point index and cannot survive a cut): the sums agree with
+ * theirs to the bounds, not to the bit.  The theta-mean line of a lone context is the bits of crd_state_section(CRD_SECTION_THETA_MEAN);
+ * its phi-mean line those of crd_state_section(CRD_SECTION_PHI_MEAN).
+ * Bounds: min, max, probes, rows, columns, maps and cycle planes are exact.  With u = 2^-53,
+ *   |sum - exact| <= D u sum|x|,   |sumsq - exact| <= (D + 1) u sum x^2,
+ *   D = ceil(ceil(nx / V) / 64) + log2 V + 6 + ceil(ny / 256) + 8        (crd_recorder_info reports it);
+ * theta-mean and phi-mean: the bounds stated for the sections above.  A NaN in a row makes that field's four statistics and that row's
+ * theta-mean NaN and touches nothing else.
+ *
+ * crd_recorder_open: ctxs[k] must be slab k of n_slabs, the whole group (n_slabs = 1: a single-slab context).  Allocates, on slab 0's
+ * device, capacity rows of 8 + 2 n_probes doubles, capacity lines per section and one record of 10 + 2 (column sections) doubles per
+ * grid row; per slab, with maps three and with cycles four planes of nyl x nx doubles.  extras may be NULL.  CRD_EINVAL before any
+ * device work, crd_last_error(ctxs[0]) naming the reason: everything crd_ensemble_observe_begin_with refuses; CRD_SECTION_PHI_MEAN on
+ * more than one slab (a column's sum crosses the slabs; allowed on a lone context); block contexts (crd_create_block with d0 > 1); a
+ * context wired through RCCL with more than one rank; a context list that is not the whole LOCAL group; a second recorder on a context.
+ * While it is open:
+ *   crd_step_rk4 / crd_group_step_rk4 and their timed variants take a sample after every step whose count since open is a multiple of
+ *   stride (the count carries over calls), at time t0 + (s + 1) dt for step s of the call.  A call that would overrun the capacity is
+ *   refused whole (CRD_EINVAL, nothing launched, state and counts untouched).  Stage times are formed from the call's t0 and the step's
+ *   index as without a recorder; only the grouping of steps into launches changes -- no pair, triple or split launch straddles a
+ *   sample -- so the state is bit-identical to the same call without a recorder.  A recorded group is issued by one host thread.
+ *   crd_integrate_adaptive / crd_group_integrate_adaptive record one sample per call, at tout, of the state handed back (CRD_EINVAL
+ *   before any work when no room is left); the stride's count does not move.
+ *   A stepping call on recorded contexts that does not cover the recorder's whole group returns CRD_ESTATE.
+ * With no recorder open every call launches exactly what it launches without this interface. */
+typedef struct crd_recorder crd_recorder;
+int crd_recorder_open(crd_ctx *const *ctxs, int n_slabs, const crd_observe_options *opt, const crd_observe_extras *extras, int64_t capacity, crd_recorder **out);
+/* Samples recorded (enqueued) so far. */
+int crd_recorder_count(const crd_recorder *rec, int64_t *n_samples);
+/* D of the bound above, values per field (nx ny), the slabs recorded, the options and the capacity.  Any pointer may be NULL. */
+int crd_recorder_info(const crd_recorder *rec, int64_t *additions, int64_t *values_per_field, int32_t *n_slabs, crd_observe_options *opt, crd_observe_extras *extras,
+                      int64_t *capacity);
+/* Samples first .. first + count - 1: t[count], stats[count][8], probes[count][n_probes][2], any of them NULL.  Synchronises; one
+ * device-to-host copy.  CRD_EINVAL for a range outside the recorded samples.  Reading does not consume. */
+int crd_recorder_read(crd_recorder *rec, int64_t first, int64_t count, double *t, double *stats, double *probes);
+/* As crd_ensemble_observe_section_info / _read_section: values[count][length][2]; one copy. */
+int crd_recorder_section_info(const crd_recorder *rec, int section, int32_t *kind, int32_t *index, int64_t *length, int64_t *additions);
+int crd_recorder_read_section(crd_recorder *rec, int section, int64_t first, int64_t count, double *values);
+/* The maps / cycle maps as they stand, as whole-grid ny x nx planes gathered from the slabs (one copy per slab), any of them NULL;
+ * meaning and initial values as crd_ensemble_observe_maps / _cycles.  CRD_EINVAL when maps / cycles are off. */
+int crd_recorder_maps(crd_recorder *rec, double *min_u, double *max_u, double *t_act);
+int crd_recorder_cycles(crd_recorder *rec, int32_t *count, double *t_first, double *t_last);
+/* Close the recorder and free what it holds.  crd_destroy of a recorded context closes it too (do not close it again). */
+int crd_recorder_close(crd_recorder *rec);
 
 #ifdef __cplusplus
 }
