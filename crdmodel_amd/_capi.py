@@ -210,6 +210,8 @@ _SIGNATURES = {
     "crd_get_exchange_period": (C.c_int, [_vp]),
     "crd_group_set_threads": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int]),
     "crd_launch_plan_candidate": (C.c_int, [C.c_int, C.POINTER(LaunchPlan)]),
+    "crd_steps_per_launch_on": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "crd_rows_addressable": (C.c_int, [C.c_int64, C.c_int64, C.c_int]),
     "crd_get_step_timing": (C.c_int, [_vp, C.POINTER(StepTiming)]),
     "crd_ensemble_create": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_vp)]),
     "crd_ensemble_create_mixed": (C.c_int, [C.POINTER(Params), C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -803,6 +803,26 @@ int crd_launch_plan_candidate(int index, crd_launch_plan *out)
 	return CRD_OK;
 }
 
+int crd_rows_addressable(int64_t nx, int64_t rows, int real_bytes)
+{
+	if (nx > INT32_MAX || rows > INT32_MAX) return 0;
+	return fused_scalar_rows_addressable((long)nx, (long)rows, (long)real_bytes) ? 1 : 0;
+}
+
+int crd_steps_per_launch_on(int model, int precision, int64_t nx, int64_t nyl, int single_slab, int steps_wanted)
+{
+	if ((model != CRD_MODEL_FHN && model != CRD_MODEL_GOLDBETER) || (precision != CRD_PRECISION_F64 && precision != CRD_PRECISION_F32) || nx < 1 || nyl < 1 || nx > INT32_MAX ||
+	    nyl > INT32_MAX || steps_wanted < 1 || steps_wanted > 3)
+		return CRD_EINVAL;
+	SlabDesc d{};
+	d.nx = (int)nx;
+	d.nyl = (int)nyl;
+	d.ny = (int)nyl;
+	d.wrap = single_slab ? 1 : 0;
+	d.model = model;
+	return fused_steps_supported(precision, d, steps_wanted);
+}
+
 int crd_state_max_abs(crd_ctx *c, double *out)
 {
 	if (!c || !out) return CRD_EINVAL;

@@ -20,9 +20,13 @@ int fused_steps_supported(int precision, const SlabDesc &d, int want)
 #endif
 	// (single slabs; in fp32 -- a strip per wavefront -- the slabs of a multi-slab run too, inside their exchange cycles: the fp64 block strip
 	// measured nothing on a rank's share and keeps pairs there)
+	// (the fp64 block strip addresses its rows by 32-bit offsets into the plane, kScalarRows: beyond that span, pairs)
+	if (precision == CRD_PRECISION_F64 && !fused_scalar_rows_addressable(d.nx, fused_addressed_rows(d), 8)) three = false;
 	if (want >= 3 && three && (d.wrap || precision != CRD_PRECISION_F64) && d.nyl >= 6 * kStepHalo) return 3;
 	return (want >= 2 && fused_two_steps_supported(d)) ? 2 : 1;
 }
+
+long fused_addressed_rows(const SlabDesc &d) { return (long)d.nyl + (d.wrap ? 0L : 2L * kGhost); }
 
 // Chunk mode 3 (eight wavefronts per block strip): where a launch of the plan is the three-step fp64 FHN kernel's (crd_fused_impl.h: kCanWide).
 bool fused_wide_supported(int precision, const SlabDesc &d, int want_steps)

@@ -173,6 +173,22 @@ constexpr bool kReadAhead = false;
 template <typename Real, int MODEL, int COLS, int STEPS>
 constexpr bool kReadAhead = kCoop<Real, MODEL, COLS, STEPS> && STEPS == 3;
 #endif
+// ... and addresses its rows by ONE buffer resource per field and launch -- based at the lowest row a launch can address: row 0 of a
+// single slab, the first ghost row elsewhere -- with the row as a 32-bit byte offset in scalar registers, handed to the fills and the
+// stores as their scalar offset.  The offsets RUN (one add per row, a select at the periodic seam) where every row used to rebuild a
+// 64-bit base and a four-register resource per field; b(j) is read at a running, clamped byte offset likewise, and the fill phase's
+// shorter wait is peeled out of the steady-state loop (fused_item_multi_step).  About 50 scalar instructions per iteration down to
+// about 25; a wavefront issues one instruction per turn of its SIMD whatever its kind, and at two wavefronts per SIMD behind a barrier
+// per iteration nothing covers them (profiles/r10/scalar_rows_ab.txt).  The scalar offset is not part of a raw buffer's range check:
+// lanes parked at kStoreNowhere stay dropped.  The host keeps such launches to planes whose addressed span fits 32 bits
+// (crd_kernels.h: fused_scalar_rows_addressable).
+#if defined(CRD_NO_SCALAR_ROWS)  // (experiment switch: a resource per row, as in the two-step pipelines)
+template <typename Real, int MODEL, int COLS, int STEPS>
+constexpr bool kScalarRows = false;
+#else
+template <typename Real, int MODEL, int COLS, int STEPS>
+constexpr bool kScalarRows = kReadAhead<Real, MODEL, COLS, STEPS>;
+#endif
 // The eight-wide block strip (launch-plan chunk mode 3): the three-step fp64 FHN kernel with EIGHT wavefronts around one apron -- 488 valid
 // lanes of 512 instead of 232 of 256 -- as the only block of its CU (244 VGPRs: eight wavefronts per CU).
 constexpr int kWideWaves = 8;
@@ -665,13 +681,27 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_resource(const void *row)
 	// raw buffer (stride 0) over the bytes from `row` on: offsets are a lane's byte offset within its row (< 2 GiB)
 	return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(row), 0, (int)kRowResourceBytes, 0x00020000);
 }
+// (kScalarRows) What a work item keeps to address its rows by scalar offsets: the four planes' resources, based at local row `row_lo`,
+// the row pitch and the seam (all in bytes), the running offsets of the next fill's row, of the next stores' row and of the next b(j) --
+// the latter from the table's entry of the item's first row on, up to its last row's.  Empty where rows build their own resources.
+template <bool ON>
+struct ScalarRows {
+};
+template <>
+struct ScalarRows<true> {
+	__amdgpu_buffer_rsrc_t in_u, in_v, out_u, out_v;
+	unsigned pitch, seam, in_off, out_off, b_off, b_last;
+	int row_lo;
+	const __attribute__((address_space(4))) char *b_first;
+};
 template <bool NT, typename V>
-__device__ __forceinline__ void buffer_row_store(__amdgpu_buffer_rsrc_t r, unsigned byte_offset, V v)
+__device__ __forceinline__ void buffer_row_store(__amdgpu_buffer_rsrc_t r, unsigned byte_offset, V v, unsigned row_offset = 0)
 {
+	// (row_offset: uniform, the instruction's scalar offset -- added to the address, not to what the range check sees; kScalarRows)
 	constexpr int aux = NT ? 2 : 0;  // (2 = nt)
-	if constexpr (sizeof(V) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, byte_offset, 0, aux);
-	else if constexpr (sizeof(V) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, byte_offset, 0, aux);
-	else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_offset, 0, aux);
+	if constexpr (sizeof(V) == 4) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, byte_offset, row_offset, aux);
+	else if constexpr (sizeof(V) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, byte_offset, row_offset, aux);
+	else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_offset, row_offset, aux);
 }
 // Both fields of a ring slot into registers: waits until at most VMCNT vector-memory operations of this wavefront are outstanding
 // (the slot's LDS-DMA has landed then: the counter retires in issue order), reads, waits for the reads.  One asm statement, so no
@@ -799,6 +829,11 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	// fill q + 1 -- is what it was, and so are both counts above.  Re-derived for the read ahead of iteration p: behind the fill of its slot
 	// (iteration p + 1 - kRingRows) lie that iteration's stores, fills and stores of iterations p + 2 - kRingRows .. p - 1 and the fill of
 	// iteration p, kRingRows - 1 fills and kRingRows - 1 store pairs = kWaitAhead; nothing moved across a vector-memory operation.
+	// (kScalarRows) ... nor does the row's address moving from the resource's base into the instruction's scalar offset: the same fills and
+	// stores in the same order.  The iterations that wait for kWaitFill behind the fill -- the first kRingRows - 1 of them -- are
+	// straight-line code of their own (below), so that the loop proper carries neither the compare nor the branch around that wait.
+	constexpr bool SROWS = kScalarRows<Real, MODEL, COLS, STEPS>;
+	static_assert(!SROWS || AHEAD, "scalar row offsets: the read-ahead block strip");
 	const int lane = threadIdx.x & (kLanes - 1);
 	const int nx = s.nx;
 	// column of lane 0 (before wrapping), and this lane's place in what the apron surrounds: the wavefront's 64 lanes -- or the block's
@@ -833,6 +868,26 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		j -= (j >= s.nyl) ? wrap_nyl : 0;
 		return (ptrdiff_t)j * nx;
 	};
+	// (kScalarRows) A row as a byte offset from the lowest row a launch can address -- row 0 where phi wraps inside the slab, the first
+	// ghost row elsewhere -- in 32 bits (the host's rule: fused_scalar_rows_addressable), and the four planes' resources based there.
+	// row_offset is the arithmetic of row_base, once per item; from there the offsets run (take_row, the stores).
+	// (All of it lives in `sr`, which is empty in every other kernel: their code is what it was, to the instruction.)
+	[[maybe_unused]] ScalarRows<SROWS> sr;
+	[[maybe_unused]] auto row_offset = [&](int j, auto &rows) -> unsigned {
+		j += wrap_nyl & (j >> 31);
+		j -= (j >= s.nyl) ? wrap_nyl : 0;
+		return (unsigned)(j - rows.row_lo) * rows.pitch;
+	};
+	if constexpr (SROWS) {
+		sr.pitch = (unsigned)nx * (unsigned)sizeof(Real);
+		sr.row_lo = s.wrap ? 0 : -kGhost;
+		sr.seam = s.wrap ? (unsigned)s.nyl * sr.pitch : 0xffffffffu;  // one row beyond the last: the next row is the plane's first (no wrap: never reached)
+		const ptrdiff_t lo = (ptrdiff_t)sr.row_lo * nx;
+		sr.in_u = row_resource(a.in_u + lo);
+		sr.in_v = row_resource(a.in_v + lo);
+		sr.out_u = row_resource(a.out_u + lo);
+		sr.out_v = row_resource(a.out_v + lo);
+	}
 	// Global phi boundary rows (src/FHNmodel_torus.cpp:643-653).  Rows ny - 1 and 0 are neighbours on the periodic grid: within the rows
 	// this item's pipeline touches (fewer than 2 ny of them) they are local rows jb, jb + 1 and possibly jb + ny, jb + ny + 1.  Two
 	// scalars and a bit mask of the 4 STEPS stage flags instead of js, ny and as many flag words: the body with the selects must not need
@@ -890,17 +945,37 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		if (col < 0) col += nx;
 		doff[h] = (unsigned)col * (unsigned)sizeof(Real) + (unsigned)(q % (int)sizeof(Real));
 	}
+	// the row at byte `row_off` (uniform) of both fields' resources -> the ring slot at byte `slot_byte` (uniform)
+	[[maybe_unused]] auto fill_from = [&](const auto ru, const auto rv, unsigned row_off, int slot_byte) {  // (kScalarRows)
+#pragma unroll
+		for (int h = 0; h < G1; h++) __builtin_amdgcn_raw_ptr_buffer_load_lds(ru, ring + (slot_byte + 256 * h), 4, doff[h], row_off, 0, 0);
+#pragma unroll
+		for (int h = 0; h < G1; h++) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, ring + (slot_byte + RB + 256 * h), 4, doff[h], row_off, 0, 0);
+	};
 	auto fill = [&](int jrow, int slot_byte) {  // row jrow of both fields -> the ring slot at byte `slot_byte` (uniform)
-		const ptrdiff_t rb = row_base(jrow);
-		const __amdgpu_buffer_rsrc_t ru = row_resource(a.in_u + rb), rv = row_resource(a.in_v + rb);
+		if constexpr (SROWS) {
+			fill_from(sr.in_u, sr.in_v, row_offset(jrow, sr), slot_byte);
+		} else {
+			const ptrdiff_t rb = row_base(jrow);
+			const __amdgpu_buffer_rsrc_t ru = row_resource(a.in_u + rb), rv = row_resource(a.in_v + rb);
 #pragma unroll
-		for (int h = 0; h < G1; h++) __builtin_amdgcn_raw_ptr_buffer_load_lds(ru, ring + (slot_byte + 256 * h), 4, doff[h], 0, 0, 0);
+			for (int h = 0; h < G1; h++) __builtin_amdgcn_raw_ptr_buffer_load_lds(ru, ring + (slot_byte + 256 * h), 4, doff[h], 0, 0, 0);
 #pragma unroll
-		for (int h = 0; h < G1; h++) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, ring + (slot_byte + RB + 256 * h), 4, doff[h], 0, 0, 0);
+			for (int h = 0; h < G1; h++) __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, ring + (slot_byte + RB + 256 * h), 4, doff[h], 0, 0, 0);
+		}
 	};
 #pragma unroll
 	for (int k = 0; k < kRingRows; k++) fill((jbase + k < jlast) ? jbase + k : jlast, k * SLOT);
 	int jn = (jbase + kRingRows < jlast) ? jbase + kRingRows : jlast;  // the row the next fill takes (the tail re-reads the last valid row)
+	// (kScalarRows) ... as its running byte offset; where the stores of the next iteration go (modulo 2^32 while the pipeline fills: the
+	// rows in front of the item's first are not stored); b(j) of the next row, from the table's entry of the item's first row on
+	if constexpr (SROWS) {
+		sr.in_off = row_offset(jn, sr);
+		sr.out_off = (unsigned)(jbase - APRON - sr.row_lo) * sr.pitch;
+		sr.b_first = (const __attribute__((address_space(4))) char *)(brow + jbase);
+		sr.b_off = 0;
+		sr.b_last = (unsigned)(jlast - jbase) * (unsigned)sizeof(Real);
+	}
 	// (kReadAhead) the first row's reads go out here: kRingRows - 1 fills behind its own
 	if constexpr (AHEAD) ring_read_ahead<kWaitFill, 0, RB>(ring_lane, P[0].u0[0], P[0].v0[0]);
 	Real pb = brow[jbase];                                            // b(j) of the row the next iteration takes
@@ -967,8 +1042,9 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			ring_trip = ring_lane + (unsigned)trip_byte;
 		}
 	};
-	auto iteration = [&](int m, auto kk, auto fed_c) {
+	auto iteration = [&](int m, auto kk, auto fed_c, auto steady_c) {
 		constexpr int FED = decltype(fed_c)::value;  // iterations before this one, if fewer than FILL
+		constexpr bool STEADY = decltype(steady_c)::value;  // (kScalarRows) an iteration of the loop proper: m + 1 >= FILL + kRingRows, known where it is written
 		constexpr int K = decltype(kk)::value;
 		constexpr int S0 = K % M, S4 = (K + 2 * M - 4) % M;
 #if !defined(CRD_NO_LOCKSTEP) && !defined(CRD_NO_LOCKSTEP_TWO)
@@ -990,9 +1066,24 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		auto take_row = [&]() {
 			P[0].bq[S0] = uniform(pb);
 #ifndef CRD_PROBE_NOLOAD  // (probe builds, tools/build_variant.sh: what a launch costs without its row reads / its later steps / its stores)
-			fill(jn, trip_byte + S0 * SLOT);  // ... and row p + kRingRows into it
+			if constexpr (SROWS) fill_from(sr.in_u, sr.in_v, sr.in_off, trip_byte + S0 * SLOT);
+			else fill(jn, trip_byte + S0 * SLOT);  // ... and row p + kRingRows into it
 #endif
+			if constexpr (SROWS) {
+				// one pitch on, unless the tail holds the last row; behind the plane's last row comes its first (periodic single slab)
+				sr.in_off += (jn < jlast) ? sr.pitch : 0u;
+				sr.in_off = (sr.in_off == sr.seam) ? 0u : sr.in_off;
+			}
 			jn = (jn < jlast) ? jn + 1 : jlast;
+		};
+		// b(j) of the row the next iteration takes: row p + 1, the item's last row at the most
+		[[maybe_unused]] auto next_b = [&]() {
+			if constexpr (SROWS) {
+				sr.b_off = (sr.b_off + (unsigned)sizeof(Real) < sr.b_last) ? sr.b_off + (unsigned)sizeof(Real) : sr.b_last;
+				pb = *(const __attribute__((address_space(4))) Real *)(sr.b_first + sr.b_off);
+			} else {
+				pb = brow[(p < jlast) ? p + 1 : jlast];
+			}
 		};
 		if constexpr (AHEAD) {
 			// ... which the previous iteration read ahead: it landed at that iteration's barrier wait (edge_exchange), and behind the barrier the
@@ -1008,7 +1099,7 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			ring_row_landed(edge);
 			// The scalar load of the next b(j) goes out BEHIND that wait: it returns on the same counter as the edge reads, and in front of the
 			// wait the wavefront would stand for its latency as well.  The barrier's wait is the next to see it, a whole iteration later.
-			pb = brow[(p < jlast) ? p + 1 : jlast];
+			next_b();
 #pragma unroll
 			for (int n = 0; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
 		} else if constexpr (COOP) {
@@ -1033,7 +1124,8 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		// second register set, and lands under the stages of the later steps (this iteration's barrier wait, edge_exchange, retires it).  (Behind the item's last row it reads the slot the tail's
 		// fills keep rewriting: one read per iteration, whatever the row.)
 		[[maybe_unused]] auto read_ahead = [&]() {
-			if (m + 1 < FILL + kRingRows) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitFill) : "memory");
+			if constexpr (!STEADY)
+				if (m + 1 < FILL + kRingRows) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitFill) : "memory");
 			ring_read_ahead<kWaitAhead, ((K + 1) % M) * SLOT, ((K + 1) % M) * SLOT + RB>(ring_trip, P[0].u0[(K + 1) % M], P[0].v0[(K + 1) % M]);
 		};
 #ifdef CRD_PROBE_NOMATH  // (probe build: the launch as a copy -- its memory traffic alone)
@@ -1073,13 +1165,19 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		// then has fewer operations in flight than the wait assumes, and its ring read can overtake the LDS-DMA fill of its slot.
 		if constexpr (FED >= FILL) {
 #if defined(CRD_PROBE_BRANCHY_STORES)  // (probe build: round 5's form, stores under the lanes' condition -- what the parked lanes cost; NOT safe, see above)
+			static_assert(!SROWS, "the probe stores through the row pointers: build it with -DCRD_NO_SCALAR_ROWS");
 			if (lane_stores) {
 				buffer_row_store<NT>(row_resource(out_row_u), xb, nu);
 				buffer_row_store<NT>(row_resource(out_row_v), xb, nv);
 			}
 #elif !defined(CRD_PROBE_NOSTORE)
-			buffer_row_store<NT>(row_resource(out_row_u), xb_store, nu);
-			buffer_row_store<NT>(row_resource(out_row_v), xb_store, nv);
+			if constexpr (SROWS) {
+				buffer_row_store<NT>(sr.out_u, xb_store, nu, sr.out_off);
+				buffer_row_store<NT>(sr.out_v, xb_store, nv, sr.out_off);
+			} else {
+				buffer_row_store<NT>(row_resource(out_row_u), xb_store, nu);
+				buffer_row_store<NT>(row_resource(out_row_v), xb_store, nv);
+			}
 #else
 			if (a.nchunks < 0) {  // (never: keeps the arithmetic alive)
 				buffer_row_store<NT>(row_resource(out_row_u), xb_store, nu);
@@ -1087,8 +1185,12 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			}
 #endif
 		}
-		out_row_u += nx;
-		out_row_v += nx;
+		if constexpr (SROWS) {
+			sr.out_off += sr.pitch;
+		} else {
+			out_row_u += nx;
+			out_row_v += nx;
+		}
 		// (COOP) what the block's wavefronts published during this iteration is complete beyond the barrier; the reads of what the next
 		// iteration needs of it go out at once and land while that iteration waits for its row
 		// (kReadAhead: ... and its wait retires the read of the next row, whose registers it names)
@@ -1099,18 +1201,38 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	for_sequence(  // the pipeline fills (a chunk has at least one row: FILL iterations and more)
 	    [&](auto i) {
 		    constexpr int I = decltype(i)::value;
-		    iteration(I, std::integral_constant<int, I % M>{}, i);
+		    iteration(I, std::integral_constant<int, I % M>{}, i, std::false_type{});
 		    if constexpr (!AHEAD && I % M == M - 1) next_trip();  // (kReadAhead: the trip's last iteration moves on itself, in front of its read ahead)
 	    },
 	    std::make_integer_sequence<int, FILL>{});
 	m = FILL;
-	for (; m + M - 1 < niter; m += M) {
-		for_sequence([&](auto k) { iteration(m + decltype(k)::value, k, std::integral_constant<int, FILL>{}); }, std::make_integer_sequence<int, M>{});
-		if constexpr (!AHEAD) next_trip();
+	if constexpr (SROWS) {
+		// The first kRingRows iterations behind the fill, trip by trip as far as the item has them: m is a constant in each, and so is which
+		// wait its read ahead takes (kWaitFill while m + 1 < FILL + kRingRows).  The loop proper starts behind them.
+		bool whole = true;
+		for_sequence(
+		    [&](auto t) {
+			    constexpr int M0 = FILL + M * decltype(t)::value;
+			    whole = whole && M0 + M - 1 < niter;
+			    if (whole) {
+				    for_sequence([&](auto k) { iteration(M0 + decltype(k)::value, k, std::integral_constant<int, FILL>{}, std::false_type{}); }, std::make_integer_sequence<int, M>{});
+				    m = M0 + M;
+			    }
+		    },
+		    std::make_integer_sequence<int, kRingRows / M>{});
+		// (an item that ended inside those trips has fewer than M iterations left: the loop's condition is false for it)
+		for (; m + M - 1 < niter; m += M)
+			for_sequence([&](auto k) { iteration(m + decltype(k)::value, k, std::integral_constant<int, FILL>{}, std::true_type{}); }, std::make_integer_sequence<int, M>{});
+	} else {
+		for (; m + M - 1 < niter; m += M) {
+			for_sequence([&](auto k) { iteration(m + decltype(k)::value, k, std::integral_constant<int, FILL>{}, std::false_type{}); }, std::make_integer_sequence<int, M>{});
+			if constexpr (!AHEAD) next_trip();
+		}
 	}
+	// (the tail: up to M - 1 iterations, of an item of any length -- the wait of their read ahead is decided at run time)
 	for_sequence(
 	    [&](auto k) {
-		    if (m + decltype(k)::value < niter) iteration(m + decltype(k)::value, k, std::integral_constant<int, FILL>{});
+		    if (m + decltype(k)::value < niter) iteration(m + decltype(k)::value, k, std::integral_constant<int, FILL>{}, std::false_type{});
 	    },
 	    std::make_integer_sequence<int, M - 1>{});
 	// the fills still in flight write LDS: they must have landed before the wavefront ends and its LDS goes to the next workgroup
@@ -1381,6 +1503,9 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 	// Two steps per launch: plain steps only, and not the diffusion-only variant (no instantiation: that model is a plumbing case).
 	constexpr bool kCanTwoSteps = MODEL != kModelDiffusionOnly;
 	if (c.steps != 1 && (c.embed || !((c.steps == 2 && kCanTwoSteps) || (c.steps == 3 && kCanThreeSteps<Real, MODEL> && (kThreeStepCols<Real, MODEL> == 1 || d.nx % 2 == 0)))))
+		return hipErrorInvalidValue;
+	// (the kernels that address rows by 32-bit offsets into the plane: fused_steps_supported keeps such a launch from being asked for)
+	if (c.steps == 3 && kScalarRows<Real, MODEL, kThreeStepCols<Real, MODEL>, 3> && !fused_scalar_rows_addressable(d.nx, fused_addressed_rows(d), (long)sizeof(Real)))
 		return hipErrorInvalidValue;
 	// rows may extend into the ghost region (deep-halo steps), but the pipeline reads kStepHalo rows per step beyond them
 	if (!d.wrap && (row_begin < -(kGhost - c.steps * kStepHalo) || row_end > d.nyl + (kGhost - c.steps * kStepHalo))) return hipErrorInvalidValue;
@@ -1669,6 +1794,7 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 		const bool room_for_three = d.wrap || (row_begin >= -(kGhost - 3 * kStepHalo) && row_end <= d.nyl + (kGhost - 3 * kStepHalo));
 		const bool three_steps_ok = two_steps_ok && kCanThreeSteps<Real, MODEL> && (kThreeStepCols<Real, MODEL> == 1 || cols2_ok) && d.nyl >= 6 * kStepHalo &&
 		                            (d.wrap || sizeof(Real) == 4) && room_for_three &&
+		                            (!kScalarRows<Real, MODEL, kThreeStepCols<Real, MODEL>, 3> || fused_scalar_rows_addressable(d.nx, fused_addressed_rows(d), (long)sizeof(Real))) &&
 		                            !(sizeof(Real) == 4 && absorb12);  // (... or triples: single slabs, and in fp32 slabs of a run; fp32 without absorbing rows on)
 		float t_best[kCandidates];
 		bool live[kCandidates];

@@ -138,6 +138,17 @@ bool fused_plan_candidate(int index, int *chunk_mode, int *mapping, int *cols, i
 bool fused_two_steps_supported(const SlabDesc &d);
 bool fused_wide_supported(int precision, const SlabDesc &d, int want_steps);  // chunk mode 3 (eight wavefronts per block strip) runs its own kernel on this slab
 int fused_steps_supported(int precision, const SlabDesc &d, int want);  // steps per launch a plan that asks for `want` gets on this slab
+// The three-step fp64 block strip addresses a plane's rows by a 32-bit byte offset from the lowest row a launch can address
+// (crd_fused_impl.h: kScalarRows): the addressed span -- `rows` rows of nx reals, ghost rows included where the slab has them -- must
+// stay below 2^32 bytes minus one row (an offset is advanced by a row before it is wrapped or clamped).  Beyond that such a plan steps
+// pairs, whose addressing is 64-bit (fused_steps_supported).
+inline bool fused_scalar_rows_addressable(long nx, long rows, long real_bytes)
+{
+	if (nx < 1 || rows < 1 || real_bytes < 1) return false;
+	const unsigned long pitch = (unsigned long)nx * (unsigned long)real_bytes, limit = 1ul << 32;
+	return pitch < limit && (unsigned long)rows <= limit / pitch && (unsigned long)rows * pitch < limit - pitch;
+}
+long fused_addressed_rows(const SlabDesc &d);  // rows of a plane a launch can address: the slab's own, and its ghost rows unless phi wraps inside it
 int fused_max_items(const SlabDesc &d);
 
 // Layout adaptors between the AoS boundary layout (host precision: f64 or device precision) and SoA planes.

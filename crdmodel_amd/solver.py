@@ -690,6 +690,20 @@ def launch_plan_candidates(eight_wide=False):
         k += 1
 
 
+def steps_per_launch_on(model, precision, nx, nyl, steps_wanted, single_slab=True):
+    """crd_steps_per_launch_on: the steps per launch a plan asking for `steps_wanted` gets on a slab of nx x nyl points (no device needed)."""
+    rc = lib().crd_steps_per_launch_on(MODELS[model] if isinstance(model, str) else model,
+                                       {"f64": PRECISION_F64, "f32": PRECISION_F32}[precision] if isinstance(precision, str) else precision,
+                                       nx, nyl, 1 if single_slab else 0, steps_wanted)
+    check(min(rc, 0), "crd_steps_per_launch_on")
+    return rc
+
+
+def rows_addressable(nx, rows, real_bytes=8):
+    """crd_rows_addressable: `rows` rows of nx reals span less than 2^32 bytes minus one row (the three-step fp64 kernel's 32-bit row offsets)."""
+    return bool(lib().crd_rows_addressable(nx, rows, real_bytes))
+
+
 def plan_key(model, precision, plan):
     """Key of a launch plan in profiles/pmc_traffic.json / profiles/plan_stats.json: plan = (chunk_mode, mapping, columns, nt[, steps per
     launch]) or the dict Slab.launch_plan() returns."""

@@ -490,6 +490,13 @@ int crd_get_launch_geometry(crd_ctx *ctx, crd_launch_geometry *out);
  * columns_per_lane, nontemporal_stores and steps_per_launch of *out are set, the rest zero.  (tools/plan_sweep.py profiles every one of them;
  * tests/test_profiles.py checks that profiles/pmc_traffic.json has an entry for each.) */
 int crd_launch_plan_candidate(int index, crd_launch_plan *out);
+/* Steps per launch a plan that asks for `steps_wanted` (1..3) gets on a slab of nx x nyl points -- what crd_get_launch_plan reports as
+ * steps_per_launch for a context of that shape -- without a context or a device (single_slab: phi wraps inside the slab).  The
+ * three-step fp64 kernel addresses a plane's rows by 32-bit byte offsets: crd_rows_addressable says whether `rows` rows of nx reals
+ * (the slab's rows, and its ghost rows where it has them) fit -- rows x nx x real_bytes below 2^32 minus one row; beyond that such a
+ * plan steps pairs.  crd_steps_per_launch_on: CRD_EINVAL (negative) for arguments out of range.  No reference counterpart. */
+int crd_steps_per_launch_on(int model, int precision, int64_t nx, int64_t nyl, int single_slab, int steps_wanted);
+int crd_rows_addressable(int64_t nx, int64_t rows, int real_bytes);
 /* Use THIS plan (chunk mode 0..2, or 3 together with three steps per launch; mapping 0..2, columns per lane 1..2, non-temporal stores 0..1, steps per launch 1..3) for the fixed-step kernel instead of measuring one -- a plan
  * read back from an earlier context of the same shape on the same device (the measurement costs ~0.45 s per context at 8192^2), or
  * a profiling run in which every launch of the kernel should be the plan a previous run chose (`bench.py --launch-plan`).  A pinned
