@@ -19,10 +19,12 @@ SURFACE_TORUS, SURFACE_FLAT = 0, 1
 PRECISION_F64, PRECISION_F32 = 0, 1
 STEPPER_AUTO, STEPPER_STAGED, STEPPER_FUSED = 0, 1, 2
 ADAPT_RK43, ADAPT_ARKODE = 0, 1
+PART_FULL, PART_DIFFUSION, PART_REACTION = 0, 1, 2
 
 MODELS = {"fhn": MODEL_FHN, "goldbeter": MODEL_GOLDBETER}
 SURFACES = {"torus": SURFACE_TORUS, "flat": SURFACE_FLAT}
 STEPPERS = {"auto": STEPPER_AUTO, "staged": STEPPER_STAGED, "fused": STEPPER_FUSED}
+PARTS = {"full": PART_FULL, "diffusion": PART_DIFFUSION, "reaction": PART_REACTION}
 
 
 class Params(C.Structure):
@@ -181,6 +183,10 @@ _SIGNATURES = {
     "crd_host_free": (None, [_vp]),
     "crd_rhs_host": (C.c_int, [_vp, C.c_double, _vp, _vp]),
     "crd_rhs_device": (C.c_int, [_vp, C.c_double, _vp, _vp]),
+    "crd_rhs_part_host": (C.c_int, [_vp, C.c_double, C.c_int, _vp, _vp]),
+    "crd_rhs_part_device": (C.c_int, [_vp, C.c_double, C.c_int, _vp, _vp]),
+    "crd_jtimes_host": (C.c_int, [_vp, C.c_double, C.c_int, _vp, _vp, _vp]),
+    "crd_jtimes_device": (C.c_int, [_vp, C.c_double, C.c_int, _vp, _vp, _vp]),
     "crd_set_stepper": (C.c_int, [_vp, C.c_int]),
     "crd_step_rk4": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64]),
     "crd_synchronize": (C.c_int, [_vp]),
@@ -192,6 +198,10 @@ _SIGNATURES = {
     "crd_group_step_rk4_timed": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.c_double, C.c_int64]),
     "crd_group_rhs_device": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.POINTER(_vp), C.POINTER(_vp)]),
     "crd_group_rhs_host": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.POINTER(_vp), C.POINTER(_vp)]),
+    "crd_group_rhs_part_device": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.c_int, C.POINTER(_vp), C.POINTER(_vp)]),
+    "crd_group_rhs_part_host": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.c_int, C.POINTER(_vp), C.POINTER(_vp)]),
+    "crd_group_jtimes_device": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.c_int, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "crd_group_jtimes_host": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_double, C.c_int, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "crd_step_rk4_timed": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "crd_dominant_kernel_rows": (C.c_int, [_vp, C.POINTER(C.c_int64)]),

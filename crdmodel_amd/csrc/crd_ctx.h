@@ -118,6 +118,8 @@ struct crd_ctx {
 	void *cE = nullptr, *cWn = nullptr, *cP = nullptr, *brow = nullptr;
 	void *stage_in = nullptr, *stage_out = nullptr;  // AoS staging for the *_host entry points (lazy)
 	size_t stage_bytes = 0;
+	void *stage_v = nullptr;  // ... and for the direction v of crd_jtimes_host (lazy, crd_jacobian.cpp)
+	size_t stage_v_bytes = 0;
 	void *ghost_lo = nullptr, *ghost_hi = nullptr;   // var0 of rows -1 / nyl for the AoS RHS (multi-slab)
 	void *edge_lo = nullptr, *edge_hi = nullptr;     // var0 of rows 0 / nyl-1 packed from an AoS vector
 	// theta-blocks (d0 > 1): var0 of the columns beside the block (ghost) and of its own first / last column (edge), nyl reals each,

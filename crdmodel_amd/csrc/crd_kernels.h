@@ -53,6 +53,14 @@ struct StageCall {
 hipError_t launch_rhs_aos(int precision, const SlabDesc &d, int absorb, const void *y, void *ydot, const void *ghost_lo,
                           const void *ghost_hi, int row_begin, int row_end, hipStream_t s, const void *gcol_w = nullptr, const void *gcol_e = nullptr);
 
+// One part of f (CRD_PART_*: FULL launches launch_rhs_aos), and J(t, y) v for the same parts, on whole slabs of AoS device vectors
+// (crd_jacobian.hip).  ghost_lo / ghost_hi: var0 of rows -1 and nyl of the vector the stencil reads -- y for a part, v for J v --
+// ignored when d.wrap and by the reaction part.  theta-blocks (d.wrap_x = 0) are refused.
+hipError_t launch_rhs_part_aos(int precision, const SlabDesc &d, int part, int absorb, const void *y, void *ydot, const void *ghost_lo, const void *ghost_hi,
+                               hipStream_t s);
+hipError_t launch_jtimes_aos(int precision, const SlabDesc &d, int part, int absorb, const void *y, const void *v, void *jv, const void *ghost_lo,
+                             const void *ghost_hi, hipStream_t s);
+
 // One RK4 stage (or a bare RHS) on SoA planes, rows [row_begin, row_end) of the slab.
 hipError_t launch_stage(int precision, const SlabDesc &d, const StageCall &c, int row_begin, int row_end, hipStream_t s);
 const char *stage_kernel_name(int precision, int model);

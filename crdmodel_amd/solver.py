@@ -29,6 +29,10 @@ def make_params(model, surface, nx, surface_length, surface_width, diffusion, be
     return p
 
 
+def _part(part):
+    return capi.PARTS[part] if isinstance(part, str) else int(part)
+
+
 def grid_of(params):
     g = Grid()
     check(lib().crd_grid_from_params(C.byref(params), C.byref(g)), "crd_grid_from_params")
@@ -259,6 +263,25 @@ class Slab:
         assert ydot.shape == y.shape and ydot.dtype == y.dtype and ydot.flags["C_CONTIGUOUS"]
         self._check(lib().crd_rhs_host(self._h, t, y.ctypes.data, ydot.ctypes.data), "crd_rhs_host")
         return ydot
+
+    def _vector(self, y):
+        y = np.ascontiguousarray(y, dtype=self.dtype)
+        assert y.shape == (self.nyl, self.nx, 2), (y.shape, (self.nyl, self.nx, 2))
+        return y
+
+    def rhs_part(self, t, y, part):
+        """One part of f(t, y) = f_D + f_R for this slab's AoS vector: part "full", "diffusion" or "reaction" (or a CRD_PART_* value)."""
+        y = self._vector(y)
+        ydot = np.empty_like(y)
+        self._check(lib().crd_rhs_part_host(self._h, t, _part(part), y.ctypes.data, ydot.ctypes.data), "crd_rhs_part_host")
+        return ydot
+
+    def jtimes(self, t, y, v, part="full"):
+        """J_part(t, y) v: the action of the Jacobian of f, or of one part of it, on the direction v (laid out like y)."""
+        y, v = self._vector(y), self._vector(v)
+        jv = np.empty_like(y)
+        self._check(lib().crd_jtimes_host(self._h, t, _part(part), y.ctypes.data, v.ctypes.data, jv.ctypes.data), "crd_jtimes_host")
+        return jv
 
     # -- time stepping -----------------------------------------------------------------------------------------
     def set_stepper(self, stepper):
@@ -784,6 +807,27 @@ class LocalGroup:
         ins = (C.c_void_p * n)(*[q.ctypes.data for q in parts])
         out = (C.c_void_p * n)(*[q.ctypes.data for q in outs])
         check(lib().crd_group_rhs_host(self._arr, n, t, ins, out), "crd_group_rhs_host", self.slabs[0].handle)
+        return self._assemble(outs, outs[0].dtype)
+
+    def _split(self, y):
+        parts = [np.ascontiguousarray(y[s.js:s.je + 1, s.is_:s.ie + 1], dtype=s.dtype) for s in self.slabs]
+        return parts, (C.c_void_p * len(parts))(*[q.ctypes.data for q in parts])
+
+    def rhs_part(self, t, y, part):
+        """One part of f(t, y) on the whole grid (Slab.rhs_part), slab by slab with the halos of y exchanged between the slabs' vectors."""
+        n = len(self.slabs)
+        ys, ins = self._split(y)
+        outs, out = self._split(np.empty((self.grid.ny, self.grid.nx, 2), dtype=ys[0].dtype))
+        check(lib().crd_group_rhs_part_host(self._arr, n, t, _part(part), ins, out), "crd_group_rhs_part_host", self.slabs[0].handle)
+        return self._assemble(outs, outs[0].dtype)
+
+    def jtimes(self, t, y, v, part="full"):
+        """J_part(t, y) v on the whole grid (Slab.jtimes): the halos exchanged are those of v."""
+        n = len(self.slabs)
+        ys, ins = self._split(y)
+        vs, vins = self._split(v)
+        outs, out = self._split(np.empty((self.grid.ny, self.grid.nx, 2), dtype=ys[0].dtype))
+        check(lib().crd_group_jtimes_host(self._arr, n, t, _part(part), ins, vins, out), "crd_group_jtimes_host", self.slabs[0].handle)
         return self._assemble(outs, outs[0].dtype)
 
     def step_rk4(self, t0, dt, nsteps):

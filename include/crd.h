@@ -288,6 +288,29 @@ void crd_host_free(void *p);
 int crd_rhs_host(crd_ctx *ctx, double t, const void *y_aos, void *ydot_aos);
 int crd_rhs_device(crd_ctx *ctx, double t, const void *y_aos_dev, void *ydot_aos_dev);
 
+/* The rest of what an integrator asks of a problem: f split into its diffusion and its reaction part, and the action of the
+ * Jacobian on a vector -- ARKode's implicit slot `fi` and its Jacobian-times-vector callback, both of which the reference leaves
+ * empty (ARKodeInit(arkode_mem, f, NULL, T0, y), src/FHNmodel_torus.cpp:362; arkode_pcg.h included at :51 and never used).
+ * Vectors are in the layout of crd_rhs_*: AoS [var0, var1], theta fastest, the local slab only, the context's precision.
+ *   f = f_D + f_R.  CRD_PART_FULL: f itself; crd_rhs_part_* then launches what crd_rhs_* launches and gives its bits.
+ *   CRD_PART_DIFFUSION: the operator alone, dvar1 = +0.0 (the bits of a diffusion-only Goldbeter context's f on the same geometry).
+ *   CRD_PART_REACTION: the kinetics alone (zeros for Goldbeter with just_diffusion); on a uniform state it has the bits of f.
+ *   crd_jtimes_*: jv = J_part(t, y) v.  J_D does not depend on y: J_D v is f_D evaluated on v, bit for bit.  J_R is the pointwise
+ *   2x2 block, FHN [[3 - 3u^2, -1], [EPSILON, 0]], Goldbeter [[-w_z - k, -w_y + kf], [w_z, w_y - kf]] with w = v2(z) - v3(z, y).
+ * Absorbing rows: while t < t_boundary (strictly, as in f) global rows 0 and ny - 1 are zero in every part of f and are zero rows
+ * of every part of J, on the slab that owns them.  A Goldbeter context with just_diffusion has no absorbing rows in f
+ * (src/GoldbeterModel_torus.cpp:668 skips them with the kinetics), so it has none here either.
+ * Halos: DIFFUSION and FULL of crd_rhs_part_* exchange var0 of y's edge rows as crd_rhs_* does; DIFFUSION and FULL of crd_jtimes_*
+ * exchange var0 of V's edge rows and nothing of y.  Those calls are collective like crd_rhs_*: RCCL contexts through the plain entry
+ * points, LOCAL groups through the crd_group_* ones.  REACTION exchanges nothing and is NOT collective: any context may call it alone,
+ * through either entry point.  theta-block contexts (crd_create_block with d0 > 1) are refused with CRD_ESTATE; a part that is none
+ * of the three returns CRD_EINVAL.  The *_host forms stage through device memory (no banded pipeline). */
+enum { CRD_PART_FULL = 0, CRD_PART_DIFFUSION = 1, CRD_PART_REACTION = 2 };
+int crd_rhs_part_device(crd_ctx *ctx, double t, int part, const void *y_aos_dev, void *ydot_aos_dev);
+int crd_rhs_part_host(crd_ctx *ctx, double t, int part, const void *y_aos, void *ydot_aos);
+int crd_jtimes_device(crd_ctx *ctx, double t, int part, const void *y_aos_dev, const void *v_aos_dev, void *jv_aos_dev);
+int crd_jtimes_host(crd_ctx *ctx, double t, int part, const void *y_aos, const void *v_aos, void *jv_aos);
+
 /* Fast path that never leaves the GPU: nsteps classical RK4 steps of size dt on the context's resident state,
  * stage k of step n evaluated at t0 + n dt + c_k dt (replaces the ARKode(...) call, src/FHNmodel_torus.cpp:423).
  * Asynchronous; crd_synchronize() waits.  With several slabs every context of the run must make the same call: stepping is
@@ -389,6 +412,12 @@ int crd_group_step_rk4_timed(crd_ctx *const *ctxs, int n, double t0, double dt, 
 int crd_group_set_threads(crd_ctx *const *ctxs, int n, int threads);
 int crd_group_rhs_device(crd_ctx *const *ctxs, int n, double t, const void *const *y_aos_dev, void *const *ydot_aos_dev);
 int crd_group_rhs_host(crd_ctx *const *ctxs, int n, double t, const void *const *y_aos, void *const *ydot_aos); /* host vectors, device precision */
+/* ... and the parts of f and J v (crd_rhs_part_* / crd_jtimes_* above) on every slab of a LOCAL group */
+int crd_group_rhs_part_device(crd_ctx *const *ctxs, int n, double t, int part, const void *const *y_aos_dev, void *const *ydot_aos_dev);
+int crd_group_rhs_part_host(crd_ctx *const *ctxs, int n, double t, int part, const void *const *y_aos, void *const *ydot_aos);
+int crd_group_jtimes_device(crd_ctx *const *ctxs, int n, double t, int part, const void *const *y_aos_dev, const void *const *v_aos_dev,
+                            void *const *jv_aos_dev);
+int crd_group_jtimes_host(crd_ctx *const *ctxs, int n, double t, int part, const void *const *y_aos, const void *const *v_aos, void *const *jv_aos);
 
 /* Same as crd_step_rk4 but bracketed by HIP events on the context's compute stream; blocks until done.
  * ms_total: device time of the whole batch; kernel_ms: average duration of one launch of the dominant kernel

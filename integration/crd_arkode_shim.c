@@ -11,6 +11,42 @@ int crd_arkode_f(realtype t, N_Vector y, N_Vector ydot, void *user_data)
 	return crd_rhs_host(ctx, (double)t, NV_DATA_P(y), NV_DATA_P(ydot)) == CRD_OK ? 0 : -1;
 }
 
+/* the reference's one f split for ARKodeInit(mem, fe, fi, T0, y): fe + fi = f */
+int crd_arkode_fe(realtype t, N_Vector y, N_Vector ydot, void *user_data)
+{
+	crd_ctx *ctx = (crd_ctx *)user_data;
+	if (!ctx || !y || !ydot) return -1;
+	return crd_rhs_part_host(ctx, (double)t, CRD_PART_REACTION, NV_DATA_P(y), NV_DATA_P(ydot)) == CRD_OK ? 0 : -1;
+}
+
+int crd_arkode_fi(realtype t, N_Vector y, N_Vector ydot, void *user_data)
+{
+	crd_ctx *ctx = (crd_ctx *)user_data;
+	if (!ctx || !y || !ydot) return -1;
+	return crd_rhs_part_host(ctx, (double)t, CRD_PART_DIFFUSION, NV_DATA_P(y), NV_DATA_P(ydot)) == CRD_OK ? 0 : -1;
+}
+
+static int jtimes_part(int part, N_Vector v, N_Vector Jv, realtype t, N_Vector y, void *user_data)
+{
+	crd_ctx *ctx = (crd_ctx *)user_data;
+	if (!ctx || !v || !Jv || !y) return -1;
+	return crd_jtimes_host(ctx, (double)t, part, NV_DATA_P(y), NV_DATA_P(v), NV_DATA_P(Jv)) == CRD_OK ? 0 : -1;
+}
+
+int crd_arkode_jtimes_fi(N_Vector v, N_Vector Jv, realtype t, N_Vector y, N_Vector fy, void *user_data, N_Vector tmp)
+{
+	(void)fy;
+	(void)tmp;
+	return jtimes_part(CRD_PART_DIFFUSION, v, Jv, t, y, user_data);
+}
+
+int crd_arkode_jtimes(N_Vector v, N_Vector Jv, realtype t, N_Vector y, N_Vector fy, void *user_data, N_Vector tmp)
+{
+	(void)fy;
+	(void)tmp;
+	return jtimes_part(CRD_PART_FULL, v, Jv, t, y, user_data);
+}
+
 int crd_arkode_attach(const crd_run_config *cfg, int rank, int nprocs, int device, crd_bcast_fn bcast, void *comm, crd_ctx **out)
 {
 	if (!cfg || !out) return CRD_EINVAL;

@@ -33,6 +33,24 @@ extern "C" {
  * Returns 0, or -1 as the reference does when its Exchange fails (:522) -- unrecoverable for ARKode. */
 int crd_arkode_f(realtype t, N_Vector y, N_Vector ydot, void *user_data);
 
+/* The same right-hand side split for an IMEX or implicit ARKode: fe = the kinetics (crd_rhs_part_host, CRD_PART_REACTION), fi = the
+ * diffusion operator (CRD_PART_DIFFUSION); fe + fi = f up to rounding.  The reference passes NULL for fi (src/FHNmodel_torus.cpp:362):
+ *
+ *     ARKodeInit(arkode_mem, crd_arkode_fe, crd_arkode_fi, T0, y);
+ *     ARKSpgmr(arkode_mem, PREC_NONE, 0);
+ *     ARKSpilsSetJacTimesVecFn(arkode_mem, crd_arkode_jtimes_fi);
+ *
+ * crd_arkode_jtimes_fi is J_fi(t, y) v, the Jacobian of the implicit part alone, which is what an IMEX ARKode's Newton iteration
+ * linearises (it equals fi applied to v: the operator is linear); crd_arkode_jtimes is the whole f's, for a fully implicit run
+ * (ARKodeInit(arkode_mem, NULL, crd_arkode_f, T0, y)).  Both take the arguments ARKode 1.x documents for ARKSpilsJacTimesVecFn,
+ * (v, Jv, t, y, fy, user_data, tmp); fy and tmp are not used.  UNVERIFIED: the signature is taken from SUNDIALS' documentation, no
+ * SUNDIALS build has compiled or called these callbacks (tests drive them through the test double's N_Vector).  Return 0 / -1 as
+ * crd_arkode_f.  INTEGRATION.md section 1b has the surrounding lines and why GMRES, not the PCG solver the reference includes. */
+int crd_arkode_fe(realtype t, N_Vector y, N_Vector ydot, void *user_data);
+int crd_arkode_fi(realtype t, N_Vector y, N_Vector ydot, void *user_data);
+int crd_arkode_jtimes_fi(N_Vector v, N_Vector Jv, realtype t, N_Vector y, N_Vector fy, void *user_data, N_Vector tmp);
+int crd_arkode_jtimes(N_Vector v, N_Vector Jv, realtype t, N_Vector y, N_Vector fy, void *user_data, N_Vector tmp);
+
 /* Creates the rank's context from the run configuration (crd_config_load_ini of the same ini file main() reads, :158-174) and,
  * for nprocs > 1, joins the RCCL ring: `bcast(buf, bytes, comm)` is any broadcast of `bytes` (129: a status byte + the 128-byte
  * id) from rank 0 -- with MPI, `MPI_Bcast(buf, bytes, MPI_BYTE, 0, comm)` wrapped in a two-line function.  Every rank always
