@@ -112,6 +112,34 @@ to 2048 items on 4 slabs, 1.3e-15 of dsm.  Negligible beside 32 u in fp32; of it
 
     sigma = (N_ACC u + K_RED 2^-53) / 2.
 
+One RK4(3) attempt (CRD_ADAPT_RK43, fused_item<..., EMBED = 1, ...>)
+------------------------------------------------------------------
+The propagated solution is classical RK4 formed by the running accumulators of the plain step (ACC_U / ACC_V stay live beside the
+fifth stage): reference and per-point bound B are "One RK4 step"'s, K_ACC included.  The fifth stage is k5 = f(t + h, y_new) on the
+y_new the lane has just formed (U4 / V4 hold a window of it, K4U / K4V hold k4 itself), its absorbing flag the host's absorb[3],
+decided at t + h like stage 4's (crd_steppers.cpp: launch_attempt).  The device's y_new is within B of the reference's, so
+
+    e5 = stage_error(t + h, y_new; dY = B)
+
+-- the construction f_new_bound uses for the interpolant's f_{n+1}.  The estimate.  Reference: err = h/6 (k4 - k5) (the pair's
+third-order weights are (1/6, 1/3, 1/3, 0, 1/6): y_new - yhat).  Device: `h6 * (K4U - du) / wu`:
+
+    d_err = h/6 (e4 + e5) + K_EST43 u h/6 (|k4| + |k5|),
+
+K_EST43 = 3: the rounded h6 = fl(h / 6), the subtraction, the product (each relative to h/6 |k4 - k5| <= h/6 (|k4| + |k5|)); the
+quotient is K_W's.  No K_Y term: nothing here is formed from stage values.  k4 - k5 = O(h) k, so the estimate is a third-order
+quantity in h |lambda|, orders above the rounding floor the Zonneveld estimate has in fp32, and the norm bound is accordingly a
+smaller fraction of the norm: 5e-6 ... 1e-4 in fp32, 1e-14 ... 4e-13 in fp64 on the grids of the tests.
+
+The norm: as above, delta = w d_err + K_W u |err| w, |dsm_gpu - dsm_ref| <= D + sigma (dsm_ref + D), with the same reduction
+(K_RED).  Only N_ACC differs.  An EMBED = 1 launch takes the launch plan the context keeps for it, plan_embed; on a grid of 2^20
+points or more that plan is measured on the first launch (autotune is on by default), and two of its chunk modes make chunks
+taller than 32 rows: 64 rows (mode 2) and "one round" (mode 1), stretched to at most 96 (fused_chunk_rows: `need <= 96`).  A lane
+can therefore add 96 rows' squares, both fields: N_ACC_RK43 = 192, sigma = 96 u + 12 2^-53 (5.7e-6 in fp32).  The grids of the
+tests are below 2^20 points and get 4- to 32-row chunks; the bound is stated for what the path can do, not for what the tests meet.
+(plan_arkode is measured by the same code, so the Zonneveld section's "32 at most" holds for unmeasured plans only -- every grid
+its gates run on; its N_ACC is left as it is, erk_attempt_bound's results being pinned by those gates.)
+
 Dense output (Hermite, ARK_NORMAL)
 ----------------------------------
 theta = (tout - t_n) / h in (0, 1):  y(theta) = h00 y_n + h01 y_{n+1} + h (h10 f_n + h11 f_{n+1}) with the cubic Hermite basis
@@ -148,6 +176,14 @@ K_W = 4.0         # the weight's three roundings and the quotient's
 N_ACC = 64        # additions into a lane's sum of squares in the kernel's precision: 32 rows at most, both fields
 K_RED = 24.0      # fp64 roundings between a lane's sum and dsm
 K_HERM = 6.0      # the interpolant's four roundings + two on a coefficient
+# The RK4(3) attempt's constants: counted in the docstring ("One RK4(3) attempt"), from crd_fused_impl.h: fused_item, EMBED = 1.
+# K_EST43: the roundings of `eu = h6 * (K4U[S5 & 1] - du) / wu` (and ev alike) on h/6 (k4 - k5), the quotient apart (that one is K_W's):
+# h6 = (Real)(dt / 6.0) rounded to the kernel's precision (launch_fused_t), the subtraction k4 - k5, the product with h6.  K4U holds
+# k4 as stage 4 left it (`K4U[S4 & 1] = du`): no rounding of its own.  Three, none spare.
+K_EST43 = 3.0
+# N_ACC_RK43: additions into a lane's sum of squares, both fields, over the tallest chunk an EMBED = 1 launch can take under plan_embed:
+# 96 rows (fused_chunk_rows: a measured plan's one-round chunks, `need <= 96`; its 64-row mode and the plain 32 lie below).
+N_ACC_RK43 = 192
 KF, KK, V0, V1, VM2, VM3, K2, KR, KA, EPS = 1.0, 10.0, 1.0, 7.3, 65.0, 500.0, 1.0, 2.0, 0.9, cn.EPSILON
 
 
@@ -304,7 +340,7 @@ def rk4_step_bound(problem, t, dt, y, precision, j0=0):
 
 
 class AttemptBound:
-    """erk_attempt_bound's result.  state: (ref, bound_u, bound_v) of y_new, as rk4_step_bound's (for check()); err: the reference's
+    """erk_attempt_bound's and rk43_attempt_bound's result.  state: (ref, bound_u, bound_v) of y_new, as rk4_step_bound's (for check()); err: the reference's
     per-point estimate (rows, nx, 2) with its per-point bounds err_bound_u / err_bound_v (not weighted); dsm, dsm_bound: the
     reference's WRMS norm and the bound on |dsm_device - dsm|; f_new_bound(): see hermite_bound."""
 
@@ -340,21 +376,31 @@ def erk_attempt_bound(problem, t, h, y, precision, rtol, atol, j0=0):
     # beta as exact rationals of the reference's dtype: 2/3 and 16/3 are not binary fractions
     bw = [rd(2) / rd(3), rd(-2), rd(-2), rd(-2), rd(16) / rd(3)]
     assert all(abs(float(a) - b) <= 1e-15 for a, b in zip(bw, beta)), (bw, beta)
-    err, d_err, delta2, e2 = [], [], 0.0, rd(0)
+    err, d_err = [], []
     for f in (0, 1):
-        er = hh * sum(b * k[f] for b, k in zip(bw, ks5))
-        de = hf * sum(abs(b) * e[f] for b, e in zip(beta, es5)) + K_ERR * un * hf * sum(abs(b) * k[f] for b, k in zip(beta, ak)) + K_Y * un * a0[f]
-        w = 1.0 / (rtol * a0[f] + atol)
-        delta = w * de + K_W * un * np.abs(er.astype(np.float64)) * w
+        err.append(hh * sum(b * k[f] for b, k in zip(bw, ks5)))
+        d_err.append(hf * sum(abs(b) * e[f] for b, e in zip(beta, es5)) + K_ERR * un * hf * sum(abs(b) * k[f] for b, k in zip(beta, ak)) + K_Y * un * a0[f])
+    return _attempt_result(P, precision, j0, y0, ref, bounds, err, d_err, rtol, atol, N_ACC)
+
+
+def _attempt_result(P, precision, j0, y0, ref, bounds, err, d_err, rtol, atol, n_acc):
+    """The AttemptBound of an embedded pair from its per-point parts: y0 = (u, v) in the reference's dtype, the step's reference and
+    bounds, err / d_err the reference's estimate and the bound on the device's per field; n_acc: additions into a lane's sum of
+    squares in the kernel's precision.  The norm and its bound are the module docstring's ("The norm")."""
+    rd = y0[0].dtype.type
+    un = UNIT[precision]
+    delta2, e2 = 0.0, rd(0)
+    for f in (0, 1):
+        a0 = np.abs(y0[f].astype(np.float64))
+        w = 1.0 / (rtol * a0 + atol)
+        delta = w * d_err[f] + K_W * un * np.abs(err[f].astype(np.float64)) * w
         wr = rd(1) / (rd(rtol) * np.abs(y0[f]) + rd(atol))
-        e2 = e2 + np.sum((er * wr) ** 2)
+        e2 = e2 + np.sum((err[f] * wr) ** 2)
         delta2 += float(np.sum(delta * delta))
-        err.append(er)
-        d_err.append(de)
-    n = 2 * y0u.size
+    n = 2 * y0[0].size
     dsm = float(np.sqrt(e2 / n))
     D = float(np.sqrt(delta2 / n))
-    sigma = 0.5 * (N_ACC * un + K_RED * UNIT["f64"])
+    sigma = 0.5 * (n_acc * un + K_RED * UNIT["f64"])
     dsm_bound = D + sigma * (dsm + D)
 
     def f_new_bound(t_new):
@@ -365,6 +411,31 @@ def erk_attempt_bound(problem, t, h, y, precision, rtol, atol, j0=0):
 
     return AttemptBound(state=(ref, bounds[0], bounds[1]), err=np.stack(err, axis=-1), err_bound_u=d_err[0], err_bound_v=d_err[1], dsm=dsm,
                         dsm_bound=dsm_bound, rms_delta=D, sigma=sigma, f_new_bound=f_new_bound)
+
+
+def rk43_attempt_bound(problem, t, h, y, precision, rtol, atol, j0=0):
+    """One RK4(3) attempt of size h from (t, y) (CRD_ADAPT_RK43; fused_item<..., EMBED = 1, ...>): as erk_attempt_bound, an AttemptBound
+    with the propagated state's reference and per-point bound, the reference's estimate err = h/6 (k4 - k5), k5 = f(t + h, y_new), the
+    per-point bound on the device's, and the WRMS norm with the bound on |dsm_device - dsm_ref| (module docstring, "One RK4(3)
+    attempt").  The lane's sum is charged N_ACC_RK43 = 192 additions, not N_ACC = 64: an EMBED = 1 launch goes out under the context's
+    plan_embed, which on grids of 2^20 points and more may be measured, and a measured plan's one-round chunks are up to 96 rows
+    high (crd_fused_impl.h: fused_chunk_rows) -- 192 additions of both fields' squares per lane."""
+    P = _Problem(problem)
+    rd = reference_dtype(precision)
+    un = UNIT[precision]
+    y0 = _split(y, rd)
+    ks, es, ref, bounds = _rk4_stages(P, t, h, y0[0], y0[1], precision, j0)
+    hf = float(h)
+    t5 = t + hf
+    k5 = P.rhs(t5, ref[..., 0], ref[..., 1], rd, j0)
+    e5 = P.stage_error(precision, t5, ref[..., 0], ref[..., 1], j0, bounds[0], bounds[1])  # (f_new_bound's construction: the device's y_new is within B)
+    h6r, h6 = rd(h) / rd(6), hf / 6.0
+    err, d_err = [], []
+    for f in (0, 1):
+        k4 = ks[3][f]
+        err.append(h6r * (k4 - k5[f]))
+        d_err.append(h6 * (es[3][f] + e5[f]) + K_EST43 * un * h6 * (np.abs(k4.astype(np.float64)) + np.abs(k5[f].astype(np.float64))))
+    return _attempt_result(P, precision, j0, y0, ref, bounds, err, d_err, rtol, atol, N_ACC_RK43)
 
 
 def hermite_bound(problem, t, h, theta, y, precision, attempt, j0=0):

@@ -339,13 +339,13 @@ def attempt_state(op, seed, R=np.float64):
     return y.astype(R)
 
 
-def attempt_bound(op, t, h, y, precision):
+def attempt_bound(op, t, h, y, precision, bound=eb.erk_attempt_bound):
     """(tol, erk_attempt_bound) with rtol = atol = tol scaled on the REFERENCE so that its norm is ATTEMPT_DSM (the norm is
-    proportional to 1 / tol when both scale together), asserted to lie in [1e-3, 0.5]."""
-    first = eb.erk_attempt_bound(op, t, h, y, precision, 1e-4, 1e-4)
+    proportional to 1 / tol when both scale together), asserted to lie in [1e-3, 0.5].  bound: eb.rk43_attempt_bound for the RK4(3) pair."""
+    first = bound(op, t, h, y, precision, 1e-4, 1e-4)
     assert np.isfinite(first.dsm) and first.dsm > 0.0, first.dsm
     tol = float(np.float32(1e-4 * first.dsm / ATTEMPT_DSM))  # (a float32 value: the same number in both kernels' precisions ... and in print)
-    ab = eb.erk_attempt_bound(op, t, h, y, precision, tol, tol)
+    ab = bound(op, t, h, y, precision, tol, tol)
     assert 1e-3 <= ab.dsm <= 0.5, (tol, ab.dsm)
     return tol, ab
 
@@ -514,5 +514,190 @@ def test_attempt_bound_on_a_band_is_the_whole_grids():
     for j0 in (-7, 20):
         rows = np.arange(j0, j0 + 20) % 48
         band = eb.erk_attempt_bound(op, 0.99, 0.02, y[rows], "f32", 1e-3, 1e-3, j0=j0 % 48)
+        for a, b in zip(band.state + (band.err, band.err_bound_u, band.err_bound_v), whole.state + (whole.err, whole.err_bound_u, whole.err_bound_v)):
+            assert np.allclose(a[5:-5].astype(np.float64), b[rows[5:-5]].astype(np.float64), rtol=1e-9, atol=0)
+
+
+# ---- one RK4(3) attempt (CRD_ADAPT_RK43, EMBED = 1): restatements, honest, powerful ------------------------------------------------
+def kernel_order_rk43_attempt(op, t, h, y, R, rtol, atol, chunk=4, mutant=None, at=None):
+    """fused_item<..., EMBED = 1, ...> in precision R, in its order (crd_fused_impl.h): the staged running accumulators of
+    kernel_order_step, k5 = f(t + h, y_new) with stage 4's absorbing flag, e = h6 * (k4 - k5) / fma(rtol, |y0|, atol), a lane's sum of
+    squares in R over its chunk's rows (both fields), everything after that in double.  Returns (y_new, err, dsm); err is the
+    estimate before the weight, h6 * (k4 - k5).  mutant (at: its column or row):
+      "stale"   stage 5 of column `at` (a strip's last) reads its east neighbour from y3 instead of y_new
+      "twice"   column `at` (nx - 1) is counted twice
+      "row"     row `at` (a chunk's first) is not counted
+      "time"    stage 5's absorbing flag is decided at t + 3/4 h
+      "third"   h / 3 in place of h / 6"""
+    fma = _fma(R)
+    f = lambda ts, z: kernel_order_rhs(op, ts, z, R)  # noqa: E731
+    h1, h2, h3, h6 = R(h), R(0.5 * h), R(h / 3.0), R(h / 6.0)
+    y0 = y.astype(R)
+    k = f(t, y0)
+    acc = fma(h6, k, y0)
+    k = f(t + 0.5 * h, fma(h2, k, y0))
+    acc = fma(h3, k, acc)
+    k = f(t + 0.5 * h, fma(h2, k, y0))
+    acc = fma(h3, k, acc)
+    y3 = fma(h1, k, y0)
+    k4 = f(t + h, y3)
+    ynew = fma(h6, k4, acc)
+    k5 = f(t + (0.75 if mutant == "time" else 1.0) * h, ynew)
+    if mutant == "stale":
+        zs = ynew.copy()
+        zs[:, (at + 1) % op.nx] = y3[:, (at + 1) % op.nx]
+        k5[:, at] = f(t + h, zs)[:, at]
+    err = (R(h / 3.0) if mutant == "third" else h6) * (k4 - k5)
+    e = err / fma(R(rtol), np.abs(y0), R(atol))
+    rows, nx = y0.shape[:2]
+    total = 0.0
+    for j0 in range(0, rows, chunk):
+        acc = np.zeros(nx, dtype=R)
+        for j in range(j0, min(j0 + chunk, rows)):
+            if mutant == "row" and j == at:
+                continue
+            acc = fma(e[j, :, 0], e[j, :, 0], fma(e[j, :, 1], e[j, :, 1], acc))
+        total += float(np.sum(acc.astype(np.float64)))
+        if mutant == "twice":
+            total += float(acc[at])
+    return ynew, err, float(np.sqrt(total / (2 * rows * nx)))
+
+
+def reference_order_rk43_attempt(op, t, h, y, rtol, atol):
+    """The pair in the reference's order around the float32 restatement of the reference's f: the oracle's stage inputs
+    y + (c h) k, y + h/6 (k1 + 2 k2 + 2 k3 + k4), err = h/6 (k4 - k5), the WRMS norm, all in float32."""
+    P, g = _float32_problem(op)
+    f = lambda ts, z: np.stack(cn.rhs(P.model, P.surface, g, op.diff, ts, z[..., 0], z[..., 1], dtype=np.float32, **P.kw), axis=-1)  # noqa: E731
+    f32 = np.float32
+    h32 = f32(h)
+    k1 = f(t, y)
+    k2 = f(t + 0.5 * h, y + (f32(0.5) * h32) * k1)
+    k3 = f(t + 0.5 * h, y + (f32(0.5) * h32) * k2)
+    k4 = f(t + h, y + h32 * k3)
+    ynew = y + (h32 / f32(6)) * (k1 + f32(2) * k2 + f32(2) * k3 + k4)
+    err = (h32 / f32(6)) * (k4 - f(t + h, ynew))
+    e = err / (f32(rtol) * np.abs(y) + f32(atol))
+    return ynew, err, float(np.sqrt(np.sum(e * e, dtype=np.float32) / f32(e.size)))
+
+
+def rk43_bound(op, t, h, y, precision):
+    return attempt_bound(op, t, h, y, precision, eb.rk43_attempt_bound)
+
+
+@pytest.mark.parametrize("case", ATTEMPT_CONFIGS, ids=[c[0] for c in ATTEMPT_CONFIGS])
+def test_rk43_restatements_stay_inside_the_state_estimate_and_norm_bounds(case):
+    """Honest: the RK4(3) attempt in the kernel's order (fp32 and fp64) and in the reference's (fp32, torus) against
+    rk43_attempt_bound -- y_new and the estimate per point, the WRMS norm as a scalar -- with tBoundary off, between t + 3/4 h and
+    t + h (stages 4 and 5 free, a fifth flag taken at t + 3/4 h would absorb) and on for all five stages.  Worst ratios over these
+    cases, as printed ("Tolerances"): kernel order state 0.39, estimate 0.14 (Goldbeter; FHN 0.07), norm 0.029 (diffusion
+    only in fp64; every other case 0.007 at most); reference order 0.17, 0.14, 0.025.  K_EST43 = 3 is the count's and has nothing spare;
+    the estimate's ratios are small because h/6 (e4 + e5), the stages' worst case, is most of its bound."""
+    t = 0.3
+    worst = {}
+    for nx, ny in ATTEMPT_GRIDS:
+        h = attempt_step(attempt_problem(case, nx, ny))
+        for label, tb in attempt_placements(h):
+            op = attempt_problem(case, nx, ny, t_boundary=t + tb if tb else 0.0)
+            for precision, R in (("f64", np.float64), ("f32", np.float32)):
+                y = attempt_state(op, nx + ny, R)
+                tol, ab = rk43_bound(op, t, h, y, precision)
+                runs = [("kernel", kernel_order_rk43_attempt(op, t, h, y, R, tol, tol))]
+                if precision == "f32" and reference_order_applies(op):
+                    runs.append(("reference", reference_order_rk43_attempt(op, t, h, y, tol, tol)))
+                for order, (ynew, err, dsm) in runs:
+                    name = "RK4(3) %s order %s %s %dx%d tB %s" % (order, precision, case[0], nx, ny, label)
+                    ws = eb.check(name + " state", ynew, ab.state)
+                    we = eb.check(name + " estimate", err, (ab.err, ab.err_bound_u, ab.err_bound_v))
+                    rn = abs(dsm - ab.dsm) / ab.dsm_bound
+                    assert rn <= 1.0, (name, dsm, ab.dsm, ab.dsm_bound)
+                    key = (order, precision)
+                    worst[key] = tuple(max(a, b) for a, b in zip(worst.get(key, (0, 0, 0)), (worst_ratio(ws), worst_ratio(we), rn)))
+    for key, w in sorted(worst.items()):
+        print("BOUND RK4(3) attempt %s order %s %s: worst err/bound state %.3g, estimate %.3g, norm %.3g" % (key + (case[0],) + w))
+
+
+# the narrowest grid of the device gate, one strip edge, two, four strips and a ragged fifth, the largest grid of the gate
+RK43_MUTANT_GRIDS = [(5, 59), (55, 33), (109, 41), (217, 41), (1000, 65)]
+RK43_MUTANT_CONFIGS = [0, 3, 5]  # FHN, Goldbeter, diffusion only (torus)
+RK43_MUTANTS = ["stale", "twice", "row", "time", "third"]
+
+
+def rk43_mutant_claimed(mutant, precision, k, nx):
+    """Where the norm bound is claimed to see a mutant (the docstring of test_rk43_mutants_exceed_the_norm_bound: "Reach")."""
+    if mutant == "time" and ATTEMPT_CONFIGS[k][4].get("just_diffusion"):
+        return False  # a diffusion-only run has no absorbing rows: the mistake does not exist there
+    if precision == "f64":
+        return True
+    if mutant == "stale":
+        return nx >= (217 if ATTEMPT_CONFIGS[k][1] == co.GOLDBETER and not ATTEMPT_CONFIGS[k][4].get("just_diffusion") else 53)
+    if mutant == "row":
+        return k != 3
+    return True
+
+
+_rk43_mutant_cases = {}
+
+
+def rk43_mutant_case(nx, ny, precision, k, key):
+    """The unmutated attempt of configuration k, shared by its mutants: key "off" (absorbing rows off) or "time" (tBoundary between
+    t + 3/4 h and t + h)."""
+    q = (nx, ny, precision, k, key)
+    if q not in _rk43_mutant_cases:
+        R = np.float64 if precision == "f64" else np.float32
+        t = 0.3
+        h = attempt_step(attempt_problem(ATTEMPT_CONFIGS[k], nx, ny))
+        op = attempt_problem(ATTEMPT_CONFIGS[k], nx, ny, t_boundary=t + 0.8 * h if key == "time" else 0.0)
+        y = attempt_state(op, 11, R)
+        tol, ab = rk43_bound(op, t, h, y, precision)
+        _, _, dsm = kernel_order_rk43_attempt(op, t, h, y, R, tol, tol)
+        assert abs(dsm - ab.dsm) <= ab.dsm_bound
+        _rk43_mutant_cases[q] = (op, t, h, y, R, tol, ab)
+    return _rk43_mutant_cases[q]
+
+
+@pytest.mark.parametrize("nx,ny,precision,k,mutant", [
+    pytest.param(nx, ny, p, k, m, id="%dx%d-%s-%s-%s" % (nx, ny, p, ATTEMPT_CONFIGS[k][0], m))
+    for nx, ny in RK43_MUTANT_GRIDS for p in ("f64", "f32") for k in RK43_MUTANT_CONFIGS for m in RK43_MUTANTS if rk43_mutant_claimed(m, p, k, nx)])
+def test_rk43_mutants_exceed_the_norm_bound(nx, ny, precision, k, mutant):
+    """Powerful: five mistakes in the EMBED = 1 path that leave y_new inside its bound and move only the scalar err_last exceed the
+    norm bound by more than a factor 2 -- stage 5 reading a stale east neighbour (y3 for y_new) at a strip's last column, column
+    nx - 1 counted twice, a chunk's first row not counted, stage 5's absorbing flag decided at t + 3/4 h with tBoundary between that
+    and t + h, h / 3 for h / 6 -- on FHN, Goldbeter and diffusion only (torus), at the tolerances and the step (ATTEMPT_STEP x
+    crd.stable_dt) of the device gate.
+
+    Reach, measured with this step on 5 x 59, 53 x 26, 55 x 8, 55 x 33, 109 x 41, 163 x 47, 217 x 41, 271 x 38 and 1000 x 65.  The
+    estimate is a third-order quantity and the bound 1.4e-5 ... 4.5e-4 of the norm in fp32, 1e-14 ... 4e-13 in fp64.
+    fp64: every mutant, every configuration, every grid: factors from 1.3e3 (Goldbeter's row on 5 x 59) and otherwise above 1e6.
+    fp32, "twice", "time", "third": every configuration and every grid -- FHN 11 (55 x 8) ... 39 (5 x 59) and 25 (1000 x 65) for
+    "twice", above 160 for the other two; Goldbeter 887 ... 14.5 (271 x 38), 19 (1000 x 65); diffusion only 2.2 (5 x 59), 480
+    (55 x 33) ... 33 (1000 x 65).  A column's share falls with 1 / nx against a bound that does not: "twice" ends near nx = 10 000.
+    fp32, "stale": the stale value differs from the right one by the stage's own increment, and what stage 5 makes of it scales
+    with the diffusion's h |lambda|, which a coarse grid does not have.  FHN and diffusion only: seen from 53 columns on (FHN 3.9
+    at 55 x 33, 53 at 217 x 41, 8.7 at 1000 x 65; diffusion only 14 ... 259), not on 5 x 59 (0.1, 0.02).  Goldbeter, whose step the
+    reaction rate binds: seen from 217 columns on (3.3, 3.1, 9.2 at 1000 x 65), not below (0.005 ... 1.0).  Up to 54 columns there
+    is one strip and its last column's east neighbour is the periodic seam's.
+    fp32, "row": FHN 22 (55 x 33) ... 458 and diffusion only 26 (5 x 59) ... 2000 on every grid.  NOT claimed for Goldbeter: on this
+    state the five rows of the initial front carry the norm (8 to 10 times a row's fair share each; a row elsewhere 0.02 of it), and a
+    single uncounted row comes to anything between 0.008 (5 x 59) and 283 (1000 x 65) of the bound according to where it lies.
+    So the device gate's norm claim in fp32 is: double counting, the fifth flag's time and the factor at every width and configuration;
+    a stale strip-edge neighbour from 55 columns (Goldbeter: 217); an uncounted row on the FHN and diffusion-only configurations,
+    which run at every width beside Goldbeter's and share the row rule's code with them."""
+    op, t, h, y, R, tol, ab = rk43_mutant_case(nx, ny, precision, k, "time" if mutant == "time" else "off")
+    at = {"stale": min(ATTEMPT_VALID, op.nx) - 1, "twice": op.nx - 1, "row": 4 * (op.ny // 8)}.get(mutant)
+    ynew, _, dsm = kernel_order_rk43_attempt(op, t, h, y, R, tol, tol, mutant=mutant, at=at)
+    eb.check("RK4(3) mutant %s state" % mutant, ynew, ab.state)  # the solution cannot show it
+    ratio = abs(dsm - ab.dsm) / ab.dsm_bound
+    print("BOUND RK4(3) mutant %s %s %s %dx%d: |dsm - dsm_ref| / bound %.3g" % (mutant, precision, ATTEMPT_CONFIGS[k][0], op.nx, op.ny, ratio))
+    assert ratio > 2.0, ratio
+
+
+def test_rk43_attempt_bound_on_a_band_is_the_whole_grids():
+    """rk43_attempt_bound's per-point parts on a cropped band starting at global row j0, away from the band's edges."""
+    op = attempt_problem(ATTEMPT_CONFIGS[1], 64, 48, t_boundary=1.0)
+    y = attempt_state(op, 2)
+    whole = eb.rk43_attempt_bound(op, 0.99, 0.02, y, "f32", 1e-3, 1e-3)
+    for j0 in (-7, 20):
+        rows = np.arange(j0, j0 + 20) % 48
+        band = eb.rk43_attempt_bound(op, 0.99, 0.02, y[rows], "f32", 1e-3, 1e-3, j0=j0 % 48)
         for a, b in zip(band.state + (band.err, band.err_bound_u, band.err_bound_v), whole.state + (whole.err, whole.err_bound_u, whole.err_bound_v)):
             assert np.allclose(a[5:-5].astype(np.float64), b[rows[5:-5]].astype(np.float64), rtol=1e-9, atol=0)

@@ -9,6 +9,7 @@ fresh upload -- no launch-ahead, no dense output, the downloaded state is y_new 
 scaled on the REFERENCE so that its norm is 0.1 (test_error_bounds.attempt_bound), asserted in [1e-3, 0.5] before the device is
 touched.  Widths: the edges of one, two, three, four and five 54-column strips; rows: ragged, 8, and 33 (a last chunk of one row
 under the 4-row and the 8-row chunk rule alike).  Every failure names the case, and for the state the worst point.
+The RK4(3) attempt (CRD_ADAPT_RK43, EMBED = 1) and its dense output are gated the same way in tests/test_gpu_rk43_bounds.py.
 """
 import copy
 

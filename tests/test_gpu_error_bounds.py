@@ -4,7 +4,8 @@ The joint max-norm gate (conftest.rel_err) is dominated by the largest diffusion
 is held to |kernel - reference| <= K u S (+ the reciprocal's own term) for f(), and to the bound propagated through the four
 stages for one step.  The two- and three-step kernels, slab cuts and the ring are tied bit for bit to the one-step kernel by
 tests/test_gpu_parity.py, which carries these gates up to them.  Every failure names the case and the worst err/bound per field
-with its (row, column).
+with its (row, column).  The error-controlled attempts are gated per point and in norm in tests/test_gpu_attempt_bounds.py (Zonneveld
+5(3)4) and tests/test_gpu_rk43_bounds.py (the RK4(3) pair).
 """
 import numpy as np
 import pytest
