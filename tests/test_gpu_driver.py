@@ -160,6 +160,48 @@ def test_driver_block_layout_with_the_error_controlled_integrator(gpu_device, tm
         assert r.returncode == 1 and word in r.stderr, r.stderr
 
 
+def test_driver_block_contexts_wider_than_one_tile(gpu_device, tmp_path):
+    """`--block-contexts` on 260 x 40: 2 x 2 blocks of 130 columns, three 64-column tiles each, the middle one taking neither
+    ghost-strip branch of the tile loader (tests/test_theta_blocks_host.py: no block of 64 columns or fewer can see a per-tile slip
+    there, and the 16-column grid above is one of those).  The files of the four block contexts must be, byte for byte, those cut
+    out of ONE context's staged run: both are the staged RK4, and tests/test_gpu_theta_blocks.py holds their states to the same bits.
+    39 steps, outputs at 0.3, 0.6 and 0.9, the absorbing rows switching off (tBoundary = 0.4) inside the second interval."""
+    text = open(INI).read()
+    p = crd.load_ini(INI, "fhn", "torus").params
+    dt = 0.8 * crd.stable_dt(crd.make_params("fhn", "torus", 260, p.surface_length, p.surface_width, p.diffusion, p.beta, ny=p.ny, t_boundary=p.t_boundary))
+    for key, value in (("thetaMesh", "260"), ("tFinal", "0.9"), ("dt", repr(dt))):
+        text, n = re.subn(r"(?m)^%s = .*$" % key, "%s = %s" % (key, value), text)
+        assert n == 1, key
+    ini = tmp_path / "wide_blocks.ini"
+    ini.write_text(text)
+    cfg = crd.load_ini(ini, "fhn", "torus")
+    g = crd.grid_of(cfg.params)
+    steps = cfg.output_timestep * int(np.ceil(cfg.t_final / cfg.output_timestep / cfg.dt - 1e-12))
+    assert (g.nx, g.ny, cfg.dt, cfg.output_timestep) == (260, 40, dt, 3) and 24 <= steps <= 48
+    assert cfg.t_final / 3 < cfg.params.t_boundary < 2 * cfg.t_final / 3  # outputs 2 and 3 lie past tBoundary
+    runs = {"blocks": ["--gpus", "4", "--devices", "1", "--decomp", "2x2", "--block-contexts"], "whole": ["--gpus", "1", "--decomp", "2x2", "--stepper", "staged"]}
+    for name, argv in runs.items():
+        (tmp_path / name).mkdir()
+        r = subprocess.run([os.path.join(BIN, "crd_run"), "--model", "fhn", "--surface", "torus"] + argv + [str(ini)], cwd=tmp_path / name,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (name, r.stderr)
+        assert "nprocs = 4" in r.stdout and "nxl = 130" in r.stdout and "nyl = 20" in r.stdout and ("rate: %d steps" % steps) in r.stdout, r.stdout
+        for rank, (c0, c1) in enumerate([(0, 0), (0, 1), (1, 0), (1, 1)]):
+            hdr = open(tmp_path / name / ("FHNmodel_torus_subdomain.%03d.txt" % rank)).read().split()
+            assert tuple(int(v) for v in hdr[:6]) == (260, 40) + crd.block_extents(260, 40, c0, 2, c1, 2), (name, rank)
+        assert not (tmp_path / name / "FHNmodel_torus_subdomain.004.txt").exists()
+    for var in ("u", "v"):
+        a, ma = load_like_the_plot_script(tmp_path / "blocks", "FHNmodel_torus", var)
+        b, mb = load_like_the_plot_script(tmp_path / "whole", "FHNmodel_torus", var)
+        assert ma == mb and (ma["nprocs"], ma["nt"]) == (4, 4) and a.shape == (4, 40, 260)
+        assert np.array_equal(a, b), (var, np.argwhere(a != b)[:4])
+        assert np.all(np.isfinite(a)) and np.abs(a[-1] - a[0]).max() > 0.1  # the wave moved
+    files = sorted(os.listdir(tmp_path / "blocks"))
+    assert files == sorted(os.listdir(tmp_path / "whole")) and len(files) == 12  # subdomain, u, v of four ranks
+    for f in files:
+        assert open(tmp_path / "blocks" / f, "rb").read() == open(tmp_path / "whole" / f, "rb").read(), f
+
+
 def test_driver_stops_when_any_slab_blows_up(gpu_device, tmp_path):
     """Round-2 advice: the blow-up guard must be sticky over the slabs -- a NaN confined to slab 0 of a two-slab run was
     overwritten by slab 1's finite maximum and the driver kept writing NaN frames.  A step six times the stability limit

@@ -5,7 +5,9 @@ is held to |kernel - reference| <= K u S (+ the reciprocal's own term) for f(), 
 stages for one step.  The two- and three-step kernels, slab cuts and the ring are tied bit for bit to the one-step kernel by
 tests/test_gpu_parity.py, which carries these gates up to them.  Every failure names the case and the worst err/bound per field
 with its (row, column).  The error-controlled attempts are gated per point and in norm in tests/test_gpu_attempt_bounds.py (Zonneveld
-5(3)4) and tests/test_gpu_rk43_bounds.py (the RK4(3) pair).
+5(3)4) and tests/test_gpu_rk43_bounds.py (the RK4(3) pair).  theta-block contexts (SlabDesc::wrap_x == 0: ghost-column strips for the
+row's wrap) are gated per point, f() and one staged step, in tests/test_gpu_theta_blocks.py, at block widths on both sides of one,
+two and three 64-column tiles.
 """
 import numpy as np
 import pytest
