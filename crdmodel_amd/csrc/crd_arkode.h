@@ -1,11 +1,14 @@
 // crd_arkode.h -- ARKode's step-size controller (CRD_ADAPT_ARKODE) and its per-step bookkeeping, restated from its documentation;
 // oracle/arkode_erk.py has the same rules with the same names, and the tests compare the two attempt by attempt.  Host code only,
 // shared by the single-context integrator (crd_steppers.cpp: integrate_adaptive_impl) and the ensemble's (crd_ensemble.cpp), so that
-// both take the same decisions from the same norms.  Not part of the ABI.
+// both take the same decisions from the same norms -- and, at the end, what both keep around the controller: the dense-output record,
+// the rotation of the state planes and their relabelling when a call ends.  Not part of the ABI.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <utility>
 
 #include "crd.h"
 
@@ -172,6 +175,73 @@ inline bool options_valid(const crd_adaptive_options &o, double t0, double tout)
 	return o.rtol >= 0.0 && o.atol >= 0.0 && o.rtol + o.atol > 0.0 && o.safety > 0.0 && o.bias > 0.0 && o.growth >= 1.0 && o.shrink > 0.0 && o.shrink < 1.0 &&
 	       o.max_steps >= 1 && o.h0 >= 0.0 && !std::isnan(o.h_max) && std::isfinite(t0) && std::isfinite(tout) && !(tout < t0) &&
 	       (o.method == CRD_ADAPT_RK43 || o.method == CRD_ADAPT_ARKODE);
+}
+
+// ---- Around the controller: what both error-controlled integrators (RK4(3) too) keep of a trajectory between and during calls ----
+
+// The state planes of a trajectory by role -- a context's plane[role], an ensemble member's role[]: Y the state handed back, SA / SB the
+// staged stepper's ping-pong, ACC its accumulator, OUT the third state plane of a dense output.
+enum Role { Y = 0, SA = 1, SB = 2, ACC = 3, OUT = 4, NPLANES = 5 };
+
+// Dense output (ARK_NORMAL): after a call that overshot tout, Y holds the interpolant at t_out, SA the integrator's own state y_{n+1}
+// at t_np1, OUT y_n at t_n, SB / ACC f(t_n, y_n) / f(t_{n+1}, y_{n+1}).
+struct Dense {
+	bool pending = false;
+	double t_out = 0.0, t_n = 0.0, t_np1 = 0.0;
+};
+// Whatever replaces the resident state (an upload, a fixed step) drops the finished step and the controller's memory with it.
+inline void drop(Dense &d, Memory &A) { d.pending = A.live = false; }
+// A call continues the previous one when it starts at the output time that one handed back and nothing has replaced the state since
+// (ARKode keeps its memory between ARKode() calls the same way); the ARKode-style controller also needs its own memory.
+inline bool resumes(const Dense &d, const Memory &A, double t0, bool arkode_method) { return d.pending && t0 == d.t_out && (!arkode_method || A.live); }
+// The cap on the step size: the caller's, the trajectory's own diffusion-stability bound (h_max = 0), or none (h_max < 0).
+inline double h_cap(const crd_adaptive_options &o, const crd_params &p) { return o.h_max > 0.0 ? o.h_max : (o.h_max == 0.0 ? crd_stable_dt(&p) : INFINITY); }
+
+// Three state planes -- Y, SA and, with dense output, OUT -- take turns as y_n (prev), y_{n+1} (cur) and the next attempt's target (spare).
+struct Rotation {
+	int cur = Y, spare = SA, third = OUT, prev = -1;  // a fresh state with dense output; third: a plane nothing has been stepped into yet
+
+	static Rotation fresh(bool dense) { return dense ? Rotation{} : Rotation{Y, SA, -1, -1}; }
+	// A resumed call steps on from the integrator's own state; y_n of the finished step and the interpolant handed back are free.
+	void resume() { cur = SA, spare = OUT, third = Y; }
+	// A resumed call whose tout lies inside the step already taken: that step again (nothing is stepped; the interpolant overwrites Y).
+	void reinterpolate() { prev = OUT, cur = SA, spare = Y, third = -1; }
+	// An accepted step into dst: the old state becomes y_n (kept for the interpolant), the old y_n / the untouched plane the next target.
+	void accept(int dst, bool dense)
+	{
+		spare = dense ? ahead() : cur;
+		if (dense && prev < 0) third = -1;
+		if (dense) prev = cur;
+		cur = dst;
+	}
+	int interpolant() const { return Y + SA + OUT - prev - cur; }  // the state plane that is neither y_n nor y_{n+1}
+	int ahead() const { return prev >= 0 ? prev : third; }         // where a step after the one being attempted may go before the verdict (-1: nowhere)
+};
+
+// A relabelling of a trajectory's planes at the end of a call: role r gets the storage that had role from[r].
+struct Relabel {
+	int from[NPLANES];
+	template <typename T>
+	void apply(T (&slot)[NPLANES]) const  // T: a plane's handle(s), trivially copyable (void *, void *[2])
+	{
+		T old[NPLANES];
+		std::memcpy(old, slot, sizeof old);
+		for (int r = 0; r < NPLANES; r++) std::memcpy(&slot[r], &old[from[r]], sizeof(T));
+	}
+};
+// The end of a call.  output: the step t_n -> t_np1 (r.prev -> r.cur) has reached or passed tout and the interpolant at tout is in
+// r.interpolant() -- Y <- that, SA <- y_{n+1}, OUT <- y_n, and the step is recorded for the next call.  Otherwise (no dense output, a
+// zero-length interval, a failure) the state reached is handed back: Y <-> r.cur, nothing to resume.
+inline Relabel end_of_call(const Rotation &r, bool output, Dense &d, double tout, double t_n, double t_np1)
+{
+	if (output) {
+		d = Dense{true, tout, t_n, t_np1};
+		return Relabel{{r.interpolant(), r.cur, SB, ACC, r.prev}};
+	}
+	d.pending = false;
+	Relabel p{{Y, SA, SB, ACC, OUT}};
+	std::swap(p.from[Y], p.from[r.cur]);
+	return p;
 }
 
 }  // namespace arkode

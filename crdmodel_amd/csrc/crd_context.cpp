@@ -465,9 +465,8 @@ int crd_state_upload(crd_ctx *c, const void *y, int host_is_f64)
 	if (int rc = set_device(c)) return rc;
 	const size_t bytes = 2 * (size_t)c->nx * (size_t)c->nyl * (host_is_f64 ? 8 : 4);
 	if (int rc = ensure_staging(c, 2 * (size_t)c->nx * (size_t)c->nyl * 8)) return rc;
-	c->dense.pending = false;  // a new state: nothing to resume
-	c->ark.live = false;       // ... and a controller history that belongs to the old one
-	c->cycle_pos = -1;         // ... and ghost rows that belong to the old one
+	crd::arkode::drop(c->dense, c->ark);  // a new state: nothing to resume, and a controller history that belongs to the old one
+	c->cycle_pos = -1;                    // ... and ghost rows that belong to the old one
 	HIP_TRY(c, hipMemcpyAsync(c->stage_in, y, bytes, hipMemcpyHostToDevice, c->compute));
 	HIP_TRY(c, launch_aos_to_planes(c->p.precision, host_is_f64, c->stage_in, c->planes(crd_ctx::Y), c->nx, c->nyl, c->compute));
 	HIP_TRY(c, hipStreamSynchronize(c->compute));
@@ -752,11 +751,8 @@ int crd_get_launch_geometry(crd_ctx *c, crd_launch_geometry *out)
 	FusedCall call{};
 	call.dt = 1.0;
 	// the stage flags of the last step the context took (none taken: of a step at t = 0): which instantiation a launch there runs
-	{
-		const double cs4[4] = {0.0, 0.5, 0.5, 1.0}, dt_last = c->last_step_dt > 0.0 ? c->last_step_dt : 0.0;
-		for (int k = 0; k < 4; k++) call.absorb[k] = absorbing(c, c->last_step_t + cs4[k] * dt_last) ? 1 : 0;
-		call.absorb[4] = call.absorb[3];
-	}
+	crd::step::stage_flags(c->last_step_t, c->last_step_dt > 0.0 ? c->last_step_dt : 0.0, c->p.t_boundary, 4, call.absorb);
+	call.absorb[4] = call.absorb[3];
 	call.steps = c->plan.tuned ? fused_steps_supported(c->p.precision, c->desc, c->plan.steps) : 1;
 	// (fp32 triples any stage of which has the absorbing rows on are stepped as a pair and a single step: run_steps, triple_absorbs)
 	if (call.steps == 3 && c->p.precision != CRD_PRECISION_F64 && (call.absorb[0] || call.absorb[1] || call.absorb[2] || call.absorb[3])) call.steps = 2;

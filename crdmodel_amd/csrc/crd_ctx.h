@@ -17,6 +17,7 @@
 #include "crd_arkode.h"
 #include "crd_internal.h"
 #include "crd_kernels.h"
+#include "crd_step.h"
 
 namespace crd {
 
@@ -111,7 +112,7 @@ struct crd_ctx {
 
 	// State planes: Y (current), SA / SB (stage ping-pong), ACC; [k][0] = var0, [k][1] = var1.
 	// OUT exists only in contexts that have produced dense output (lazy): the third state plane of crd_integrate_adaptive.
-	enum { Y = 0, SA = 1, SB = 2, ACC = 3, OUT = 4, NPLANES = 5 };
+	enum { Y = crd::arkode::Y, SA = crd::arkode::SA, SB = crd::arkode::SB, ACC = crd::arkode::ACC, OUT = crd::arkode::OUT, NPLANES = crd::arkode::NPLANES };
 	void *plane[NPLANES][2] = {};
 	std::vector<void *> plane_allocs;  // what hipMalloc returned for them (a plane starts `plane_skew` x its index into its allocation)
 	size_t plane_skew = 0;             // bytes; see alloc_plane (crd_context.cpp)
@@ -146,14 +147,8 @@ struct crd_ctx {
 	hipStream_t down = nullptr;    // device-to-host stream of the pipelined crd_rhs_host (lazy)
 	std::vector<hipEvent_t> ev_band;  // its per-band events (lazy)
 
-	// Dense output of the adaptive integrator (ARK_NORMAL): after a call that overshot tout, plane Y holds the interpolant at
-	// t_out, SA the integrator's own state y_{n+1} at t_np1, OUT y_n at t_n, SB / ACC f(t_n, y_n) / f(t_{n+1}, y_{n+1}).
-	struct {
-		bool pending = false;
-		double t_out = 0.0, t_n = 0.0, t_np1 = 0.0;
-	} dense;
-
-	// Memory of the ARKode-style controller (CRD_ADAPT_ARKODE) between calls (crd_arkode.h).
+	// Dense output of the adaptive integrator and memory of the ARKode-style controller (CRD_ADAPT_ARKODE) between calls (crd_arkode.h).
+	crd::arkode::Dense dense;
 	crd::arkode::Memory ark;
 
 	// Multi-slab fused stepping: position in the deep-halo exchange cycle the resident state is at (steps taken since the ghost
@@ -229,7 +224,7 @@ hipError_t upload_reals(int precision, const std::vector<double> &src, void **ds
 int upload_table(crd_ctx *c, const std::vector<double> &src, void **dst);  // host doubles -> device precision
 int ensure_staging(crd_ctx *c, size_t bytes);                              // AoS staging of the *_host entry points
 int alloc_plane(crd_ctx *c, int k, int f);                                 // one field plane of state k, zeroed
-inline bool absorbing(const crd_ctx *c, double t_stage) { return t_stage < c->p.t_boundary; }  // strict <, src/FHNmodel_torus.cpp:643
+inline bool absorbing(const crd_ctx *c, double t_stage) { return step::absorbing_at(t_stage, c->p.t_boundary); }
 int resolve_stepper(const crd_ctx *c);  // CRD_STEPPER_STAGED / _FUSED, or -1 when the requested one is unavailable
 int check_group(crd_ctx *const *ctxs, int n);
 

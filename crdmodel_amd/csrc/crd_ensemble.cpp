@@ -46,12 +46,9 @@ struct crd_ensemble {
 	// Error-controlled integration (crd_ensemble_integrate_adaptive): allocated at the first such call, empty before.
 	struct Adaptive {
 		void *buf[5];             // the member's five state buffers: its two (EnsembleMember::u) and three for the dense output
-		void *role[5];            // buffer of each role Y, SA, SB, ACC, OUT, as a context's planes (crd_ctx); role[Y] is the state handed back
+		void *role[5];            // buffer of each role (arkode::Y .. OUT), as a context's planes; role[Y] is the state handed back
 		arkode::Memory ark;       // the controller's memory between calls (crd_ctx::ark)
-		struct {
-			bool pending = false;
-			double t_out = 0.0, t_n = 0.0, t_np1 = 0.0;
-		} dense;                  // crd_ctx::dense
+		arkode::Dense dense;      // the finished step a next call may resume from (crd_ctx::dense)
 	};
 	std::vector<Adaptive> adapt;
 	EnsemblePlan aplan;                        // the attempt kernel's plan: fixed at the first adaptive call
@@ -154,6 +151,28 @@ const char *mixed_disagreement(const crd_params &a, const crd_params &b)
 }
 
 size_t member_points(const crd_ensemble *e, int member) { return (size_t)e->grids[(size_t)member].nx * (size_t)e->grids[(size_t)member].ny; }
+
+// the reaction block of a diffusion-only run is skipped, absorbing rows included: no launch of it takes the instantiation with the selects
+bool can_absorb(const crd_ensemble *e) { return e->model != dev::kModelDiffusionOnly; }
+
+// The fixed steps go on from the states handed back, not from the integrator's own (run_steps): no member has anything to resume.
+void drop_adaptive(crd_ensemble *e) { for (auto &a : e->adapt) arkode::drop(a.dense, a.ark); }
+
+// `call` between the ensemble's two timing events: its elapsed time on the stream in *ms_total (the *_timed entry points).
+template <typename Call>
+int timed_call(crd_ensemble *e, double *ms_total, Call call)
+{
+	if (!e) return CRD_EINVAL;
+	ENS_TRY(e, hipSetDevice(e->device));
+	ENS_TRY(e, hipEventRecord(e->ev0, e->stream));
+	if (int rc = call()) return rc;
+	ENS_TRY(e, hipEventRecord(e->ev1, e->stream));
+	ENS_TRY(e, hipEventSynchronize(e->ev1));
+	float ms = 0.f;
+	ENS_TRY(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
+	if (ms_total) *ms_total = ms;
+	return CRD_OK;
+}
 
 constexpr const char *kMixedRefusal = "members of different shape";
 
@@ -434,7 +453,7 @@ int crd_ensemble_upload(crd_ensemble *e, int member, const void *y, int host_is_
 	const size_t points = member_points(e, member);
 	const EnsembleMember &m = e->members[(size_t)member];
 	ENS_TRY(e, hipMemcpyAsync(e->stage, y, 2 * points * (host_is_f64 ? 8 : 4), hipMemcpyHostToDevice, e->stream));
-	if (!e->adapt.empty()) e->adapt[(size_t)member].dense.pending = e->adapt[(size_t)member].ark.live = false;  // this member starts afresh
+	if (!e->adapt.empty()) arkode::drop(e->adapt[(size_t)member].dense, e->adapt[(size_t)member].ark);  // this member starts afresh
 	ENS_TRY(e, launch_ensemble_aos_to_planes(e->precision, host_is_f64, e->stage, m.u[e->cur], m.v[e->cur], points, e->stream));
 	ENS_TRY(e, hipStreamSynchronize(e->stream));
 	return CRD_OK;
@@ -466,14 +485,14 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 			return efail(e, CRD_EINVAL, "the observer has room for " + std::to_string(ob.capacity - ob.count) + " more samples; this call would record " + std::to_string(samples));
 	}
 	TraceRange range("crd_ensemble_step_rk4");
-	for (auto &a : e->adapt) a.dense.pending = a.ark.live = false;  // stepping on from the states handed back (run_steps)
+	drop_adaptive(e);
 	ENS_TRY(e, hipSetDevice(e->device));
 	EnsembleStep st{};
-	// the step's constants as launch_fused_t forms them
-	st.h1 = dt;
-	st.h2 = 0.5 * dt;
-	st.h3 = dt / 3.0;
-	st.h6 = dt / 6.0;
+	const step::Sizes hs(dt);
+	st.h1 = hs.h[0];
+	st.h2 = hs.h[1];
+	st.h3 = hs.h[2];
+	st.h6 = hs.h[3];
 	st.ka4 = std::pow(kGbKa, 4.0);  // pow(KA, p), src/GoldbeterModel_torus.cpp:695
 	plan_geometry(st, e, e->plan, e->n, e->mixed ? &e->shapes : nullptr);
 	const bool pairs = e->steps_per_launch == 2;
@@ -482,37 +501,30 @@ int crd_ensemble_step_rk4(crd_ensemble *e, double t0, double dt, int64_t nsteps)
 		pr.step = st;
 		plan_geometry(pr.step, e, e->pair_plan, e->n, e->mixed ? &e->pair_shapes : nullptr);
 	}
-	const double cs[4] = {0.0, 0.5, 0.5, 1.0};
 	double latest_boundary = -INFINITY;  // the absorbing rows are on at stage time t exactly when t < some member's tBoundary
 	for (const crd_params &p : e->p) latest_boundary = std::max(latest_boundary, p.t_boundary);
-	const bool can_absorb = e->model != dev::kModelDiffusionOnly;
+	// the stage times of a step at t, which the kernel compares with each member's tBoundary; true: some member has its absorbing rows on
+	auto stage_times = [&](double t, double *ts) {
+		bool any = false;
+		for (int k = 0; k < 4; k++) any = step::absorbing_at(ts[k] = step::stage_time(t, dt, k), latest_boundary) || any;
+		return any && can_absorb(e);
+	};
 	for (int64_t s = 0; s < nsteps;) {
-		const double t = t0 + (double)s * dt;  // as run_steps forms it
-		bool absorb = false;
-		for (int k = 0; k < 4; k++) {
-			st.t_stage[k] = t + cs[k] * dt;  // as make_fused_call forms it
-			absorb = absorb || st.t_stage[k] < latest_boundary;
-		}
+		bool absorb = stage_times(t0 + (double)s * dt, st.t_stage);  // (the step's time as run_steps forms it)
 		// Two steps in one launch where the setting asks for pairs, two steps are left, and -- an observer open -- the first of them does
 		// not complete a stride: a pair never straddles a sample.
 		int taken = 1;
 		if (pairs && s + 2 <= nsteps && !(ob.open && (ob.steps + 1) % ob.opt.stride == 0)) {
-			const double t2 = t0 + (double)(s + 1) * dt;  // the second step's t as the next single step's is formed
-			for (int k = 0; k < 4; k++) {
-				pr.step.t_stage[k] = st.t_stage[k];
-				pr.t_stage2[k] = t2 + cs[k] * dt;
-				absorb = absorb || pr.t_stage2[k] < latest_boundary;
-			}
+			std::copy(st.t_stage, st.t_stage + 4, pr.step.t_stage);
+			absorb = stage_times(t0 + (double)(s + 1) * dt, pr.t_stage2) || absorb;  // the second step's t as the next single step's is formed
 			pr.step.src = e->cur;
-			if (e->mixed)
-				ENS_TRY(e, launch_ensemble_pair_mixed(e->precision, e->model, e->pair_plan.cols, absorb && can_absorb, e->table, e->pair_shapes_dev, e->n, e->min_ny, pr, e->stream));
-			else
-				ENS_TRY(e, launch_ensemble_pair(e->precision, e->model, e->pair_plan.cols, absorb && can_absorb, e->table, pr, e->stream));
+			if (e->mixed) ENS_TRY(e, launch_ensemble_pair_mixed(e->precision, e->model, e->pair_plan.cols, absorb, e->table, e->pair_shapes_dev, e->n, e->min_ny, pr, e->stream));
+			else ENS_TRY(e, launch_ensemble_pair(e->precision, e->model, e->pair_plan.cols, absorb, e->table, pr, e->stream));
 			taken = 2;
 		} else {
 			st.src = e->cur;
-			if (e->mixed) ENS_TRY(e, launch_ensemble_step_mixed(e->precision, e->model, e->plan.cols, absorb && can_absorb, e->table, e->shapes_dev, e->n, st, e->stream));
-			else ENS_TRY(e, launch_ensemble_step(e->precision, e->model, e->plan.cols, absorb && can_absorb, e->table, st, e->stream));
+			if (e->mixed) ENS_TRY(e, launch_ensemble_step_mixed(e->precision, e->model, e->plan.cols, absorb, e->table, e->shapes_dev, e->n, st, e->stream));
+			else ENS_TRY(e, launch_ensemble_step(e->precision, e->model, e->plan.cols, absorb, e->table, st, e->stream));
 		}
 		e->cur = 1 - e->cur;  // (a pair flips once: its first step's state never reaches memory)
 		s += taken;
@@ -574,16 +586,7 @@ int crd_ensemble_get_steps_per_launch(const crd_ensemble *e) { return e ? e->ste
 
 int crd_ensemble_step_rk4_timed(crd_ensemble *e, double t0, double dt, int64_t nsteps, double *ms_total)
 {
-	if (!e) return CRD_EINVAL;
-	ENS_TRY(e, hipSetDevice(e->device));
-	ENS_TRY(e, hipEventRecord(e->ev0, e->stream));
-	if (int rc = crd_ensemble_step_rk4(e, t0, dt, nsteps)) return rc;
-	ENS_TRY(e, hipEventRecord(e->ev1, e->stream));
-	ENS_TRY(e, hipEventSynchronize(e->ev1));
-	float ms = 0.f;
-	ENS_TRY(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
-	if (ms_total) *ms_total = ms;
-	return CRD_OK;
+	return timed_call(e, ms_total, [&] { return crd_ensemble_step_rk4(e, t0, dt, nsteps); });
 }
 
 int crd_ensemble_synchronize(crd_ensemble *e)
@@ -648,31 +651,19 @@ int step_own(crd_ensemble *e, double t0, double t1, const double *dt, const int6
 	TraceRange range(where);
 	ENS_TRY(e, hipSetDevice(e->device));
 	if (int rc = ensure_own(e)) return rc;
-	for (auto &a : e->adapt) a.dense.pending = a.ark.live = false;  // stepping on from the states handed back (run_steps)
+	drop_adaptive(e);
 
 	// What the rounds share: the plan made for all B members when the ensemble was created (no re-planning as members finish).
 	EnsembleStep st{};
 	st.ka4 = std::pow(kGbKa, 4.0);  // pow(KA, p), src/GoldbeterModel_torus.cpp:695
 	plan_geometry(st, e, e->plan, 0);  // (nblocks: the active slots', set with each slot table)
-	// Per member, once: its step size and the constants formed from it as launch_fused_t forms them.
-	struct Own {
-		double dt, h[4];
-		float hf[4];
-		int blocks;
-	};
-	std::vector<Own> own((size_t)B);
+	// Per member, once: its step size (own[k].h[0]), the constants formed from it, and its blocks.
+	std::vector<step::Sizes> own;
+	std::vector<int> blocks;
 	for (int k = 0; k < B; k++) {
-		Own &m = own[(size_t)k];
-		m.dt = dt ? dt[k] : (t1 - t0) / (double)nsteps[k];
-		m.h[0] = m.dt;
-		m.h[1] = 0.5 * m.dt;
-		m.h[2] = m.dt / 3.0;
-		m.h[3] = m.dt / 6.0;
-		for (int q = 0; q < 4; q++) m.hf[q] = (float)m.h[q];
-		m.blocks = e->mixed ? e->shapes[(size_t)k].nsb * e->shapes[(size_t)k].nchunks : st.member_blocks;
+		own.emplace_back(dt ? dt[k] : (t1 - t0) / (double)nsteps[k]);
+		blocks.push_back(e->mixed ? e->shapes[(size_t)k].nsb * e->shapes[(size_t)k].nchunks : st.member_blocks);
 	}
-	const double cs[4] = {0.0, 0.5, 0.5, 1.0};
-	const bool can_absorb = e->model != dev::kModelDiffusionOnly;
 	const size_t version_entries = 2 * ((size_t)B + 1);
 	// Round s steps every member with nsteps[k] > s, in member order.  The slot table is rewritten only when that set, or a member's
 	// absorbing decision at one of its stages, differs from the round before: at most B + 1 + 3 B times a call.
@@ -688,12 +679,10 @@ int step_own(crd_ensemble *e, double t0, double t1, const double *dt, const int6
 		for (int k = 0; k < B; k++) {
 			if (nsteps[k] <= s) continue;
 			now_active.push_back(k);
-			const double t = t0 + (double)s * own[(size_t)k].dt;  // as run_steps forms it
-			for (int q = 0; q < 4; q++) {
-				const int f = (can_absorb && t + cs[q] * own[(size_t)k].dt < e->p[(size_t)k].t_boundary) ? 1 : 0;  // as make_fused_call forms it; strict <, absorbing() (crd_ctx.h)
-				now_flags.push_back(f);
-				now_absorb = now_absorb || f;
-			}
+			const double dt_k = own[(size_t)k].h[0];
+			int f[4] = {0, 0, 0, 0};
+			if (can_absorb(e)) now_absorb = step::stage_flags(t0 + (double)s * dt_k, dt_k, e->p[(size_t)k].t_boundary, 4, f) || now_absorb;  // (the step's time as run_steps forms it)
+			now_flags.insert(now_flags.end(), f, f + 4);
 		}
 		const int count = (int)now_active.size();
 		if (s == 0 || now_active != active || now_flags != flags) {
@@ -713,14 +702,12 @@ int step_own(crd_ensemble *e, double t0, double t1, const double *dt, const int6
 					sl = EnsembleOwnSlot{};
 					sl.in = m.u[e->cur ^ parity];  // every active member has taken s steps: one parity for the round
 					sl.out = m.u[e->cur ^ parity ^ 1];
-					for (int q = 0; q < 4; q++) {
-						sl.h[q] = own[(size_t)k].h[q];
-						sl.hf[q] = own[(size_t)k].hf[q];
-						sl.absorb[q] = now_flags[(size_t)(4 * i + q)];
-					}
+					std::copy(own[(size_t)k].h, own[(size_t)k].h + 4, sl.h);
+					std::copy(own[(size_t)k].hf, own[(size_t)k].hf + 4, sl.hf);
+					std::copy(&now_flags[(size_t)(4 * i)], &now_flags[(size_t)(4 * i)] + 4, sl.absorb);
 					sl.member = k;
 					sl.first_block = first;
-					first += own[(size_t)k].blocks;
+					first += blocks[(size_t)k];
 				}
 				slots[count] = EnsembleOwnSlot{};
 				slots[count].first_block = first;
@@ -781,23 +768,12 @@ int crd_ensemble_step_rk4_own_dt(crd_ensemble *e, double t0, double t1, const do
 
 int crd_ensemble_step_rk4_own_timed(crd_ensemble *e, double t0, double t1, const int64_t *nsteps, double *ms_total)
 {
-	if (!e) return CRD_EINVAL;
-	ENS_TRY(e, hipSetDevice(e->device));
-	ENS_TRY(e, hipEventRecord(e->ev0, e->stream));
-	if (int rc = crd_ensemble_step_rk4_own(e, t0, t1, nsteps)) return rc;
-	ENS_TRY(e, hipEventRecord(e->ev1, e->stream));
-	ENS_TRY(e, hipEventSynchronize(e->ev1));
-	float ms = 0.f;
-	ENS_TRY(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
-	if (ms_total) *ms_total = ms;
-	return CRD_OK;
+	return timed_call(e, ms_total, [&] { return crd_ensemble_step_rk4_own(e, t0, t1, nsteps); });
 }
 
 }  // extern "C"
 
 namespace {
-
-enum { kY = 0, kSA = 1, kSB = 2, kACC = 3, kOUT = 4 };  // a context's plane roles (crd_ctx)
 
 // The first adaptive call's allocations: three more state buffers per member, the error partials, the per-member scalars and the
 // attempt / operand tables.  An ensemble that only takes fixed steps never makes them.
@@ -858,16 +834,18 @@ int ensure_adaptive(crd_ensemble *e)
 	return CRD_OK;
 }
 
-// What one member does during one call (integrate_adaptive_impl's locals, per member).
+// What one member does during one call (crd_steppers.cpp: what integrate_adaptive_impl keeps in locals).
 struct MemberRun {
 	crd_adaptive_stats st{};
 	double t = 0.0, t_prev = 0.0, h_cap = 0.0, t_boundary = 0.0;
-	int cur = kY, spare = kSA, third = kOUT, prev = -1;
+	arkode::Rotation rot;  // its state buffers' turns, by role
 	int nef = 0, dst = -1;
 	int64_t steps = 0;
 	bool new_step = true, reinterpolate = false, failed = false;
 	arkode::Hin hin;
 	std::string why;
+	// does the call end with an output for this member: has its last step (t_prev -> t) reached or passed tout?
+	bool output(double tout) const { return !failed && rot.prev >= 0 && t >= tout; }
 };
 
 // Operand set `set` (0 .. kOpSets) of the batched element-wise launches: host entries, then one copy to the device.
@@ -915,10 +893,7 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 	std::vector<char> resume((size_t)B, 0);
 	bool estimate = false;
 	for (int k = 0; k < B; k++) {
-		if (!e->adapt.empty()) {
-			const auto &a = e->adapt[(size_t)k];
-			resume[(size_t)k] = a.dense.pending && a.ark.live && t0 == a.dense.t_out;
-		}
+		if (!e->adapt.empty()) resume[(size_t)k] = arkode::resumes(e->adapt[(size_t)k].dense, e->adapt[(size_t)k].ark, t0, true);
 		estimate = estimate || (!resume[(size_t)k] && !(o.h0 > 0.0) && tout > t0);
 	}
 	arkode::Hin probe;
@@ -936,14 +911,14 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 		MemberRun &r = run[(size_t)k];
 		auto &a = e->adapt[(size_t)k];
 		const crd_params &p = e->p[(size_t)k];
-		r.h_cap = o.h_max > 0.0 ? o.h_max : (o.h_max == 0.0 ? crd_stable_dt(&p) : INFINITY);  // the member's own stability bound
+		r.h_cap = arkode::h_cap(o, p);  // (h_max = 0: the member's own stability bound)
 		r.t_boundary = p.t_boundary;
 		r.t = r.t_prev = t0;
 		if (!resume[(size_t)k]) {
 			// the member's state is in its descriptor's current buffer; its other four buffers are free
 			void *y = e->members[(size_t)k].u[e->cur];
-			a.role[kY] = y;
-			int next = kSA;
+			a.role[arkode::Y] = y;
+			int next = arkode::SA;
 			for (void *b : a.buf)
 				if (b != y) a.role[next++] = b;
 			a.dense.pending = false;
@@ -954,17 +929,14 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 			}
 			continue;
 		}
-		r.st.t_internal = a.dense.t_np1;
-		if (tout <= a.dense.t_np1) {  // still inside the step already taken: interpolate again
+		r.t = a.dense.t_np1;
+		if (tout <= a.dense.t_np1) {  // still inside the step already taken: that step (t_prev -> t) again, to interpolate again
 			r.reinterpolate = true;
-			r.prev = kOUT;
-			r.cur = kSA;
+			r.t_prev = a.dense.t_n;
+			r.rot.reinterpolate();
 			continue;
 		}
-		r.t = a.dense.t_np1;
-		r.cur = kSA;
-		r.spare = kOUT;
-		r.third = kY;
+		r.rot.resume();
 	}
 
 	// arkHin of the fresh members, batched: f0 -> SB, the trial state -> SA, f(trial) -> ACC
@@ -973,9 +945,9 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 		for (int i = 0; i < nh; i++) {
 			const int k = hin[(size_t)i];
 			auto &a = e->adapt[(size_t)k];
-			op_set(e, 0)[i] = make_op(k, a.role[kY], nullptr, nullptr, nullptr, a.role[kSB]);
-			op_set(e, 0)[i].absorb = t0 < run[(size_t)k].t_boundary ? 1 : 0;
-			op_set(e, 1)[i] = make_op(k, a.role[kY], a.role[kSB], nullptr, nullptr, nullptr);
+			op_set(e, 0)[i] = make_op(k, a.role[arkode::Y], nullptr, nullptr, nullptr, a.role[arkode::SB]);
+			op_set(e, 0)[i].absorb = step::absorbing_at(t0, run[(size_t)k].t_boundary) ? 1 : 0;
+			op_set(e, 1)[i] = make_op(k, a.role[arkode::Y], a.role[arkode::SB], nullptr, nullptr, nullptr);
 		}
 		ENS_TRY(e, upload_ops(e, 0, nh));
 		ENS_TRY(e, upload_ops(e, 1, nh));
@@ -994,12 +966,12 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 				auto &a = e->adapt[(size_t)k];
 				const double hg = run[(size_t)k].hin.hg;
 				EnsembleOp &ax = op_set(e, 0)[i];
-				ax = make_op(k, a.role[kY], a.role[kSB], nullptr, nullptr, a.role[kSA]);
+				ax = make_op(k, a.role[arkode::Y], a.role[arkode::SB], nullptr, nullptr, a.role[arkode::SA]);
 				ax.c[0] = hg;
 				ax.cf[0] = (float)hg;
-				op_set(e, 1)[i] = make_op(k, a.role[kSA], nullptr, nullptr, nullptr, a.role[kACC]);
-				op_set(e, 1)[i].absorb = t0 + hg < run[(size_t)k].t_boundary ? 1 : 0;
-				op_set(e, 2)[i] = make_op(k, a.role[kY], a.role[kSB], a.role[kACC], nullptr, nullptr);
+				op_set(e, 1)[i] = make_op(k, a.role[arkode::SA], nullptr, nullptr, nullptr, a.role[arkode::ACC]);
+				op_set(e, 1)[i].absorb = step::absorbing_at(t0 + hg, run[(size_t)k].t_boundary) ? 1 : 0;
+				op_set(e, 2)[i] = make_op(k, a.role[arkode::Y], a.role[arkode::SB], a.role[arkode::ACC], nullptr, nullptr);
 				op_set(e, 2)[i].c[0] = 1.0 / hg;
 			}
 			for (int set = 0; set < 3; set++) ENS_TRY(e, upload_ops(e, set, no));
@@ -1035,7 +1007,6 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 	l.partials = e->partials;
 	plan_geometry(l, e, pl, 0);  // (nblocks: the active members', set with each round)
 	l.member_items = pl.nstrips * pl.nchunks;
-	const double cs[5] = {0.0, 0.5, 0.5, 1.0, 0.75};  // stage times: make_fused_call's four, then Zonneveld's fifth (launch_attempt)
 	std::vector<int> slot_member;
 	while (!active.empty()) {
 		slot_member.clear();
@@ -1051,30 +1022,24 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 				}
 				r.new_step = false;
 				r.nef = 0;
-				r.dst = r.spare;
+				r.dst = r.rot.spare;
 			}
-			const double h = a.ark.h;
+			const step::Sizes hs(a.ark.h);
 			EnsembleAttempt &at = e->att_host[slot_member.size()];
 			at = EnsembleAttempt{};
-			at.in = a.role[r.cur];
+			at.in = a.role[r.rot.cur];
 			at.out = a.role[r.dst];
-			at.h[0] = h;  // as launch_fused_t forms them
-			at.h[1] = 0.5 * h;
-			at.h[2] = h / 3.0;
-			at.h[3] = h / 6.0;
-			for (int q = 0; q < 4; q++) at.hf[q] = (float)at.h[q];
+			std::copy(hs.h, hs.h + 4, at.h);
+			std::copy(hs.hf, hs.hf + 4, at.hf);
 			at.member = k;
-			for (int q = 0; q < 5; q++) {
-				at.absorb[q] = r.t + cs[q] * h < r.t_boundary ? 1 : 0;  // strict <, absorbing() (crd_ctx.h)
-				absorb = absorb || at.absorb[q];
-			}
+			absorb = step::stage_flags(r.t, a.ark.h, r.t_boundary, 5, at.absorb) || absorb;  // the four stages and Zonneveld's fifth
 			slot_member.push_back(k);
 		}
 		const int count = (int)slot_member.size();
 		if (count > 0) {
 			l.nblocks = l.member_blocks * count;
 			ENS_TRY(e, hipMemcpyAsync(e->att_dev, e->att_host, (size_t)count * sizeof(EnsembleAttempt), hipMemcpyHostToDevice, e->stream));
-			ENS_TRY(e, launch_ensemble_attempts(e->precision, e->model, absorb && e->model != dev::kModelDiffusionOnly, e->table, e->att_dev, count, l, e->sums_dev, e->stream));
+			ENS_TRY(e, launch_ensemble_attempts(e->precision, e->model, absorb && can_absorb(e), e->table, e->att_dev, count, l, e->sums_dev, e->stream));
 			ENS_TRY(e, fetch_sums(e, count));
 		}
 		for (int i = 0; i < count; i++) {
@@ -1087,12 +1052,7 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 				r.t_prev = r.t;
 				arkode::accept(A, dsm, o, r.h_cap, r.t, r.st);
 				r.steps++;
-				// rotate: the old state becomes y_n (kept for the interpolant), the old y_n / scratch becomes the next target
-				const int old_cur = r.cur;
-				r.cur = r.dst;
-				r.spare = (r.prev >= 0) ? r.prev : r.third;
-				if (r.prev < 0) r.third = -1;
-				r.prev = old_cur;
+				r.rot.accept(r.dst, true);
 				r.new_step = true;
 			} else if (!arkode::reject(A, dsm, &r.nef, o, r.h_cap, r.st)) {
 				r.failed = true;
@@ -1111,23 +1071,17 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 	for (int k = 0; k < B; k++) {
 		MemberRun &r = run[(size_t)k];
 		auto &a = e->adapt[(size_t)k];
-		if (r.reinterpolate || r.failed || r.prev < 0 || r.t < tout) continue;
-		op_set(e, 0)[nd] = make_op(k, a.role[r.prev], nullptr, nullptr, nullptr, a.role[kSB]);
-		op_set(e, 0)[nd].absorb = r.t_prev < r.t_boundary ? 1 : 0;
-		op_set(e, 1)[nd] = make_op(k, a.role[r.cur], nullptr, nullptr, nullptr, a.role[kACC]);
-		op_set(e, 1)[nd].absorb = r.t < r.t_boundary ? 1 : 0;
-		nd++;
-	}
-	for (int k = 0; k < B; k++) {
-		MemberRun &r = run[(size_t)k];
-		auto &a = e->adapt[(size_t)k];
-		const bool fresh_output = !r.reinterpolate && !r.failed && r.prev >= 0 && r.t >= tout;
-		if (!r.reinterpolate && !fresh_output) continue;
-		const double t_n = r.reinterpolate ? a.dense.t_n : r.t_prev, t_np1 = r.reinterpolate ? a.dense.t_np1 : r.t, hstep = t_np1 - t_n;
-		const int out = kY + kSA + kOUT - r.prev - r.cur;
+		if (!r.output(tout)) continue;
+		const double hstep = r.t - r.t_prev;
 		EnsembleOp &op = op_set(e, 2)[nhm++];
-		op = make_op(k, a.role[r.prev], a.role[r.cur], a.role[kSB], a.role[kACC], a.role[out]);
-		ensemble_hermite_coefficients((tout - t_n) / hstep, hstep, op.c, op.cf);
+		op = make_op(k, a.role[r.rot.prev], a.role[r.rot.cur], a.role[arkode::SB], a.role[arkode::ACC], a.role[r.rot.interpolant()]);
+		ensemble_hermite_coefficients((tout - r.t_prev) / hstep, hstep, op.c, op.cf);
+		if (r.reinterpolate) continue;
+		op_set(e, 0)[nd] = make_op(k, a.role[r.rot.prev], nullptr, nullptr, nullptr, a.role[arkode::SB]);
+		op_set(e, 0)[nd].absorb = step::absorbing_at(r.t_prev, r.t_boundary) ? 1 : 0;
+		op_set(e, 1)[nd] = make_op(k, a.role[r.rot.cur], nullptr, nullptr, nullptr, a.role[arkode::ACC]);
+		op_set(e, 1)[nd].absorb = step::absorbing_at(r.t, r.t_boundary) ? 1 : 0;
+		nd++;
 	}
 	for (int set = 0; set < 3; set++) ENS_TRY(e, upload_ops(e, set, set < 2 ? nd : nhm));
 	ENS_TRY(e, launch_ensemble_rhs(e->precision, e->model, e->table, e->ops_dev, nd, e->nx, e->ny, ka4, e->stream));
@@ -1139,28 +1093,10 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 	for (int k = 0; k < B; k++) {
 		MemberRun &r = run[(size_t)k];
 		auto &a = e->adapt[(size_t)k];
-		const bool output = r.reinterpolate || (!r.failed && r.prev >= 0 && r.t >= tout);
-		if (output) {
-			// roles now: prev = y_n, cur = y_{n+1}, SB = f_n, ACC = f_{n+1}; the interpolant is in the remaining state buffer
-			const int out = kY + kSA + kOUT - r.prev - r.cur;
-			void *b_out = a.role[out], *b_n = a.role[r.prev], *b_np1 = a.role[r.cur];
-			a.role[kY] = b_out;
-			a.role[kSA] = b_np1;
-			a.role[kOUT] = b_n;
-			if (!r.reinterpolate) {
-				a.dense.pending = true;
-				a.dense.t_n = r.t_prev;
-				a.dense.t_np1 = r.t;
-				r.st.t_internal = r.t;
-			}
-			a.dense.t_out = tout;
-			r.st.t = tout;
-		} else {  // no output (a zero-length interval, or a failure): hand back the state reached
-			if (r.cur != kY) std::swap(a.role[kY], a.role[r.cur]);
-			a.dense.pending = false;
-			r.st.t_internal = r.t;
-			r.st.t = r.t;
-		}
+		// an output at tout, or -- a zero-length interval, a failure -- the state reached handed back
+		arkode::end_of_call(r.rot, r.output(tout), a.dense, tout, r.t_prev, r.t).apply(a.role);
+		r.st.t_internal = r.t;
+		r.st.t = r.output(tout) ? tout : r.t;
 		if (!r.reinterpolate) a.ark.live = !r.failed && a.dense.pending;
 		r.st.h_next = a.ark.hprime;
 		if (r.failed) {
@@ -1172,10 +1108,10 @@ int crd_ensemble_integrate_adaptive(crd_ensemble *e, double t0, double tout, con
 		// the descriptor: the state handed back is the current buffer; the other one (overwritten only by a fixed step, which ends the
 		// carry-over) the integrator's own state
 		EnsembleMember &m = e->members[(size_t)k];
-		m.u[e->cur] = a.role[kY];
-		m.v[e->cur] = static_cast<char *>(a.role[kY]) + plane;
-		m.u[1 - e->cur] = a.role[kSA];
-		m.v[1 - e->cur] = static_cast<char *>(a.role[kSA]) + plane;
+		m.u[e->cur] = a.role[arkode::Y];
+		m.v[e->cur] = static_cast<char *>(a.role[arkode::Y]) + plane;
+		m.u[1 - e->cur] = a.role[arkode::SA];
+		m.v[1 - e->cur] = static_cast<char *>(a.role[arkode::SA]) + plane;
 	}
 	ENS_TRY(e, hipMemcpyAsync(e->table, e->members.data(), (size_t)B * sizeof(EnsembleMember), hipMemcpyHostToDevice, e->stream));
 	if (e->obs.open) {

@@ -19,8 +19,8 @@ struct EnsembleMember {
 
 // What one launch of the ensemble step shares over its members.
 struct EnsembleStep {
-	double h1, h2, h3, h6;  // dt, dt/2, dt/3, dt/6, formed in double as launch_fused_t forms them; the kernel rounds them to its precision
-	double t_stage[4];      // t + c_k dt of the four stages (t = t0 + s dt, as run_steps forms it)
+	double h1, h2, h3, h6;  // dt, dt/2, dt/3, dt/6 in double (crd_step.h: step::Sizes); the kernel rounds them to its precision
+	double t_stage[4];      // the four stages' times (step::stage_time; t = t0 + s dt, as run_steps forms it)
 	double ka4;             // Goldbeter pow(KA, 4)
 	int src;                // buffer holding the input; the step writes buffer 1 - src
 	int nx, ny;
@@ -120,7 +120,7 @@ hipError_t launch_ensemble_pair_mixed(int precision, int model, int cols, bool a
 struct EnsembleOwnSlot {
 	const void *in;         // the member's input: a state buffer (u plane, then v plane), row 0 first, no ghost rows
 	void *out;              // ... and the buffer its step writes
-	double h[4];            // dt_k, dt_k/2, dt_k/3, dt_k/6 formed in double as launch_fused_t forms them (fp64 kernels)
+	double h[4];            // dt_k, dt_k/2, dt_k/3, dt_k/6 in double (crd_step.h: step::Sizes of dt_k; fp64 kernels)
 	float hf[4];            // ... rounded to fp32 on the host (fp32 kernels)
 	int member;             // index into the member table (and the shape table)
 	int absorb[4];          // t_stage < tBoundary at the member's own t + (0, 1/2, 1/2, 1) dt_k
@@ -141,7 +141,7 @@ hipError_t launch_ensemble_own_step(int precision, int model, int cols, bool abs
 struct EnsembleAttempt {
 	const void *in;         // y_n: a state buffer (u plane, then v plane), row 0 first, no ghost rows
 	void *out;              // the attempt's y_{n+1}
-	double h[4];            // h, h/2, h/3, h/6 formed in double as launch_fused_t forms them (fp64 kernels)
+	double h[4];            // h, h/2, h/3, h/6 in double (crd_step.h: step::Sizes of h; fp64 kernels)
 	float hf[4];            // ... rounded to fp32 on the host (fp32 kernels: a conversion in the kernel would cost registers)
 	int member;             // index into the member table and into the error partials' segments
 	int absorb[5];          // t_stage < tBoundary at t + (0, 1/2, 1/2, 1, 3/4) h: the four stages and Zonneveld's fifth

@@ -29,6 +29,7 @@
 #include <utility>
 
 #include "crd_device.h"
+#include "crd_step.h"
 #include "crd_tuning.h"
 
 namespace crd {
@@ -1515,10 +1516,11 @@ hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, 
 	a.in_v = row0<Real>(c.y0.v, d.nx);
 	a.out_u = row0<Real>(c.yout.u, d.nx);
 	a.out_v = row0<Real>(c.yout.v, d.nx);
-	a.h2 = (Real)(0.5 * c.dt);
-	a.h3 = (Real)(c.dt / 3.0);
-	a.h6 = (Real)(c.dt / 6.0);
-	a.h1 = (Real)c.dt;
+	const step::Sizes hs(c.dt);
+	a.h1 = (Real)hs.h[0];
+	a.h2 = (Real)hs.h[1];
+	a.h3 = (Real)hs.h[2];
+	a.h6 = (Real)hs.h[3];
 	for (int k = 0; k < 5; k++) a.absorb[k] = c.absorb[k];
 	for (int k = 0; k < 4; k++) a.absorb2[k] = c.absorb2[k];
 	for (int k = 0; k < 4; k++) a.absorb3[k] = c.absorb3[k];

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "crd_device.h"
+#include "crd_step.h"
 
 namespace crd {
 
@@ -287,11 +288,12 @@ hipError_t launch_stage_t(const SlabDesc &d, const StageCall &c, int row_begin, 
 	a.gw = static_cast<const Real *>(c.gcol_w);
 	a.ge = static_cast<const Real *>(c.gcol_e);
 	if (!d.wrap_x && (!a.gw || !a.ge)) return hipErrorInvalidValue;
+	const step::Sizes hs(c.dt);  // h[] = dt, dt/2, dt/3, dt/6
 	switch (c.stage) {
-	case 1: a.h_out = (Real)(0.5 * c.dt); a.h_acc = (Real)(c.dt / 6.0); break;
-	case 2: a.h_out = (Real)(0.5 * c.dt); a.h_acc = (Real)(c.dt / 3.0); break;
-	case 3: a.h_out = (Real)c.dt; a.h_acc = (Real)(c.dt / 3.0); break;
-	case 4: a.h_out = (Real)0; a.h_acc = (Real)(c.dt / 6.0); break;
+	case 1: a.h_out = (Real)hs.h[1]; a.h_acc = (Real)hs.h[3]; break;
+	case 2: a.h_out = (Real)hs.h[1]; a.h_acc = (Real)hs.h[2]; break;
+	case 3: a.h_out = (Real)hs.h[0]; a.h_acc = (Real)hs.h[2]; break;
+	case 4: a.h_out = (Real)0; a.h_acc = (Real)hs.h[3]; break;
 	default: a.h_out = a.h_acc = (Real)0; break;
 	}
 	if (row_end <= row_begin) return hipSuccess;

@@ -14,9 +14,8 @@ namespace {
 
 struct StagePlan {
 	int in, out;
-	double c;  // stage time = t + c dt
 };
-const StagePlan kStages[4] = {{crd_ctx::Y, crd_ctx::SA, 0.0}, {crd_ctx::SA, crd_ctx::SB, 0.5}, {crd_ctx::SB, crd_ctx::SA, 0.5}, {crd_ctx::SA, crd_ctx::Y, 1.0}};
+const StagePlan kStages[4] = {{crd_ctx::Y, crd_ctx::SA}, {crd_ctx::SA, crd_ctx::SB}, {crd_ctx::SB, crd_ctx::SA}, {crd_ctx::SA, crd_ctx::Y}};
 
 StageCall make_stage_call(const crd_ctx *c, int stage, double t, double dt)
 {
@@ -24,7 +23,7 @@ StageCall make_stage_call(const crd_ctx *c, int stage, double t, double dt)
 	StageCall call{};
 	call.stage = stage;
 	call.dt = dt;
-	call.absorb = absorbing(c, t + sp.c * dt) ? 1 : 0;
+	call.absorb = absorbing(c, step::stage_time(t, dt, stage - 1)) ? 1 : 0;
 	call.yin = c->planes(sp.in);
 	call.y0 = c->planes(crd_ctx::Y);
 	call.acc = c->planes(crd_ctx::ACC);
@@ -232,31 +231,32 @@ int fused_launch_multi(crd_ctx *const *cs, int n, double t, double dt, int src, 
 // t + dt (make_fused_call); the stepping loops form that step's time as t0 + (s + 1) dt, which may differ by a rounding -- which
 // matters only where a stage time lands within an ulp of tBoundary.  Such a pair is stepped singly, so that paired and unpaired
 // stepping take the same decisions.
+bool same_flags(const crd_ctx *c, double ta, double tb, double dt)  // do steps of size dt at ta and at tb take the same absorbing decisions?
+{
+	int fa[4], fb[4];
+	step::stage_flags(ta, dt, c->p.t_boundary, 4, fa);
+	step::stage_flags(tb, dt, c->p.t_boundary, 4, fb);
+	return std::equal(fa, fa + 4, fb);
+}
 bool pair_is_exact(const crd_ctx *c, double t0, int64_t s, double dt)
 {
-	const double t = t0 + (double)s * dt, t2 = t0 + (double)(s + 1) * dt, cs4[4] = {0.0, 0.5, 0.5, 1.0};
-	for (int k = 0; k < 4; k++)
-		if (absorbing(c, t2 + cs4[k] * dt) != absorbing(c, (t + dt) + cs4[k] * dt)) return false;
-	return true;
+	const double t = t0 + (double)s * dt;
+	return same_flags(c, t0 + (double)(s + 1) * dt, t + dt, dt);
 }
 // Does any stage of the three steps from t on have the absorbing rows on?  (The fp32 three-step kernel has no instantiation with the
 // selects -- it would not fit the registers: 256 + scratch --; such triples are stepped as a pair and a single step.)
 bool triple_absorbs(const crd_ctx *c, double t, double dt)
 {
-	const double ts[3] = {t, t + dt, (t + dt) + dt}, cs4[4] = {0.0, 0.5, 0.5, 1.0};
-	for (double tk : ts)
-		for (int k = 0; k < 4; k++)
-			if (absorbing(c, tk + cs4[k] * dt)) return true;
+	int f[4];
+	for (double tk : {t, t + dt, (t + dt) + dt})
+		if (step::stage_flags(tk, dt, c->p.t_boundary, 4, f)) return true;
 	return false;
 }
 // ... and steps s, s + 1, s + 2 as one three-step launch: the third step's flags come from (t + dt) + dt.
 bool triple_is_exact(const crd_ctx *c, double t0, int64_t s, double dt)
 {
-	if (!pair_is_exact(c, t0, s, dt)) return false;
-	const double t = t0 + (double)s * dt, t3 = t0 + (double)(s + 2) * dt, cs4[4] = {0.0, 0.5, 0.5, 1.0};
-	for (int k = 0; k < 4; k++)
-		if (absorbing(c, t3 + cs4[k] * dt) != absorbing(c, ((t + dt) + dt) + cs4[k] * dt)) return false;
-	return true;
+	const double t = t0 + (double)s * dt;
+	return pair_is_exact(c, t0, s, dt) && same_flags(c, t0 + (double)(s + 2) * dt, (t + dt) + dt, dt);
 }
 
 // RCCL runs: one decision for the whole ring on where in the exchange cycle the call starts (see crd_ctx::agree_dev).  begin_
@@ -312,10 +312,9 @@ FusedCall make_fused_call(const crd_ctx *c, double t, double dt, int src, int ds
 {
 	FusedCall call{};
 	call.dt = dt;
-	const double cs[4] = {0.0, 0.5, 0.5, 1.0};
-	for (int k = 0; k < 4; k++) call.absorb[k] = absorbing(c, t + cs[k] * dt) ? 1 : 0;
-	for (int k = 0; k < 4; k++) call.absorb2[k] = absorbing(c, (t + dt) + cs[k] * dt) ? 1 : 0;  // the step after this one, as the stepping loop forms its time
-	for (int k = 0; k < 4; k++) call.absorb3[k] = absorbing(c, ((t + dt) + dt) + cs[k] * dt) ? 1 : 0;  // ... and the one after that (three-step launches)
+	step::stage_flags(t, dt, c->p.t_boundary, 4, call.absorb);
+	step::stage_flags(t + dt, dt, c->p.t_boundary, 4, call.absorb2);         // the step after this one, as the stepping loop forms its time
+	step::stage_flags((t + dt) + dt, dt, c->p.t_boundary, 4, call.absorb3);  // ... and the one after that (three-step launches)
 	call.absorb[4] = call.absorb[3];  // (the embedded pairs' fifth stage: set by the adaptive integrator)
 	call.y0 = c->planes(src);
 	call.yout = c->planes(dst);
@@ -341,7 +340,7 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 	auto sample_due = [&](int64_t s) { return rec && s > 0 && (rec_steps + s) % rec_stride == 0; };  // s: steps of this call taken so far
 	const int stepper = resolve_stepper(lead);
 	if (stepper < 0) return fail(lead, CRD_EINVAL, "fused stepper not available for this configuration");
-	for (int k = 0; k < n; k++) cs[k]->dense.pending = cs[k]->ark.live = false;  // stepping on from the state handed back, not from the integrator's internal one
+	for (int k = 0; k < n; k++) arkode::drop(cs[k]->dense, cs[k]->ark);  // stepping on from the state handed back, not from the integrator's internal one
 	if (nsteps > 0)
 		for (int k = 0; k < n; k++) cs[k]->last_step_t = t0 + (double)(nsteps - 1) * dt, cs[k]->last_step_dt = dt;
 	if (stepper != CRD_STEPPER_FUSED)
@@ -742,17 +741,15 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 	}
 	for (int k = 0; k < n; k++) cs[k]->cycle_pos = -1;  // the integrator exchanges as it needs; a fixed-step call afterwards starts afresh
 	crd_adaptive_stats st{};
-	const double h_cap = o.h_max > 0.0 ? o.h_max : (o.h_max == 0.0 ? crd_stable_dt(&lead->p) : INFINITY);
+	const double h_cap = arkode::h_cap(o, lead->p);
 	const double n_components = 2.0 * (double)lead->g.nx * (double)lead->g.ny;  // WRMS norm over the whole grid
 	constexpr int kEmbedHalo = kStepHalo + 1;                                     // the fifth stage reads one more row
 
 	// Three state planes take turns as y_n, y_{n+1} and scratch: Y and SA (and OUT with dense output).
 	double t = t0;
-	int cur = crd_ctx::Y, spare = crd_ctx::SA, third = dense ? crd_ctx::OUT : -1, prev = -1;
+	arkode::Rotation R = arkode::Rotation::fresh(dense);
 	double t_prev = t0;
-	// A call continues the previous one when it starts at the output time that one handed back and nothing has replaced the state
-	// since (ARKode keeps its memory between ARKode() calls the same way); the ARKode-style controller also needs its own memory.
-	bool resume = dense && t0 == lead->dense.t_out && (!arkode_method || lead->ark.live);
+	bool resume = dense && arkode::resumes(lead->dense, lead->ark, t0, arkode_method);
 	for (int k = 0; k < n; k++)  // (every slab of a group must still hold the step: an upload to one of them alone ends the carry-over for all)
 		resume = resume && cs[k]->dense.pending && cs[k]->dense.t_out == lead->dense.t_out && cs[k]->dense.t_np1 == lead->dense.t_np1;
 	// Under RCCL that decision has to be the RING's (round-3 advice): crd_state_upload on one rank only is allowed between calls, and a
@@ -767,22 +764,17 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 	}
 	for (int k = 0; k < n; k++)
 		if (!resume) cs[k]->dense.pending = false;
-	auto hand_back = [&](double theta, double hstep) -> int {  // interpolant of step prev -> cur at t_prev + theta hstep into plane Y, planes re-labelled
-		// roles now: prev = y_n, cur = y_{n+1}, SB = f_n, ACC = f_{n+1}; the interpolant goes to the remaining state plane
-		const int out = crd_ctx::Y + crd_ctx::SA + crd_ctx::OUT - prev - cur;
+	// The interpolant of the step R.prev -> R.cur (t_n -> t_np1; SB = f_n, ACC = f_{n+1}) at tout into the remaining state plane; then
+	// the step is recorded and the planes are re-labelled (arkode::end_of_call).
+	auto hand_back = [&](double t_n, double t_np1) -> int {
+		const double hstep = t_np1 - t_n;
 		for (int k = 0; k < n; k++) {
 			crd_ctx *c = cs[k];
 			if (int rc = set_device(c)) return rc;
-			HIP_TRY(c, launch_hermite(c->p.precision, c->planes(prev), c->planes(cur), c->planes(crd_ctx::SB), c->planes(crd_ctx::ACC), c->planes(out), c->nx, c->nyl,
-			                          theta, hstep, c->compute));
-			void *b_out[2] = {c->plane[out][0], c->plane[out][1]}, *b_n[2] = {c->plane[prev][0], c->plane[prev][1]},
-			     *b_np1[2] = {c->plane[cur][0], c->plane[cur][1]};
-			for (int f = 0; f < 2; f++) {
-				c->plane[crd_ctx::Y][f] = b_out[f];
-				c->plane[crd_ctx::SA][f] = b_np1[f];
-				c->plane[crd_ctx::OUT][f] = b_n[f];
-			}
+			HIP_TRY(c, launch_hermite(c->p.precision, c->planes(R.prev), c->planes(R.cur), c->planes(crd_ctx::SB), c->planes(crd_ctx::ACC), c->planes(R.interpolant()), c->nx,
+			                          c->nyl, (tout - t_n) / hstep, hstep, c->compute));
 		}
+		for (int k = 0; k < n; k++) arkode::end_of_call(R, true, cs[k]->dense, tout, t_n, t_np1).apply(cs[k]->plane);
 		return CRD_OK;
 	};
 	auto &A = lead->ark;  // (every context of the run gets a copy at the end)
@@ -790,26 +782,21 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 	if (resume) {
 		st.t_internal = lead->dense.t_np1;
 		if (tout <= lead->dense.t_np1) {  // still inside the step the integrator has already taken: interpolate again
-			prev = crd_ctx::OUT;
-			cur = crd_ctx::SA;
-			const double hstep = lead->dense.t_np1 - lead->dense.t_n;
-			if (int rc = hand_back((tout - lead->dense.t_n) / hstep, hstep)) return rc;
-			for (int k = 0; k < n; k++) cs[k]->dense.t_out = tout;
+			R.reinterpolate();
+			if (int rc = hand_back(lead->dense.t_n, lead->dense.t_np1)) return rc;
 			st.t = tout;
 			st.h_next = arkode_method ? A.hprime : std::fmin(o.h0 > 0.0 ? o.h0 : 0.8 * crd_stable_dt(&lead->p), h_cap);
 			if (stats) *stats = st;
 			return CRD_OK;
 		}
 		t = lead->dense.t_np1;
-		cur = crd_ctx::SA;   // the integrator's own state
-		spare = crd_ctx::OUT;  // y_n of the finished step: free
-		third = crd_ctx::Y;    // the interpolant handed back last time: free
+		R.resume();
 	}
 	if (arkode_method) {
 		if (!resume) {  // a fresh state: ARKodeInit
 			arkode::init(A, t0, o.h0);
 			if (arkode::needs_estimate(A, t0, tout))
-				if (int rc = arkode_initial_step(cs, n, t0, tout, cur, o, n_components, &A.h)) return rc;
+				if (int rc = arkode_initial_step(cs, n, t0, tout, R.cur, o, n_components, &A.h)) return rc;
 			arkode::first_step(A, h_cap);
 		}
 		h = A.h;
@@ -861,7 +848,7 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 			if (int rc = set_device(c)) return rc;
 			FusedCall call = make_fused_call(c, tt, hh, src, dst);
 			call.embed = arkode_method ? 2 : 1;
-			call.absorb[4] = arkode_method ? (absorbing(c, tt + 0.75 * hh) ? 1 : 0) : call.absorb[3];  // the fifth stage's time: t + 3/4 h (Zonneveld) / t + h
+			if (arkode_method) step::stage_flags(tt, hh, c->p.t_boundary, 5, call.absorb);  // the fifth stage's time: t + 3/4 h (Zonneveld); RK4(3)'s is t + h, the fourth's
 			call.plan = arkode_method ? &c->plan_arkode : &c->plan_embed;
 			call.rtol = o.rtol;
 			call.atol = o.atol;
@@ -922,19 +909,8 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 		return CRD_OK;
 	};
 	auto attempt = [&](double hh, int dst, double *sum) -> int {  // launch and wait (the RK4(3) pair's loop)
-		if (int rc = launch_attempt(t, hh, cur, dst, 0)) return rc;
+		if (int rc = launch_attempt(t, hh, R.cur, dst, 0)) return rc;
 		return finish_attempt(0, sum);
-	};
-	auto accept_planes = [&](int dst) {  // rotate: the old state becomes y_n (kept for the interpolant), the old y_n / scratch becomes the next target
-		const int old_cur = cur;
-		cur = dst;
-		if (dense) {
-			spare = (prev >= 0) ? prev : third;
-			if (prev < 0) third = -1;
-			prev = old_cur;
-		} else {
-			spare = old_cur;
-		}
 	};
 
 	bool after_reject = false;
@@ -952,18 +928,18 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 			rc = fail(lead, CRD_ESTATE, why);
 			break;
 		}
-		const int dst = spare;
+		const int dst = R.spare;
 		double dsm = 0.0;
 		for (int nef = 0;;) {
 			// This attempt -- unless it is already in flight: the previous step launched it ahead of its own verdict (below).
 			int my_slot;
-			if (ahead.live && ahead.h == A.h && ahead.src == cur && ahead.dst == dst) {
+			if (ahead.live && ahead.h == A.h && ahead.src == R.cur && ahead.dst == dst) {
 				my_slot = ahead.slot;
 				st.launched_ahead++;
 			} else {
 				my_slot = next_slot;
 				next_slot ^= 1;
-				if ((rc = launch_attempt(t, A.h, cur, dst, my_slot))) break;
+				if ((rc = launch_attempt(t, A.h, R.cur, dst, my_slot))) break;
 			}
 			ahead.live = false;
 			// The step after this one, launched BEFORE this one's error norm is known, on the assumption the integrator makes most of
@@ -972,7 +948,7 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 			// accepted; if this step is rejected, y_{n-1} in it is not needed either: the interpolant is built on the LAST step) --
 			// and the next attempt is simply issued afresh.  The host's wait for the norm (reduction over the ranks, copy, wake-up)
 			// then hides under a kernel that is already running.  No exchange is ever issued ahead.
-			const int after = prev >= 0 ? prev : third;
+			const int after = R.ahead();
 			if (after >= 0 && t + A.h < tout && steps_this_call + 1 < o.max_steps && ext_of[dst] >= kEmbedHalo) {
 				if ((rc = launch_attempt(t + A.h, A.h, dst, after, next_slot))) break;
 				ahead = {true, A.h, dst, after, next_slot};
@@ -996,7 +972,7 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 		t_prev = t;
 		arkode::accept(A, dsm, o, h_cap, t, st);
 		steps_this_call++;
-		accept_planes(dst);
+		R.accept(dst, dense);
 	}
 	while (t < tout && rc == CRD_OK && !arkode_method) {
 		// ---- CRD_ADAPT_RK43: the embedded pair and I-controller of rounds 1-2 ----
@@ -1014,7 +990,7 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 			rc = fail(lead, CRD_ESTATE, "adaptive integration: step size underflow");
 			break;
 		}
-		const int dst = spare;
+		const int dst = R.spare;
 		double sum = 0.0;
 		if ((rc = attempt(hh, dst, &sum))) break;
 		const double err = o.bias * std::sqrt(sum / n_components);
@@ -1026,7 +1002,7 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 		if (err <= 1.0) {
 			t_prev = t;
 			t = clipped ? tout : t + hh;
-			accept_planes(dst);
+			R.accept(dst, dense);
 			st.accepted++;
 			if (after_reject) eta = std::fmin(eta, 1.0);  // no growth right after a rejection
 			after_reject = false;
@@ -1052,27 +1028,13 @@ static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double 
 			(void)finish_attempt(slot, &ignored);
 		}
 	st.t_internal = t;
-	if (rc == CRD_OK && dense && prev >= 0 && t >= tout) {
+	if (rc == CRD_OK && dense && R.prev >= 0 && t >= tout) {
 		// ARK_NORMAL: the step t_prev -> t has reached or passed tout.  f at both ends, then the cubic Hermite interpolant at tout.
-		const double hstep = t - t_prev;
-		if ((rc = rhs_on_planes(cs, n, t_prev, prev, crd_ctx::SB)) == CRD_OK && (rc = rhs_on_planes(cs, n, t, cur, crd_ctx::ACC)) == CRD_OK &&
-		    (rc = hand_back((tout - t_prev) / hstep, hstep)) == CRD_OK) {
-			for (int k = 0; k < n; k++) {
-				cs[k]->dense.pending = true;
-				cs[k]->dense.t_out = tout;
-				cs[k]->dense.t_n = t_prev;
-				cs[k]->dense.t_np1 = t;
-			}
+		if ((rc = rhs_on_planes(cs, n, t_prev, R.prev, crd_ctx::SB)) == CRD_OK && (rc = rhs_on_planes(cs, n, t, R.cur, crd_ctx::ACC)) == CRD_OK &&
+		    (rc = hand_back(t_prev, t)) == CRD_OK)
 			t = tout;
-		}
 	} else {  // no dense output (or a zero-length interval, or an error): hand back the state reached
-		for (int k = 0; k < n; k++) {
-			if (cur != crd_ctx::Y) {
-				std::swap(cs[k]->plane[crd_ctx::Y][0], cs[k]->plane[cur][0]);
-				std::swap(cs[k]->plane[crd_ctx::Y][1], cs[k]->plane[cur][1]);
-			}
-			cs[k]->dense.pending = false;
-		}
+		for (int k = 0; k < n; k++) arkode::end_of_call(R, false, cs[k]->dense, tout, t_prev, t).apply(cs[k]->plane);
 	}
 	if (arkode_method) {
 		A.live = rc == CRD_OK && lead->dense.pending;
