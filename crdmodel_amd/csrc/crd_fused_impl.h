@@ -29,6 +29,7 @@
 #include <utility>
 
 #include "crd_device.h"
+#include "crd_edge_waits.h"
 #include "crd_step.h"
 #include "crd_tuning.h"
 
@@ -190,6 +191,21 @@ constexpr bool kScalarRows = false;
 template <typename Real, int MODEL, int COLS, int STEPS>
 constexpr bool kScalarRows = kReadAhead<Real, MODEL, COLS, STEPS>;
 #endif
+// ... and takes the neighbours' edge values AS EACH READ LANDS (round 11).  Behind an iteration's barrier every wavefront of the block
+// issues its six ds_read_b128 in the same few cycles against the CU's one LDS; one `s_waitcnt lgkmcnt(0)` in front of the iteration's
+// first stage held every wavefront until its LAST read was back, though step 0's stages 1 and 2 need only the first.  LDS operations
+// return in issue order, so a counted wait retires all but the newest N (crd_edge_waits.h has the counting): 0 = the single wait,
+// 1 = two waits (read 0; the rest in front of step 0's stage 3), 2 = one wait per step, 3 = one wait per read, each in front of the
+// stage that first needs it.  profiles/r11/edge_ladder_ab.txt has the three measured against the single wait.
+// (The probe builds that drop publishes or stages issue other operations than the counts assume: they keep the single wait.)
+#if defined(CRD_NO_EDGE_LADDER) || defined(CRD_PROBE_NOPUBLISH) || defined(CRD_PROBE_NOMATH) || defined(CRD_PROBE_HALFMATH)  // (experiment switch: the single wait for all six reads)
+#undef CRD_EDGE_LADDER
+#define CRD_EDGE_LADDER 0
+#elif !defined(CRD_EDGE_LADDER)  // (experiment switch: -DCRD_EDGE_LADDER=1 / 2 / 3)
+#define CRD_EDGE_LADDER 3
+#endif
+template <typename Real, int MODEL, int COLS, int STEPS>
+constexpr int kEdgeLadder = kReadAhead<Real, MODEL, COLS, STEPS> ? CRD_EDGE_LADDER : 0;
 // The eight-wide block strip (launch-plan chunk mode 3): the three-step fp64 FHN kernel with EIGHT wavefronts around one apron -- 488 valid
 // lanes of 512 instead of 232 of 256 -- as the only block of its CU (244 VGPRs: eight wavefronts per CU).
 constexpr int kWideWaves = 8;
@@ -758,6 +774,32 @@ __device__ __forceinline__ void ring_row_landed(double2r (&e)[6])
 {
 	asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]) : : "memory");
 }
+// (kEdgeLadder) ... or the counted waits in its place: at most N operations of the LGKM counter outstanding, which retires the reads
+// named -- exactly the ones the statement releases, so that nothing reads them above it (tools/kernel_regs.py: async_lds_read_hazards
+// counts the LDS instructions behind each read along every path and stops the build where a wait is too lax for its place).
+template <int N>
+__device__ __forceinline__ void edge_landed(double2r &e0)
+{
+	static_assert(N >= 0 && N <= edge_waits::kLgkmcntMax, "lgkmcnt is four bits");
+	asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(e0) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void edge_landed(double2r &e0, double2r &e1)
+{
+	static_assert(N >= 0 && N <= edge_waits::kLgkmcntMax, "lgkmcnt is four bits");
+	asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(e0), "+v"(e1) : "n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void edge_landed(double2r &e0, double2r &e1, double2r &e2, double2r &e3, double2r &e4)
+{
+	static_assert(N >= 0 && N <= edge_waits::kLgkmcntMax, "lgkmcnt is four bits");
+	asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3), "+v"(e4) : "n"(N) : "memory");
+}
+// (what the stages call in front of stage 1 and stage 3 where no counted wait sits: nothing, and no state)
+struct NoEdgeWait {
+	template <typename H>
+	__device__ __forceinline__ void operator()(H) const {}
+};
 // (the first row, read in front of the loop: no barrier wait has seen it)
 __device__ __forceinline__ void ring_first_row_landed(double &u, double &v)
 {
@@ -769,8 +811,23 @@ template <int N>
 __device__ __forceinline__ void ring_row_landed(double2r (&)[N]) {}
 template <typename V>
 __device__ __forceinline__ void ring_first_row_landed(V &, V &) {}
+// (kEdgeLadder) ... and the b(j) the iteration loaded behind its last counted wait: an operand too, so that the compiler's own wait for the
+// loaded value -- an `s_waitcnt lgkmcnt(0)` in front of its first use, wherever the scheduler puts that -- stands HERE, beside the wait
+// this statement begins with, and not between the next iteration's edge reads and its counted waits, which it would undo.
+template <int OFF>
+__device__ __forceinline__ void edge_exchange(unsigned con, double2r (&e)[6], double &u, double &v, double &sb)
+{
+	asm volatile("s_waitcnt lgkmcnt(0)\n\t" CRD_EDGE_BARRIER "\n\ts_mov_b64 exec, %10\n\tds_read_b128 %0, %9 offset:%11\n\tds_read_b128 %1, %9 offset:%12\n\t"
+	             "ds_read_b128 %2, %9 offset:%13\n\tds_read_b128 %3, %9 offset:%14\n\tds_read_b128 %4, %9 offset:%15\n\tds_read_b128 %5, %9 offset:%16\n\t"
+	             "s_mov_b64 exec, -1"
+	             : "=&v"(e[0]), "=&v"(e[1]), "=&v"(e[2]), "=&v"(e[3]), "=&v"(e[4]), "=&v"(e[5]), "+v"(u), "+v"(v), "+s"(sb)
+	             : "v"(con), "s"(kEdgeLanes), "n"(OFF), "n"(OFF + 16), "n"(OFF + 32), "n"(OFF + 48), "n"(OFF + 64), "n"(OFF + 80)
+	             : "memory");
+}
 template <int OFF, typename V, int N>
 __device__ __forceinline__ void edge_exchange(unsigned, double2r (&)[N], V &, V &) {}
+template <int OFF, typename V, typename S, int N>
+__device__ __forceinline__ void edge_exchange(unsigned, double2r (&)[N], V &, V &, S &) {}
 // LDS bytes of a block's rings
 template <typename Real, int COLS, int STEPS = 2, int WAVES = kMaxWavesPerBlock>
 constexpr int kRingBytes = WAVES * kRingRowsOf<typename LaneValue<Real, COLS>::type, STEPS> * 2 * kLanes * COLS * (int)sizeof(Real);
@@ -787,7 +844,10 @@ constexpr int kRingBytes = WAVES * kRingRowsOf<typename LaneValue<Real, COLS>::t
 // Slot arithmetic: row r of either pipeline lives in slot r mod 4; the second pipeline's rows are the first one's shifted by 4,
 // i.e. the SAME slots -- the stage code is one lambda applied to two sets of arrays.  Per point the arithmetic is the sequence of
 // two single steps exactly (same fused multiply-adds, same constants), so the result is theirs bit for bit.
-template <typename Real, int MODEL, bool ABSORB, int COLS, bool NT, int STEPS = 2, int WAVES = kMaxWavesPerBlock>
+// (COUNTED: the kernel may take its edge values by counted waits, kEdgeLadder above.  The kernel with the absorbing-row selects, which
+// holds both bodies, may not: at its 106 scalar registers the compiler reloads kernel arguments where it likes -- an `s_load` between
+// the edge reads and a counted wait in the tail's code, which the build's contract check refuses -- and keeps the single wait in both.)
+template <typename Real, int MODEL, bool ABSORB, int COLS, bool NT, int STEPS = 2, int WAVES = kMaxWavesPerBlock, bool COUNTED = true>
 __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const FusedArgs<Real> &a, const int strip, const int chunk, lds_char *const block_rings,
                                                       const int sblk = 0, lds_char *const block_edges = nullptr)
 {
@@ -824,6 +884,13 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	constexpr bool AHEAD = kReadAhead<Real, MODEL, COLS, STEPS>;
 	constexpr int kWaitAhead = kWaitFill + 2 * (kRingRows - 1);
 	static_assert(kWaitAhead <= 63, "vmcnt is six bits");
+	// (kEdgeLadder) The same argument on the LGKM counter for the edge reads, which come back in issue order like the fills: behind edge
+	// read k of the previous iteration's exchange lie the 5 - k later reads and what this iteration has issued so far -- the publish of
+	// u0, per step the publish of its input row (steps 1 and 2) and of its three stage values, the two reads of the read ahead behind
+	// step 0.  In front of stage 1 / stage 3 of steps 0, 1, 2 that is 5 + 1 = 6, 4 + 3 = 7, 3 + 7 = 10, 2 + 9 = 11, 1 + 11 = 12 and
+	// 0 + 13 = 13 operations: `s_waitcnt lgkmcnt(N)` with that N leaves at most those outstanding, so read k is back.  The numbers are
+	// edge_waits::ladder_wait(STEPS, n, h), computed from the same quantities (crd_edge_waits.h), none above the field's 15; they hold
+	// while no scalar memory load is in flight, which returns out of order on the same counter (next_b, below).
 	// (kReadAhead, the fill in the shadow of the edge reads) Publish, fill and row scalars of an iteration sit between the reads the previous
 	// iteration's barrier released (edge_exchange) and the wait for them (ring_row_landed) instead of behind that wait.  The fill was the
 	// first vector-memory operation of its iteration before and is so now, the stores the last: a wavefront's sequence -- fill q, stores q,
@@ -1000,12 +1067,13 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		if constexpr (COOP) rhs_lane_edge<MODEL>(uC, X, uS, uN, v, cE, cWn, cP, rowp, ka4, zero, du, dv);
 		else rhs_lane<V, MODEL>(uC, uS, uN, v, cE, cWn, cP, rowp, ka4, zero, du, dv);
 	};
-	auto stages = [&](Pipe &Q, const int p, auto kk, auto live_c, const int flag_bit, const Real b4, V &nu, V &nv, [[maybe_unused]] const V (&E)[4], auto qbase_c) {
+	auto stages = [&](Pipe &Q, const int p, auto kk, auto live_c, const int flag_bit, const Real b4, V &nu, V &nv, [[maybe_unused]] const V (&E)[4], auto qbase_c, [[maybe_unused]] auto landed) {
 		constexpr int K = decltype(kk)::value;
 		[[maybe_unused]] constexpr int PUB = (K & 1) * kEdgeParityBytes<STEPS, WAVES> + decltype(qbase_c)::value * 8;
 		constexpr int live = decltype(live_c)::value;  // (compile-time: the filling iterations are so many pieces of straight-line code)
 		constexpr int S0 = K % M, S1 = (K + M - 1) % M, S2 = (K + M - 2) % M, S3 = (K + M - 3) % M, S4 = (K + 2 * M - 4) % M, S5 = (K + 2 * M - 5) % M;
 		V du, dv;
+		landed(std::integral_constant<int, 0>{});  // (kEdgeLadder: E[0], E[1] -- or nothing)
 		if constexpr (live >= 2) {
 			point(Q.u0[S1], Q.u0[S2], Q.u0[S0], Q.v0[S1], Q.bq[S1], ABSORB && ((amask >> (flag_bit + 0)) & 1) && boundary_row(p - 1), E[0], du, dv);
 			Q.U1[S1] = stage_fma(h2, du, Q.u0[S1]);
@@ -1022,6 +1090,7 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			Q.aU[S2] = stage_fma(h3, du, Q.aU[S2]);
 			Q.aV[S2] = stage_fma(h3, dv, Q.aV[S2]);
 		}
+		landed(std::integral_constant<int, 1>{});  // (kEdgeLadder: E[2], E[3] -- or nothing)
 		if constexpr (live >= 6) {
 			point(Q.U2[S3], Q.U2[S4], Q.U2[S2], Q.V2[S3 & 1], Q.bq[S3], ABSORB && ((amask >> (flag_bit + 2)) & 1) && boundary_row(p - 3), E[2], du, dv);
 			Q.U3[S3] = stage_fma(h1, du, Q.u0[S3]);
@@ -1064,8 +1133,11 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		if (!AHEAD && m < FILL + kRingRows) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitFill) : "memory");  // (fewer operations in flight while no rows come out yet)
 		V E[STEPS][4];
 		// b(j) of row p into its slot, row p + kRingRows into the ring slot row p came out of, and the row the next fill takes
+		// (kEdgeLadder) An iteration behind the fill takes the edge values read by read (LADDER: 1, 2 or 3 -- kEdgeLadder above); the
+		// filling iterations skip stages and publishes, their counts differ, and they keep the single wait.
+		constexpr int LADDER = (FED >= FILL && COUNTED) ? kEdgeLadder<Real, MODEL, COLS, STEPS> : 0;
 		auto take_row = [&]() {
-			P[0].bq[S0] = uniform(pb);
+			if constexpr (LADDER == 0) P[0].bq[S0] = uniform(pb);  // (kEdgeLadder: behind the iteration's last counted wait, see there)
 #ifndef CRD_PROBE_NOLOAD  // (probe builds, tools/build_variant.sh: what a launch costs without its row reads / its later steps / its stores)
 			if constexpr (SROWS) fill_from(sr.in_u, sr.in_v, sr.in_off, trip_byte + S0 * SLOT);
 			else fill(jn, trip_byte + S0 * SLOT);  // ... and row p + kRingRows into it
@@ -1097,12 +1169,15 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 			take_row();
 			if constexpr (K == M - 1) next_trip();  // (the read ahead below is the next trip's first slot)
 			// ... and only now the wait for the neighbours' edge values
-			ring_row_landed(edge);
-			// The scalar load of the next b(j) goes out BEHIND that wait: it returns on the same counter as the edge reads, and in front of the
-			// wait the wavefront would stand for its latency as well.  The barrier's wait is the next to see it, a whole iteration later.
-			next_b();
+			if constexpr (LADDER == 0) {
+				ring_row_landed(edge);
+				// The scalar load of the next b(j) goes out BEHIND that wait: it returns on the same counter as the edge reads, and in front of the
+				// wait the wavefront would stand for its latency as well.  The barrier's wait is the next to see it, a whole iteration later.
+				next_b();
 #pragma unroll
-			for (int n = 0; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
+				for (int n = 0; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
+			}
+			// (kEdgeLadder: ... read by read, in front of the stages -- `landed` below)
 		} else if constexpr (COOP) {
 			// ... together with the neighbours' edge values, whose reads the previous iteration issued behind its barrier
 			ring_read_with_edges<kWaitSteady, S0 * SLOT, S0 * SLOT + RB>(ring_trip, P[0].u0[S0], P[0].v0[S0], edge);
@@ -1148,7 +1223,47 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 				    if constexpr (COOP) edge_publish<(K & 1) * kEdgeParityBytes<STEPS, WAVES> + 32 * N>(edge_pub, nu);
 			    }
 			    constexpr int live = FED - 8 * N < 0 ? 0 : (FED - 8 * N > 8 ? 8 : FED - 8 * N);
-			    stages(P[N], p - kApron * N, kk, std::integral_constant<int, live>{}, 4 * N, b4[N], nu, nv, E[N], std::integral_constant<int, 4 * N>{});
+			    // (kEdgeLadder) What the stages call in front of stage 1 (H = 0) and stage 3 (H = 1): the counted wait for the edge reads that
+			    // have to be back there, and only behind it the values out of their registers.  The counts: crd_edge_waits.h, from the
+			    // iteration's operations as they are written here -- u0's publish in take_row's place, then per step the publish of its input
+			    // row, stages and stage publishes, the read ahead behind step 0.  Behind the iteration's LAST counted wait sit the two
+			    // things that must not come between an edge read and a counted wait: the first use of the b(j) loaded an iteration ago --
+			    // the compiler puts its own `s_waitcnt lgkmcnt(0)` in front of it, which above would undo every counted wait -- and the
+			    // scalar load of the next one, which returns out of order on the same counter (the barrier's wait retires it).
+			    [[maybe_unused]] auto landed = [&](auto hh) {
+				    [[maybe_unused]] constexpr int H = decltype(hh)::value;
+				    static_assert(LADDER == 0 || (STEPS == 3 && live == 8), "the counted waits: three steps, every stage and publish of the iteration");
+				    if constexpr (LADDER != 0) {
+					    using namespace edge_waits;
+					    bool last = false;
+					    if constexpr (LADDER == 3) {
+						    edge_landed<ladder_wait(STEPS, N, H)>(edge[2 * N + H]);
+						    E[N][2 * H] = edge[2 * N + H].x, E[N][2 * H + 1] = edge[2 * N + H].y;
+						    last = N == STEPS - 1 && H == 1;
+					    } else if constexpr (LADDER == 2) {
+						    if constexpr (H == 0) {
+							    edge_landed<step_wait(STEPS, N)>(edge[2 * N], edge[2 * N + 1]);
+							    E[N][0] = edge[2 * N].x, E[N][1] = edge[2 * N].y, E[N][2] = edge[2 * N + 1].x, E[N][3] = edge[2 * N + 1].y;
+							    last = N == STEPS - 1;
+						    }
+					    } else if constexpr (N == 0 && H == 0) {
+						    edge_landed<ladder_wait(STEPS, 0, 0)>(edge[0]);
+						    E[0][0] = edge[0].x, E[0][1] = edge[0].y;
+					    } else if constexpr (N == 0) {
+						    edge_landed<rest_wait(STEPS)>(edge[1], edge[2], edge[3], edge[4], edge[5]);
+						    E[0][2] = edge[1].x, E[0][3] = edge[1].y;
+#pragma unroll
+						    for (int n = 1; n < STEPS; n++) E[n][0] = edge[2 * n].x, E[n][1] = edge[2 * n].y, E[n][2] = edge[2 * n + 1].x, E[n][3] = edge[2 * n + 1].y;
+						    last = true;
+					    }
+					    if (last) {
+						    P[0].bq[S0] = uniform(pb);
+						    next_b();
+					    }
+				    }
+			    };
+			    if constexpr (LADDER != 0) stages(P[N], p - kApron * N, kk, std::integral_constant<int, live>{}, 4 * N, b4[N], nu, nv, E[N], std::integral_constant<int, 4 * N>{}, landed);
+			    else stages(P[N], p - kApron * N, kk, std::integral_constant<int, live>{}, 4 * N, b4[N], nu, nv, E[N], std::integral_constant<int, 4 * N>{}, NoEdgeWait{});
 			    if constexpr (AHEAD && N == 0) read_ahead();
 		    },
 		    std::make_integer_sequence<int, STEPS>{});
@@ -1195,7 +1310,8 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 		// (COOP) what the block's wavefronts published during this iteration is complete beyond the barrier; the reads of what the next
 		// iteration needs of it go out at once and land while that iteration waits for its row
 		// (kReadAhead: ... and its wait retires the read of the next row, whose registers it names)
-		if constexpr (AHEAD) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge, P[0].u0[(K + 1) % M], P[0].v0[(K + 1) % M]);
+		if constexpr (LADDER != 0) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge, P[0].u0[(K + 1) % M], P[0].v0[(K + 1) % M], pb);
+		else if constexpr (AHEAD) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge, P[0].u0[(K + 1) % M], P[0].v0[(K + 1) % M]);
 		else if constexpr (COOP) edge_exchange<(K & 1) * kEdgeParityBytes<STEPS, WAVES>>(edge_con, edge);
 	};
 	int m = 0;
@@ -1304,8 +1420,8 @@ __global__ void __launch_bounds__(kLanes *WAVES) __attribute__((amdgpu_waves_per
 		const int lo = a.js + j0 - APRON, hi1 = a.js + j1 + APRON;  // (lo > -ny and hi1 < 3 ny: a slab is at most the grid, ghost rows at most a slab)
 		const bool touches = (lo <= 0 && 0 <= hi1) || (lo <= a.ny && a.ny <= hi1) || (lo <= 2 * a.ny && 2 * a.ny <= hi1);
 		if constexpr (STEPS >= 2) {
-			if (touches) fused_item_multi_step<Real, MODEL, true, COLS, NT, STEPS>(s, a, strip, chunk, block_rings, sblk, block_edges);
-			else fused_item_multi_step<Real, MODEL, false, COLS, NT, STEPS>(s, a, strip, chunk, block_rings, sblk, block_edges);
+			if (touches) fused_item_multi_step<Real, MODEL, true, COLS, NT, STEPS, kMaxWavesPerBlock, false>(s, a, strip, chunk, block_rings, sblk, block_edges);
+			else fused_item_multi_step<Real, MODEL, false, COLS, NT, STEPS, kMaxWavesPerBlock, false>(s, a, strip, chunk, block_rings, sblk, block_edges);
 		} else {
 			if (touches) fused_item<Real, MODEL, true, EMBED, COLS, NT>(s, a, strip, chunk);
 			else fused_item<Real, MODEL, false, EMBED, COLS, NT>(s, a, strip, chunk);

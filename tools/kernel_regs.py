@@ -99,7 +99,7 @@ def _regs_of(ln):
 
 def async_lds_read_hazards(body):
     """LDS reads an asm block issues WITHOUT waiting for them, whose destination registers something touches before an asm block's
-    `s_waitcnt lgkmcnt(0)`: [(line, register, offending instruction)].
+    wait has retired them: [(line, register, offending instruction)].
 
     The block-strip kernels issue the reads of the neighbours' edge values at the END of an iteration (crd_fused_impl.h: edge_exchange) and
     wait for them at the start of the next (ring_read_with_edges), so that the LDS latency hides under the loop's turn-around.  The
@@ -112,7 +112,15 @@ def async_lds_read_hazards(body):
     The three-step block strip's read of the NEXT row (ring_read_ahead: two ds_read_b64 issued behind the first step's stages, retired
     by the wait in front of the same iteration's barrier in edge_exchange) is found the same way -- any ds_read of an asm block without
     its own wait -- and twice did its work while that read was being written: a second register set that the compiler copied with the
-    read in flight, and the read behind an item's last row, whose registers, dead to the compiler, went to the next stage's temporaries."""
+    read in flight, and the read behind an item's last row, whose registers, dead to the compiler, went to the next stage's temporaries.
+
+    What retires a read: an asm block's `s_waitcnt lgkmcnt(0)`, always; and an asm block's COUNTED `s_waitcnt lgkmcnt(N)` (round 11: the
+    three-step block strip takes its edge values read by read, crd_edge_waits.h) when at least N LDS instructions of asm blocks were issued
+    behind the read on the path walked -- LDS operations return in issue order, the wait leaves the newest N outstanding -- and no scalar
+    memory load (`s_load*`, `s_buffer_load*`) was met between the read and the wait: SMEM returns out of order on the same counter, and
+    with one possibly in flight a count above zero proves nothing.  Only instructions inside asm blocks are counted (the compiler's own
+    LDS instructions could only add to the count), every path keeps its own count, and a place reached again is walked again whenever it
+    is reached with fewer instructions behind the read, or with a scalar load in flight for the first time."""
     n = len(body)
     label_at = {}
     for k, ln in enumerate(body):
@@ -139,34 +147,79 @@ def async_lds_read_hazards(body):
         if any(re.match(r"\s*s_waitcnt\b.*lgkmcnt\(0\)", body[q]) for q in range(k + 1, e)):
             continue
         dst = _regs_of(t.split(",")[0])
-        seen, stack = set(), [e + 1]
+        # (behind: LDS instructions of asm blocks issued after the read -- the later reads of its own block to begin with --, capped where
+        # the counter's field ends; smem: a scalar memory load met on the way)
+        behind0 = sum(1 for q in range(k + 1, e) if body[q].strip().startswith("ds_"))
+        seen, stack = {}, [(e + 1, min(behind0, LGKMCNT_MAX + 1), False)]
         while stack:
-            q = stack.pop()
+            q, behind, smem = stack.pop()
             steps = 0
             while q < n and steps < 4000:
-                if q in seen:
+                if q in seen and seen[q][0] <= behind and (seen[q][1] or not smem):
                     break
-                seen.add(q)
+                if q in seen:
+                    behind, smem = min(behind, seen[q][0]), smem or seen[q][1]
+                seen[q] = (behind, smem)
                 steps += 1
                 u = body[q].strip()
-                if in_asm[q] and re.match(r"s_waitcnt\b.*lgkmcnt\(0\)", u):
+                w = re.match(r"s_waitcnt\b.*lgkmcnt\((\d+)\)", u) if in_asm[q] else None
+                if w and (int(w.group(1)) == 0 or (behind >= int(w.group(1)) and not smem)):
                     break  # landed
                 if u and not u.startswith((";", ".")) and not u.endswith(":"):
                     op = u.split()[0]
                     if op == "s_endpgm":
                         break
+                    if op.startswith(("s_load", "s_buffer_load")):
+                        smem = True
+                    # (the compiler's own `s_waitcnt lgkmcnt(0)`, in front of the first use of what it loaded: no scalar load is in flight
+                    # behind it.  It lands no read for this check -- only an asm block's wait does, as before)
+                    if op == "s_waitcnt" and re.search(r"lgkmcnt\(0\)", u):
+                        smem = False
                     hit = dst & _regs_of(u)
                     # (the reads of one exchange sit in one asm block: its own other reads name other registers)
                     if hit and not (in_asm[q] and op.startswith("ds_read") and not (dst & _regs_of(u.split(",")[0]))):
                         found.append((k, min(hit), u))
                         break
+                    if in_asm[q] and op.startswith("ds_"):
+                        behind = min(behind + 1, LGKMCNT_MAX + 1)
                     mb = re.match(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", u)
                     if mb and mb.group(1) in label_at:
-                        stack.append(label_at[mb.group(1)])
+                        stack.append((label_at[mb.group(1)], behind, smem))
                         if op == "s_branch":
                             break
                 q += 1
     return found
+
+
+def lgkm_waits_in_edge_window(loop):
+    """The compiler's own `s_waitcnt` with an lgkmcnt field (outside asm blocks) that sit, in the steady-state loop, between the edge reads an
+    asm block issues behind the barrier and the LAST stand-alone asm wait on lgkmcnt of the iteration those reads feed -- the single
+    `s_waitcnt lgkmcnt(0)` in front of the first stage, or the last of the counted waits in its place.  Such a wait is an
+    `lgkmcnt(0)` for a scalar load's value in practice and holds the wavefront for ALL its edge reads, whatever the counted waits behind it
+    would have let through.  None for a kernel whose loop has no such window (no asm block that is a wait on lgkmcnt and nothing else).
+    A performance figure: it stops nothing."""
+    lines = [ln.strip() for ln in loop]
+    blocks, start = [], None  # asm blocks as (first, last) line numbers
+    for k, ln in enumerate(lines):
+        if "#ASMSTART" in ln:
+            start = k
+        if "#ASMEND" in ln and start is not None:
+            blocks.append((start, k))
+            start = None
+    inside = set(q for a, b in blocks for q in range(a, b + 1))
+    code = lambda a, b: [lines[q] for q in range(a, b + 1) if lines[q] and not lines[q].startswith((";", "."))]
+    reads = [a for a, b in blocks if sum(1 for u in code(a, b) if u.startswith("ds_read_b128")) >= 2 and not re.match(r"s_waitcnt\b.*lgkmcnt", code(a, b)[-1])]
+    waits = [a for a, b in blocks if len(code(a, b)) == 1 and re.match(r"s_waitcnt\b.*lgkmcnt\(\d+\)", code(a, b)[0])]
+    if not reads or not waits:
+        return None
+    count, n = 0, len(lines)
+    for r in reads:  # the window of the reads at line r: on to the next exchange, around the loop's back edge
+        nxt = min((x for x in reads if x > r), default=reads[0] + n)
+        last = max((w + (n if w < r else 0) for w in waits if r < w + (n if w < r else 0) < nxt), default=None)
+        if last is None:
+            continue
+        count += sum(1 for q in range(r, last) if (q % n) not in inside and re.match(r"s_waitcnt\b.*lgkmcnt\(", lines[q % n]))
+    return count
 
 
 def parse(text):
@@ -191,7 +244,7 @@ def parse(text):
             m = re.match(r"^(\.LBB\d+_\d+):", ln)
             if m:
                 label_at[m.group(1)] = k
-        best = None
+        best, best_loop = None, []
         for label, k0 in label_at.items():
             if "Loop Header" not in body[k0] and not (k0 + 1 < len(body) and body[k0 + 1].lstrip().startswith(";") and "Loop Header" in body[k0 + 1]):
                 continue
@@ -213,10 +266,11 @@ def parse(text):
                     mix["nops"] += 1
             mix["total"] = sum(v for k_, v in mix.items() if k_ not in ("moves", "nops"))
             if best is None or mix["valu"] > best["valu"]:
-                best = mix
+                best, best_loop = mix, body[k0:back[-1] + 1]
         # (LDS-DMA fills: the kernels whose waits count vector-memory operations by hand -- the ones check_only holds to exec_skipped_vmem)
         lds_dma = any(re.match(r"\s*buffer_load_\w+\s.*\blds\b", ln) for ln in body)
         kernels.append({"mangled": name, "lds_dma": lds_dma, "exec_skipped_vmem": len(exec_skipped_vmem(body)), "async_lds_read_hazards": len(async_lds_read_hazards(body)),
+                        "lgkm_waits_in_edge_window": lgkm_waits_in_edge_window(best_loop),
                         "vgprs": meta.get("NumVgprs", 0), "sgprs": meta.get("TotalNumSgprs", meta.get("NumSgprs", 0)), "scratch": meta.get("ScratchSize", 0),
                         "occupancy": meta.get("Occupancy", 0), "lds": meta.get("LDSByteSize", 0), "loop": best or {"valu": 0, "salu": 0, "vmem": 0, "lds": 0, "other": 0, "moves": 0, "nops": 0, "total": 0}})
     for k, nm in zip(kernels, demangle([k["mangled"] for k in kernels])):
@@ -235,6 +289,8 @@ def table_digest(rows):
 
 
 # (the eighth argument: wavefronts per block -- 4 everywhere but in the eight-wide three-step block strip)
+LGKMCNT_MAX = 15  # gfx9: s_waitcnt's lgkmcnt field is four bits
+
 STEP_KERNEL = re.compile(r"crd_rk4_fused_step_kernel<(double|float), (\d+), (true|false), (\d+), (\d+), (true|false), (\d+)(?:, (\d+))?>")
 
 
@@ -291,6 +347,10 @@ def main():
                          "nt": int(nt == "true"), "steps": int(steps), "vgprs": k["vgprs"], "sgprs": k["sgprs"], "lds_bytes": k["lds"], "scratch_bytes": k["scratch"],
                          "wavefronts_per_simd": k["occupancy"], "loop": k["loop"], "exec_skipped_vmem": k["exec_skipped_vmem"],
                          "async_lds_read_hazards": k["async_lds_read_hazards"]})
+            # (round 11; a performance figure, in the JSON alone -- the C table's ABI stays -- and only where the loop has such a window: the
+            # other kernels' rows, and the digests over them, are what they were)
+            if k["lgkm_waits_in_edge_window"] is not None:
+                rows[-1]["lgkm_waits_in_edge_window"] = k["lgkm_waits_in_edge_window"]
             if int(waves or 4) != 4:  # (a row of the usual width carries no such key: its text, and the digests over it, are what they were)
                 rows[-1]["waves"] = int(waves)
     # The vmcnt contract of the multi-step pipelines (exec_skipped_vmem above) and the edge reads' registers (async_lds_read_hazards): a build
@@ -313,7 +373,8 @@ def main():
     for k in kernels:
         lp = k["loop"]
         print("%-64s %5d %5d %7d %4d %6d | %11d %5d %5d %4d %6d | %d" % (k["name"][:64], k["vgprs"], k["sgprs"], k["scratch"], k["occupancy"], k["lds"], lp["valu"], lp["salu"],
-                                                                          lp["vmem"], lp["lds"], lp["total"], k["exec_skipped_vmem"]) + (" | async LDS read hazards: %d" % k["async_lds_read_hazards"] if k["async_lds_read_hazards"] else ""))
+                                                                          lp["vmem"], lp["lds"], lp["total"], k["exec_skipped_vmem"]) + (" | async LDS read hazards: %d" % k["async_lds_read_hazards"] if k["async_lds_read_hazards"] else "")
+              + (" | lgkm waits in edge window: %d" % k["lgkm_waits_in_edge_window"] if k["lgkm_waits_in_edge_window"] is not None else ""))
     if a.table:
         with open(a.table, "w") as f:
             f.write("// generated by tools/kernel_regs.py from the assembly of this build's step kernels -- do not edit\n")
