@@ -114,6 +114,12 @@ class StepTiming(C.Structure):
                 ("agreement_restarts", C.c_int64)]
 
 
+class PsolveOptions(C.Structure):
+    """crd_psolve_options"""
+
+    _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("coarse", C.c_int32), ("max_levels", C.c_int32), ("omega", C.c_double)]
+
+
 OBSERVE_MAX_PROBES = 16  # CRD_OBSERVE_MAX_PROBES
 
 
@@ -187,6 +193,10 @@ _SIGNATURES = {
     "crd_rhs_part_device": (C.c_int, [_vp, C.c_double, C.c_int, _vp, _vp]),
     "crd_jtimes_host": (C.c_int, [_vp, C.c_double, C.c_int, _vp, _vp, _vp]),
     "crd_jtimes_device": (C.c_int, [_vp, C.c_double, C.c_int, _vp, _vp, _vp]),
+    "crd_psolve_defaults": (C.c_int, [C.POINTER(PsolveOptions)]),
+    "crd_psolve_info": (C.c_int, [_vp, C.POINTER(PsolveOptions), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "crd_psolve_device": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(PsolveOptions), _vp, _vp]),
+    "crd_psolve_host": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(PsolveOptions), _vp, _vp]),
     "crd_set_stepper": (C.c_int, [_vp, C.c_int]),
     "crd_step_rk4": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64]),
     "crd_synchronize": (C.c_int, [_vp]),

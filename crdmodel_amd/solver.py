@@ -283,6 +283,29 @@ class Slab:
         self._check(lib().crd_jtimes_host(self._h, t, _part(part), y.ctypes.data, v.ctypes.data, jv.ctypes.data), "crd_jtimes_host")
         return jv
 
+    @staticmethod
+    def _psolve_options(pre, post, coarse, max_levels, omega):
+        opt = capi.PsolveOptions()
+        opt.pre, opt.post, opt.coarse, opt.max_levels, opt.omega = pre, post, coarse, max_levels, omega
+        return opt
+
+    def psolve(self, t, gamma, r, pre=2, post=2, coarse=8, max_levels=16, omega=0.8):
+        """z = M r, M one multigrid V-cycle for (I - gamma J_D(t)) z = r: the preconditioner solve of an implicit stage (crd_psolve_host).
+        r is laid out like y; var1 of z is var1 of r."""
+        r = self._vector(r)
+        z = np.empty_like(r)
+        opt = self._psolve_options(pre, post, coarse, max_levels, omega)
+        self._check(lib().crd_psolve_host(self._h, t, gamma, C.byref(opt), r.ctypes.data, z.ctypes.data), "crd_psolve_host")
+        return z
+
+    def psolve_info(self, pre=2, post=2, coarse=8, max_levels=16, omega=0.8):
+        """(levels, [(nx, ny) per level], workspace bytes) of Slab.psolve with these options (crd_psolve_info)."""
+        opt = self._psolve_options(pre, post, coarse, max_levels, omega)
+        levels, nbytes = C.c_int32(), C.c_int64()
+        nx, ny = (C.c_int32 * 16)(), (C.c_int32 * 16)()
+        self._check(lib().crd_psolve_info(self._h, C.byref(opt), C.byref(levels), nx, ny, C.byref(nbytes)), "crd_psolve_info")
+        return levels.value, [(nx[k], ny[k]) for k in range(levels.value)], nbytes.value
+
     # -- time stepping -----------------------------------------------------------------------------------------
     def set_stepper(self, stepper):
         s = STEPPERS[stepper] if isinstance(stepper, str) else stepper

@@ -311,6 +311,38 @@ int crd_rhs_part_host(crd_ctx *ctx, double t, int part, const void *y_aos, void 
 int crd_jtimes_device(crd_ctx *ctx, double t, int part, const void *y_aos_dev, const void *v_aos_dev, void *jv_aos_dev);
 int crd_jtimes_host(crd_ctx *ctx, double t, int part, const void *y_aos, const void *v_aos, void *jv_aos);
 
+/* The preconditioner solve of an implicit stage's system (I - gamma J_D(t)) z = r: z = M r, M one geometric multigrid V-cycle on the
+ * device.  Vectors are those of crd_jtimes_*: AoS, the context's precision.  P = I - gamma J_D acts on var0 only; z_var1 = r_var1 bit
+ * for bit.  M is a fixed linear map of r (what a Krylov method asks of a preconditioner); gamma = 0 returns z = r exactly.
+ *   Level l:  L_l x (j, i) = cE[i] (x[j, i+1] - x[j, i]) + cWn[i] (x[j, i] - x[j, i-1]) + cP[i] (x[j+1, i] - 2 x[j, i] + x[j-1, i]), periodic in
+ *   theta and phi as crd_rhs_part_*(CRD_PART_DIFFUSION) takes its neighbours; A_l = I - gamma L_l; diagonal d_l[i] = 1 + gamma (2 cX_l + 2 cP_l[i]).
+ *   Level 0 is the context's grid and tables.  Level l + 1 exists while nx_l and ny_l are both even and both halves are >= 4, up to
+ *   max_levels; coarse point (J, I) is fine point (2 J, 2 I); the coarse tables are the same formulas at doubled spacing,
+ *   cX / 4, cA[2 I] / 2, cP[2 I] / 4 (cE = cX + cA, cWn = cA - cX formed in double, rounded once).
+ *   Held rows: when J has zero rows at t (t < t_boundary strictly, never with just_diffusion: the rule of crd_jtimes_*) level 0 holds
+ *   rows 0 and ny - 1 and every coarser level row 0 only -- fine row ny - 1 has no coarse counterpart.  L_l has zero rows there.
+ *   Sweep (damped Jacobi): z <- z + omega (r - (z - gamma L_l z)) / d_l from the old z everywhere, then z = r on held rows.
+ *   Cycle on level l: the coarsest level takes `coarse` sweeps from z = 0; any other `pre` sweeps from z = 0, the residual
+ *   r - A_l z restricted by full weighting (1/16 [1 2 1; 2 4 2; 1 2 1], periodic) and zeroed on the coarse held row, the cycle on
+ *   level l + 1 for the correction, its bilinear prolongation (periodic) zeroed on this level's held rows and added, `post` sweeps.
+ * Limit: with held rows and large gamma ONE cycle alone is not a contraction (||r - A z|| / ||r|| up to 13 was measured on a
+ * prototype: the coarse levels hold a row shifted by one fine row); as a Krylov preconditioner that costs a few iterations.
+ * opt == NULL: the defaults (pre = post = 2, coarse = 8, max_levels = 16, omega = 0.8).  CRD_EINVAL, before any device work: gamma
+ * negative or not finite; pre or post negative or pre + post < 1; coarse < 1; max_levels outside 1 .. 16; omega outside (0, 1]; z == r.
+ * CRD_ESTATE: a context that is one of several slabs (a LOCAL group member, an RCCL world > 1) and theta-block contexts.  The
+ * workspace -- three var0 planes per level, every level the grid has -- is allocated by the first crd_psolve_device / _host call and freed
+ * by crd_destroy (CRD_ENOMEM if it cannot be had); crd_psolve_info reports its size and the levels a call with `opt` uses (entries of
+ * nx / ny beyond `levels` are 0; any output pointer may be NULL).  Launches go on the context's compute stream: _device returns
+ * without waiting, like crd_jtimes_device; _host stages through device memory and waits. */
+typedef struct crd_psolve_options {
+	int32_t pre, post, coarse, max_levels;
+	double omega;
+} crd_psolve_options;
+int crd_psolve_defaults(crd_psolve_options *opt);
+int crd_psolve_info(crd_ctx *ctx, const crd_psolve_options *opt, int32_t *levels, int32_t nx[16], int32_t ny[16], int64_t *workspace_bytes);
+int crd_psolve_device(crd_ctx *ctx, double t, double gamma, const crd_psolve_options *opt, const void *r_aos_dev, void *z_aos_dev);
+int crd_psolve_host(crd_ctx *ctx, double t, double gamma, const crd_psolve_options *opt, const void *r_aos, void *z_aos);
+
 /* Fast path that never leaves the GPU: nsteps classical RK4 steps of size dt on the context's resident state,
  * stage k of step n evaluated at t0 + n dt + c_k dt (replaces the ARKode(...) call, src/FHNmodel_torus.cpp:423).
  * Asynchronous; crd_synchronize() waits.  With several slabs every context of the run must make the same call: stepping is

@@ -47,6 +47,18 @@ int crd_arkode_jtimes(N_Vector v, N_Vector Jv, realtype t, N_Vector y, N_Vector 
 	return jtimes_part(CRD_PART_FULL, v, Jv, t, y, user_data);
 }
 
+int crd_arkode_psolve(realtype t, N_Vector y, N_Vector fy, N_Vector r, N_Vector z, realtype gamma, realtype delta, int lr, void *user_data, N_Vector tmp)
+{
+	crd_ctx *ctx = (crd_ctx *)user_data;
+	(void)y;
+	(void)fy;
+	(void)delta;
+	(void)lr;
+	(void)tmp;
+	if (!ctx || !r || !z) return -1;
+	return crd_psolve_host(ctx, (double)t, (double)gamma, NULL, NV_DATA_P(r), NV_DATA_P(z)) == CRD_OK ? 0 : -1;
+}
+
 int crd_arkode_attach(const crd_run_config *cfg, int rank, int nprocs, int device, crd_bcast_fn bcast, void *comm, crd_ctx **out)
 {
 	if (!cfg || !out) return CRD_EINVAL;

@@ -51,6 +51,18 @@ int crd_arkode_fi(realtype t, N_Vector y, N_Vector ydot, void *user_data);
 int crd_arkode_jtimes_fi(N_Vector v, N_Vector Jv, realtype t, N_Vector y, N_Vector fy, void *user_data, N_Vector tmp);
 int crd_arkode_jtimes(N_Vector v, N_Vector Jv, realtype t, N_Vector y, N_Vector fy, void *user_data, N_Vector tmp);
 
+/* The preconditioner solve of the IMEX run's Newton system (I - gamma J_fi) z = r: one multigrid V-cycle on the GPU (crd_psolve_host
+ * with the default options; single-slab contexts only).  With it the Krylov iteration count stays bounded where it otherwise grows
+ * like the square root of gamma times the operator's largest eigenvalue:
+ *
+ *     ARKSpgmr(arkode_mem, PREC_LEFT, 0);                                   // or PREC_RIGHT
+ *     ARKSpilsSetPreconditioner(arkode_mem, NULL, crd_arkode_psolve);       // no setup function: the cycle has nothing to factor
+ *
+ * The arguments are those ARKode 1.x documents for ARKSpilsPrecSolveFn, (t, y, fy, r, z, gamma, delta, lr, user_data, tmp); y, fy,
+ * delta and tmp are not used and either lr is taken (the cycle is one fixed linear map).  UNVERIFIED against a SUNDIALS build like the
+ * callbacks above.  Returns 0 / -1. */
+int crd_arkode_psolve(realtype t, N_Vector y, N_Vector fy, N_Vector r, N_Vector z, realtype gamma, realtype delta, int lr, void *user_data, N_Vector tmp);
+
 /* Creates the rank's context from the run configuration (crd_config_load_ini of the same ini file main() reads, :158-174) and,
  * for nprocs > 1, joins the RCCL ring: `bcast(buf, bytes, comm)` is any broadcast of `bytes` (129: a status byte + the 128-byte
  * id) from rank 0 -- with MPI, `MPI_Bcast(buf, bytes, MPI_BYTE, 0, comm)` wrapped in a two-line function.  Every rank always
