@@ -135,36 +135,60 @@ def hermite_arkode(tau, h, yold, ynew, fold, fnew):
     return a0 * yold + a1 * ynew + a2 * fold + a3 * fnew
 
 
-def initial_step(rhs, t0, y0, f0, tout, rtol, atol):
-    """arkHin."""
+def initial_step_trace(rhs, t0, y0, f0, tout, rtol, atol):
+    """arkHin with everything it decided on the way, as a dict:
+      hlb, hub_inv, argmax   the lower bound; max_i |f_i| / (0.1 |y_i| + rtol |y_i| + atol) and the flat index of the component
+                             (of y0.ravel()) that has it
+      hub, clamped           the upper bound, and whether it is 1 / hub_inv rather than 0.1 |tout - t0|
+      iterations             per pass of the loop: dict(hg, yddnrm, formula), formula "ydd" (hnew = sqrt(2 / yddnrm)), "geometric"
+                             (hnew = sqrt(hg hub)) or None for the pass that only ends the loop (its norm decides nothing)
+      count, h0              the passes made (0: hub < hlb, the loop is skipped and h0 = sqrt(hlb hub)) and the estimate
+      ydd_terms              (ydd_i w_i)^2 of the last pass, shaped like y0 (None when the loop is skipped)
+    initial_step returns h0 of this, formed by the same operations in the same order."""
     tdist = abs(tout - t0)
     tround = UROUND * max(abs(t0), abs(tout))
     if tdist < 2.0 * tround:
         raise ValueError("tout too close to t0")
     hlb = H0_LBFACTOR * tround
-    hub_inv = float(np.max(np.abs(f0) / (H0_UBFACTOR * np.abs(y0) + (rtol * np.abs(y0) + atol))))
+    ratio = np.abs(f0) / (H0_UBFACTOR * np.abs(y0) + (rtol * np.abs(y0) + atol))
+    hub_inv = float(np.max(ratio))
+    tr = dict(hlb=hlb, hub_inv=hub_inv, argmax=int(np.argmax(ratio)), iterations=[], count=0, ydd_terms=None)
     hub = H0_UBFACTOR * tdist
-    if hub * hub_inv > 1.0:
+    tr["clamped"] = bool(hub * hub_inv > 1.0)
+    if tr["clamped"]:
         hub = 1.0 / hub_inv
+    tr["hub"] = hub
     hg = math.sqrt(hlb * hub)
     if hub < hlb:
-        return hg
+        tr["h0"] = hg
+        return tr
     w = error_weights(y0, rtol, atol)
     hnew_ok, hnew = False, hg
     for count in range(1, H0_ITERS + 1):
         ydd = (rhs(t0 + hg, y0 + hg * f0) - f0) * (1.0 / hg)
         yddnrm = wrms(ydd, w)
+        e = ydd * w
+        tr["count"], tr["ydd_terms"] = count, e * e
+        tr["iterations"].append(dict(hg=hg, yddnrm=yddnrm, formula=None))
         if hnew_ok or count == H0_ITERS:
             hnew = hg
             break
-        hnew = math.sqrt(2.0 / yddnrm) if yddnrm * hub * hub > 2.0 else math.sqrt(hg * hub)
+        by_ydd = yddnrm * hub * hub > 2.0
+        tr["iterations"][-1]["formula"] = "ydd" if by_ydd else "geometric"
+        hnew = math.sqrt(2.0 / yddnrm) if by_ydd else math.sqrt(hg * hub)
         hrat = hnew / hg
         if 0.5 < hrat < 2.0:
             hnew_ok = True
         if count > 1 and hrat > 2.0:
             hnew, hnew_ok = hg, True
         hg = hnew
-    return min(max(H0_BIAS * hnew, hlb), hub)
+    tr["h0"] = min(max(H0_BIAS * hnew, hlb), hub)
+    return tr
+
+
+def initial_step(rhs, t0, y0, f0, tout, rtol, atol):
+    """arkHin."""
+    return initial_step_trace(rhs, t0, y0, f0, tout, rtol, atol)["h0"]
 
 
 class ArkodeErk:
