@@ -1,7 +1,8 @@
 /*
  * crd_oracle.c -- CPU restatement of CRDModel's RHS hot path.  TEST INFRASTRUCTURE ONLY (see crd_oracle.h).
- * PARITY UNPINNED against reference-run output: the reference cannot be built in this image (SUNDIALS, Boost
- * absent) and ships no tests or golden vectors; see crd_oracle.h for what pins this file instead.
+ * PARITY: f(), initial conditions, geometry, the one-rank decomposition and exchange are pinned bit for bit against the reference's
+ * own compiled code at one rank (oracle/ref_build/, tests/test_refprobe_host.py); the adaptive trajectory and np > 1 remain unpinned
+ * (crd_oracle.h).  Built with -fno-builtin-sin -fno-builtin-cos: the reference's default build calls sin() and cos(), not sincos().
  *
  * Plain C99 + libm (+ OpenMP for the timed multi-core baseline).  All citations are /root/reference paths.
  */

@@ -4,16 +4,18 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may call this.  The product
  * (libcrd.so, crdmodel_amd/) never links, loads or calls anything in oracle/.
  *
- * PARITY UNPINNED: the reference (the four programs under /root/reference/src) needs SUNDIALS 2.x (ARKode +
- * NVECTOR_PARALLEL), Boost.PropertyTree and MPI; SUNDIALS and Boost are absent from this image, so the
- * reference is unbuildable here, and it ships no tests, golden vectors or fixtures.  This restatement is
- * therefore pinned only by (i) an independent numpy restatement (oracle/crd_oracle_np.py), (ii) analytic
+ * PARITY: f(), the initial conditions, the geometry (ny truncation, dx, dy), the one-rank decomposition and exchange and the output
+ * format are PINNED BIT FOR BIT against the reference's own compiled code at one rank: its four programs (/root/reference/src),
+ * compiled unmodified against stand-in headers for SUNDIALS, MPI and Boost.PropertyTree whose ARKode only calls the programs' own
+ * f() (oracle/ref_build/), wrote tests/golden/refprobe_*.npz, and tests/test_refprobe_host.py requires this file's bits.  Still
+ * UNPINNED, exactly two things: ARKode's adaptive step sequence (oracle/arkode_erk.py restates it from the documentation) and runs
+ * with more than one rank.  Beside the pin this restatement is held by (i) an independent numpy restatement
+ * (oracle/crd_oracle_np.py), (ii) analytic
  * known answers the reference's own code implies (steady states, index-space eigenfunctions), and
  * (iii) the shipped .ini parameter sets under data/, including the one result they state (the Goldbeter kinetics are
  * "oscillatory when 0.28895 < beta < 0.77427", data/GoldbeterModelArgs.ini:25 -- reproduced to the digits given, as is the
  * FHN Hopf point beta = 1 of util/FHNmodel/plot_FHNmodel_torus.py:90-92; the torus's Gaussian curvature of
- * util/PlotGaussianAndCoupling.py:11-12, which fixes the two theta-dependent coefficients of the diffusion operator) -- not by
- * outputs of the reference itself.
+ * util/PlotGaussianAndCoupling.py:11-12, which fixes the two theta-dependent coefficients of the diffusion operator).
  *
  * Every function cites the reference lines it follows (paths under /root/reference/).
  */

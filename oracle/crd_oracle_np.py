@@ -1,7 +1,7 @@
 """Independent numpy restatement of CRDModel's RHS.  TEST INFRASTRUCTURE ONLY.
 
 Written from the model equations and the reference's formulas, sharing no code with oracle/crd_oracle.c, so the
-two restatements pin each other (the reference itself cannot be built here: PARITY UNPINNED, see crd_oracle.h).
+two restatements pin each other (the C one is also pinned bit for bit against the reference's own compiled f(): oracle/ref_build/).
 Only tests/ may import this module.
 
 Precision-generic: `dtype` (default float64) is the type of the arithmetic.  The model's constants and PI stay the fp64 values

@@ -37,6 +37,23 @@ The Goldbeter reciprocal (hardware estimate + one Newton step, crd_device.h: rec
 relative error rho multiplies the quotient w and is charged as its own term, rho |w|, so a change to the reciprocal (or
 to CRD_RCP_NEWTON) moves this bound rather than hiding inside K.
 
+The torus coefficients' own conditioning.  theta_i = i dx, rho = R + r cos(theta), cA ~ sin(theta) / rho and cP ~ 1 / rho^2 are
+formed in fp64 by the host's tables and by the reference program alike, while this module's reference forms them in its own, wider
+type.  In fp64 theta_i carries the product's rounding, |d theta| <= u64 theta, so |d cos| <= u64 (theta |sin| + |cos|) and, with the
+product r cos and the sum,
+
+    |d rho| / |rho| <= u64 kappa,    kappa = r (theta |sin theta| + 2 |cos theta|) / |rho| + 1:
+
+a cancellation when the torus nearly closes on its axis (R -> r: rho -> 0 at theta = pi).  kappa <= 2.4 on an 80 x 20 torus, which
+the spare rounding in K used to cover unnoticed; at 20.5 x 20 (R / r = 1.025) it reaches 83 and the reference's own compiled f() -- a correct fp64
+evaluation by definition -- left the old bound by a factor 2.2 (tests/test_refprobe_host.py).  So the coefficients' errors are
+charged as their own term, against the exact differences they multiply and in u64 whatever the kernel's precision:
+
+    u64 [ (|cA| (kappa + 3) + D theta |cos theta| / (2 dx r |rho|)) |uE - uW| + |cP| (2 kappa + 3) |uN - 2 uC + uS| ]
+
+(the second summand of the first bracket is sin(theta)'s absolute error, theta |cos theta| u64, which is not small next to
+sin(theta) near theta = 0 and pi; the 3 are the remaining products and quotients of each table entry).  Zero on the flat surface.
+
 Absorbing rows while t < tBoundary, dv of diffusion-only Goldbeter, and a uniform field's diffusion are exact zeros: the
 bound there is 0 and any nonzero result fails.
 
@@ -215,10 +232,15 @@ class _Problem:
             cX = D * (1 / (p.r * p.r)) / (dx * dx)
             cA = D * (-np.sin(theta) / (p.r * rho)) / (2 * dx)
             cP = D * (1 / (rho * rho)) / (dy * dy)
+            # the coefficients' own fp64 errors, per column (module docstring: "The torus coefficients' own conditioning")
+            kappa = p.r * (theta * np.abs(np.sin(theta)) + 2 * np.abs(np.cos(theta))) / np.abs(rho) + 1
+            self.dcA = UNIT["f64"] * (np.abs(cA) * (kappa + 3) + D * theta * np.abs(np.cos(theta)) / (2 * dx * p.r * np.abs(rho)))
+            self.dcP = UNIT["f64"] * np.abs(cP) * (2 * kappa + 3)
         else:
             cX = D / dx / dx
             cA = np.zeros(p.nx)
             cP = np.full(p.nx, D / dy / dy)
+            self.dcA = self.dcP = np.zeros(p.nx)
         self.cE, self.cWn, self.cP = cX + cA, cA - cX, cP
 
     def rhs(self, t, u, v, dtype, j0):
@@ -267,7 +289,10 @@ class _Problem:
         """Bounds (e_u, e_v) on the error of f at a state known to within (du, dv) per point (None: exact input)."""
         S_u, S_v, w, centre, gv, hu, hv = self.terms(u, v, j0)
         rcp = RHO[precision] * w
-        eu = K * UNIT[precision] * S_u + rcp
+        u64 = np.asarray(u, dtype=np.float64)
+        tables = (self.dcA[None, :] * np.abs(np.roll(u64, -1, axis=1) - np.roll(u64, 1, axis=1))
+                  + self.dcP[None, :] * np.abs(np.roll(u64, -1, axis=0) - 2 * u64 + np.roll(u64, 1, axis=0)))
+        eu = K * UNIT[precision] * S_u + rcp + tables
         ev = K * UNIT[precision] * S_v + rcp
         if du is not None:
             cE, cWn, cP = np.abs(self.cE)[None, :], np.abs(self.cWn)[None, :], np.abs(self.cP)[None, :]

@@ -1,7 +1,8 @@
 """The oracle checks itself: C restatement vs golden vectors, vs the independent numpy restatement, vs analytic
 known answers the reference's code implies, and decomposition invariance (what MPI delivers at np in {1,2,4}).
 
-PARITY UNPINNED against reference-run output (the reference cannot be built here; it ships no tests or fixtures)."""
+The pin against the reference's own compiled code (f(), initial conditions, geometry, one-rank exchange, output format: bit for bit) is
+tests/test_refprobe_host.py; the adaptive trajectory and np > 1 remain unpinned."""
 import numpy as np
 import pytest
 
