@@ -6,10 +6,7 @@
 // share -- step size, stage times, geometry, chunking -- comes in the kernel arguments.  The work item is set up by
 // crd_ensemble_item.h, as in every ensemble step unit.  DESIGN.md, "Ensembles".
 #include "crd_ensemble.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
-#pragma clang diagnostic pop
 #include "crd_ensemble_item.h"
 
 namespace crd {

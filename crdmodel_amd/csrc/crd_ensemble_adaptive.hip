@@ -7,10 +7,7 @@
 // sets its work item up itself (hand-written, as crd_ensemble_item.h's header explains); its instantiation ladder and its plan are
 // that header's.  DESIGN.md, "Ensembles".
 #include "crd_ensemble.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
-#pragma clang diagnostic pop
 #include "crd_ensemble_item.h"
 
 namespace crd {

@@ -5,10 +5,7 @@
 // set-up is written out here (crd_ensemble_item.h's header explains why); the search, the ladder and the plan are that header's.  A unit of its own: the uniform kernels keep their code and registers and stay the path of every
 // ensemble whose members share nx and ny.  DESIGN.md, "Ensembles" (mixed geometry).
 #include "crd_ensemble.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
-#pragma clang diagnostic pop
 #include "crd_ensemble_item.h"
 
 namespace crd {

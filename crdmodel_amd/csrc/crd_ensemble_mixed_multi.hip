@@ -7,10 +7,7 @@
 // its own, its device assembly kept and checked by tools/kernel_regs.py --check before libcrd.so links, as crd_ensemble_multi.hip's.
 // DESIGN.md, "Ensembles".
 #include "crd_ensemble.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
-#pragma clang diagnostic pop
 #include "crd_ensemble_item.h"
 
 #ifndef CRD_NO_ENSEMBLE_PAIRS  // (make KERNEL_TABLE=0: nothing checks this unit's assembly, so it ships no kernel; Makefile)

@@ -8,10 +8,7 @@
 // plan and any set of active slots.  A unit of its own, compiled as crd_ensemble.hip is: the kernels of crd_ensemble_step_rk4 keep
 // their code and registers.  DESIGN.md, "Ensembles" (own step sizes).
 #include "crd_ensemble.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // (the header's error-sum kernel: this unit launches none)
 #include "crd_fused_impl.h"
-#pragma clang diagnostic pop
 #include "crd_ensemble_item.h"
 
 namespace crd {

@@ -1,6 +1,6 @@
-// crd_fused.hip -- the one-launch RK4 step kernels (crd_fused_impl.h): fp64 instantiations, the precision dispatch and the launch
+// crd_fused.hip -- the one-launch RK4 step kernels (crd_fused_launch.h): fp64 instantiations, the precision dispatch and the launch
 // interface's small functions.  The fp32 instantiations live in crd_fused_f32.hip.
-#include "crd_fused_impl.h"
+#include "crd_fused_launch.h"
 
 namespace crd {
 
@@ -8,22 +8,23 @@ bool fused_step_supported(int, const SlabDesc &d) { return d.nyl >= 2 * kStepHal
 
 bool fused_two_steps_supported(const SlabDesc &d) { return d.nyl >= 4 * kStepHalo && kernel_model(d) != kModelDiffusionOnly; }
 
-// Steps one launch of this slab takes when the plan asks for `want` (1 .. 3): three only where the three-step kernel exists (FHN:
-// kCanThreeSteps) and on a single slab (rows wrap; the exchange cycles of multi-slab runs step pairs), else two where the two-step
-// kernels do, else one.
+// What the plan arithmetic is told about the kernels of a precision and model (crd_fused_launch.h: kTraits).
+static const plan::KernelTraits &kernel_traits(int precision, int model)
+{
+	const bool f64 = precision == CRD_PRECISION_F64;
+	switch (model) {
+	case CRD_MODEL_FHN: return f64 ? kTraits<double, CRD_MODEL_FHN> : kTraits<float, CRD_MODEL_FHN>;
+	case CRD_MODEL_GOLDBETER: return f64 ? kTraits<double, CRD_MODEL_GOLDBETER> : kTraits<float, CRD_MODEL_GOLDBETER>;
+	default: return f64 ? kTraits<double, kModelDiffusionOnly> : kTraits<float, kModelDiffusionOnly>;
+	}
+}
+
+// Steps one launch of this slab takes when the plan asks for `want` (1 .. 3): crd_fused_plan.h has the rule, steps_per_launch -- the
+// one the launcher holds its calls to.
 int fused_steps_supported(int precision, const SlabDesc &d, int want)
 {
-	// (FHN: fp64 with one column per lane, fp32 with two -- an even nx; crd_fused_impl.h: kThreeStepCols)
-	bool three = kernel_model(d) == CRD_MODEL_FHN && (precision == CRD_PRECISION_F64 || d.nx % 2 == 0);
-#ifdef CRD_THREE_STEPS_GOLDBETER
-	three = three || (precision == CRD_PRECISION_F64 && kernel_model(d) == CRD_MODEL_GOLDBETER);
-#endif
-	// (single slabs; in fp32 -- a strip per wavefront -- the slabs of a multi-slab run too, inside their exchange cycles: the fp64 block strip
-	// measured nothing on a rank's share and keeps pairs there)
-	// (the fp64 block strip addresses its rows by 32-bit offsets into the plane, kScalarRows: beyond that span, pairs)
-	if (precision == CRD_PRECISION_F64 && !fused_scalar_rows_addressable(d.nx, fused_addressed_rows(d), 8)) three = false;
-	if (want >= 3 && three && (d.wrap || precision != CRD_PRECISION_F64) && d.nyl >= 6 * kStepHalo) return 3;
-	return (want >= 2 && fused_two_steps_supported(d)) ? 2 : 1;
+	const plan::KernelTraits &k = kernel_traits(precision, kernel_model(d));
+	return plan::steps_per_launch(k, {d.nx, d.nyl, d.wrap != 0, false, fused_scalar_rows_addressable(d.nx, fused_addressed_rows(d), k.real_bytes), false}, want);
 }
 
 long fused_addressed_rows(const SlabDesc &d) { return (long)d.nyl + (d.wrap ? 0L : 2L * kGhost); }
@@ -42,20 +43,34 @@ int fused_max_items(const SlabDesc &d)
 	return strips * ((d.nyl + 2 * kGhost + 3) / 4 + 2);
 }
 
+int device_cus()
+{
+	// compute units of a device of this node (the GPUs of a node are alike); initialised once, also when several issuing threads of a
+	// LOCAL group arrive together
+	static const int cus = [] {
+		int dev = 0;
+		hipDeviceProp_t prop;
+		const int n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+		(void)hipGetLastError();
+		return n;
+	}();
+	return cus;
+}
+
 const char *fused_kernel_name(int, int) { return "crd_rk4_fused_step_kernel"; }
 
 int fused_default_columns(int precision, int nx) { return (precision == CRD_PRECISION_F32 && nx % 2 == 0) ? 2 : 1; }
 
-int fused_plan_candidates() { return kNumPlanCandidates; }
+int fused_plan_candidates() { return plan::kNumPlanCandidates; }
 
 bool fused_plan_candidate(int index, int *chunk_mode, int *mapping, int *cols, int *nt, int *steps)
 {
-	if (index < 0 || index >= kNumPlanCandidates) return false;
-	*steps = kPlanCandidates[index].steps;
-	*chunk_mode = kPlanCandidates[index].one_round;
-	*mapping = kPlanCandidates[index].remap;
-	*cols = kPlanCandidates[index].cols;
-	*nt = kPlanCandidates[index].nt;
+	if (index < 0 || index >= plan::kNumPlanCandidates) return false;
+	*steps = plan::kPlanCandidates[index].steps;
+	*chunk_mode = plan::kPlanCandidates[index].one_round;
+	*mapping = plan::kPlanCandidates[index].remap;
+	*cols = plan::kPlanCandidates[index].cols;
+	*nt = plan::kPlanCandidates[index].nt;
 	return true;
 }
 

@@ -1,6 +1,6 @@
-// crd_fused_f32.hip -- the fp32 instantiations of the one-launch RK4 step kernels (crd_fused_impl.h); crd_fused.hip has the fp64 ones
+// crd_fused_f32.hip -- the fp32 instantiations of the one-launch RK4 step kernels (crd_fused_launch.h); crd_fused.hip has the fp64 ones
 // and the precision dispatch.
-#include "crd_fused_impl.h"
+#include "crd_fused_launch.h"
 
 namespace crd {
 

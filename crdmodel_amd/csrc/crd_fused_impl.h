@@ -1,6 +1,7 @@
 #pragma once
-// crd_fused_impl.h -- (included by crd_fused.hip, the fp64 instantiations, and crd_fused_f32.hip, the fp32 ones: two translation
-// units so that the two halves of the instantiation matrix compile side by side)
+// crd_fused_impl.h -- the device bodies of the one-launch RK4 step, fused_item and fused_item_multi_step, with the constants and LDS
+// sizes they share.  Device code only: the single-slab step kernel around them, its launcher and the launch-plan measurement are
+// crd_fused_launch.h's (crd_fused.hip, crd_fused_f32.hip); the ensemble units wrap the same bodies in kernels of their own.
 // One classical RK4 step of the whole slab in ONE kernel launch: all four RHS evaluations and the
 // stage updates happen on chip, so a grid-point-step costs one read and one write of the state (32 B in fp64) instead
 // of the 256 B the four stage kernels of crd_kernels.hip move.  Same arithmetic per point as the staged stepper.
@@ -1363,688 +1364,11 @@ __device__ __forceinline__ void fused_item_multi_step(const Slab<Real> &s, const
 	else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ABSORB = false: no stage of the step has t < tBoundary (every launch after the switch-off time, every launch of a run with
-// tBoundary = 0) -- the absorbing-row selects are compiled out.  ABSORB = true: the items that can meet a global phi boundary row
-// (src/FHNmodel_torus.cpp:643-653) run the body with the selects, all others the body without (see fused_item).
-// EMBED, COLS, NT: see FusedArgs / fused_item above.
-// STEPS = 2: two steps per launch (fused_item_two_steps).
 // Wavefronts per SIMD the register allocator is held to: the two-step pipelines live at the 168-register line (three wavefronts).
 template <typename Real, int MODEL, int COLS, int STEPS, bool ABSORB>
 constexpr int kMinWaves = (STEPS == 2 && COLS * (int)sizeof(Real) == 8 && MODEL == CRD_MODEL_FHN && !ABSORB) ? 3 : (STEPS == 3 ? 2 : 1);
-// WAVES: the wavefronts of a block -- kMaxWavesPerBlock everywhere but in the eight-wide three-step block strip (kWideWaves).
-template <typename Real, int MODEL, bool ABSORB, int EMBED, int COLS, bool NT = false, int STEPS = 1, int WAVES = kMaxWavesPerBlock>
-__global__ void __launch_bounds__(kLanes *WAVES) __attribute__((amdgpu_waves_per_eu(kMinWaves<Real, MODEL, COLS, STEPS, ABSORB>))) crd_rk4_fused_step_kernel(Slab<Real> s, FusedArgs<Real> a)
-{
-	static_assert(STEPS == 1 || ((STEPS == 2 || STEPS == 3) && EMBED == 0), "several steps per launch: the plain step only");
-	static_assert(WAVES == kMaxWavesPerBlock || (WAVES == kWideWaves && kCanWide<Real, MODEL, COLS, STEPS> && !ABSORB), "eight wavefronts per block: the three-step fp64 FHN block strip without the selects only");
-	// The work item is a property of the wavefront: keep it (and everything derived from it: rows, trip counts, the
-	// per-row table reads, the boundary-row tests) in scalar registers.
-	// Optional remap: blocks are dealt round-robin over the 8 XCDs; the remap gives each XCD one contiguous run of items.
-	// A block's wavefronts take adjacent strips of ONE chunk, blocks walk theta first.  The wavefronts of a block therefore
-	// run the same trip counts, and in lockstep (one barrier per pipeline iteration) their row reads reach the memory system
-	// together as one contiguous, overlapping run of a.sw x 448 B per row instead of drifting apart.
-	const int nsb = (a.nstrips + a.sw - 1) / a.sw;
-	int sblk, cblk;
-	{
-		const int b0 = (int)blockIdx.x;
-		const int blk = a.remap == 1 ? xcd_remap(b0, a.nblocks) : b0;
-		sblk = blk % nsb;
-		cblk = blk / nsb;
-		if (a.remap == 2) {
-			// Succession in phi: XCD x owns a contiguous run of chunks; its resident workgroups form `xs_lanes` lanes per strip
-			// block, and the workgroup that takes a finished one's place (ids are dispatched in order, 8 apart on one XCD) continues
-			// that lane with the NEXT chunk in phi -- whose first rows are the rows its predecessor has just read into this L2.
-			const int x = blk % kNumXcd, p = blk / kNumXcd, width = nsb * a.xs_lanes;
-			const int d = p / width, sl = p - d * width;
-			const int c0 = (int)((long)a.nchunks * x / kNumXcd), c1 = (int)((long)a.nchunks * (x + 1) / kNumXcd);
-			const int depth = (c1 - c0 + a.xs_lanes - 1) / a.xs_lanes, lane_id = sl / nsb;
-			sblk = sl - lane_id * nsb;
-			cblk = (d < depth && c0 + lane_id * depth + d < c1) ? c0 + lane_id * depth + d : a.nchunks;  // nchunks: nothing to do
-		}
-	}
-	const int strip = __builtin_amdgcn_readfirstlane(sblk * a.sw + (int)(threadIdx.x >> 6));
-	const int chunk = __builtin_amdgcn_readfirstlane(cblk);
-	if (strip >= a.nstrips || chunk >= a.nchunks) return;  // (a barrier waits for the surviving wavefronts of the workgroup only)
-	// the row rings of a two-step launch's wavefronts (fused_item_two_steps)
-	__shared__ __attribute__((aligned(16))) char rings[STEPS >= 2 ? kRingBytes<Real, COLS, STEPS, WAVES> : 16];
-	lds_char *const block_rings = (lds_char *)rings;
-	__shared__ __attribute__((aligned(16))) char edges[(STEPS >= 2 && kCoop<Real, MODEL, COLS, STEPS>) ? kEdgeBytes<STEPS, WAVES> + kEdgeDumpBytes<STEPS, WAVES> : 16];
-	lds_char *const block_edges = (lds_char *)edges;
-	if constexpr (ABSORB) {
-		// Does any row this chunk's pipeline touches -- [j0 - APRON, j1 + APRON) -- map to global row 0 or ny - 1?  The two are
-		// neighbours on the periodic grid: the rows contain one of them exactly when [lo, hi + 1] contains a multiple of ny.
-		constexpr int APRON = STEPS * (EMBED != 0 ? kApron + 1 : kApron);
-		const int range = chunk >= a.first2 ? 1 : 0;
-		const int j0 = a.r_begin[range] + (chunk - (range ? a.first2 : 0)) * a.chunk;
-		const int j1 = (j0 + a.chunk < a.r_end[range]) ? j0 + a.chunk : a.r_end[range];
-		const int lo = a.js + j0 - APRON, hi1 = a.js + j1 + APRON;  // (lo > -ny and hi1 < 3 ny: a slab is at most the grid, ghost rows at most a slab)
-		const bool touches = (lo <= 0 && 0 <= hi1) || (lo <= a.ny && a.ny <= hi1) || (lo <= 2 * a.ny && 2 * a.ny <= hi1);
-		if constexpr (STEPS >= 2) {
-			if (touches) fused_item_multi_step<Real, MODEL, true, COLS, NT, STEPS, kMaxWavesPerBlock, false>(s, a, strip, chunk, block_rings, sblk, block_edges);
-			else fused_item_multi_step<Real, MODEL, false, COLS, NT, STEPS, kMaxWavesPerBlock, false>(s, a, strip, chunk, block_rings, sblk, block_edges);
-		} else {
-			if (touches) fused_item<Real, MODEL, true, EMBED, COLS, NT>(s, a, strip, chunk);
-			else fused_item<Real, MODEL, false, EMBED, COLS, NT>(s, a, strip, chunk);
-		}
-	} else if constexpr (STEPS >= 2) {
-		fused_item_multi_step<Real, MODEL, false, COLS, NT, STEPS, WAVES>(s, a, strip, chunk, block_rings, sblk, block_edges);
-	} else {
-		fused_item<Real, MODEL, false, EMBED, COLS, NT>(s, a, strip, chunk);
-	}
-}
-
-// Adds the per-item error sums in a fixed order (thread t takes items t, t+256, ...; then a fixed LDS tree), so the error
-// norm, and with it every accept / reject decision of the adaptive stepper, is reproducible from run to run.
-__global__ void __launch_bounds__(256) crd_sum_partials_kernel(const double *__restrict__ partials, int n, double *__restrict__ out)
-{
-	__shared__ double part[256];
-	double sum = 0.0;
-	for (int q = threadIdx.x; q < n; q += 256) sum += partials[q];
-	part[threadIdx.x] = sum;
-	__syncthreads();
-	for (int w = 128; w > 0; w >>= 1) {
-		if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) *out = part[0];
-}
-
-// Rows per work item.  Every item pays 8 apron rows, which argues for long chunks; but the wavefronts of a launch run in
-// "rounds" of (resident wavefront slots) items, a partly filled last round idles most of the chip, unequal wavefront
-// speeds cost about half a round at the end whatever the count, and short chunks keep the rows two phi-neighbouring items
-// share in L2.  Measured on 8192^2 fp64 (147 strips, 4096 slots; 200-step medians, one process, tools/tune_fused.py):
-// chunk 32 0.434 ms, 24 0.451, 50 0.463, 60 0.477, 75 0.494, 128 0.51, 1024 0.62 -- many short items win.  So: 32 rows,
-// halved while the launch would not fill every slot once (an 8192 x 1024 slab, one rank's share of 8 GPUs, sweeps in
-// 58.4 us with 32-row chunks and 60.5 with 16; the edge-band launches of a multi-slab step end up with 8-row chunks).
-// `one_round` (a launch-plan choice, see FusedPlan): a launch that needs more than one round of resident blocks but would
-// fit into one with chunks of up to 96 rows gets those longer chunks -- no tail round on an almost idle chip.
-int device_cus()
-{
-	// compute units of a device of this node (the GPUs of a node are alike); initialised once, also when several issuing threads of a
-	// LOCAL group arrive together
-	static const int cus = [] {
-		int dev = 0;
-		hipDeviceProp_t prop;
-		const int n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-		(void)hipGetLastError();
-		return n;
-	}();
-	return cus;
-}
-
-template <typename Real, int MODEL, int COLS, int STEPS>
-int resident_wavefronts()
-{
-	// resident wavefronts of this kernel on a device of this node (initialised once, thread-safely: the issuing threads of a LOCAL group
-	// may arrive together)
-	static const int slots = [] {
-		int blocks_per_cu = 4;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, crd_rk4_fused_step_kernel<Real, MODEL, false, 0, COLS, false, STEPS>, kLanes * kWavesPerBlock, 0) != hipSuccess ||
-		    blocks_per_cu < 1)
-			blocks_per_cu = 4;
-		(void)hipGetLastError();
-		return device_cus() * blocks_per_cu * kWavesPerBlock;
-	}();
-	return slots;
-}
-
-// Three steps per launch (round 6), for the kernels whose two-step launch is bound by its memory path rather than by issue (DESIGN.md
-// 4c, 4d): FHN in fp64 with one column per lane and the block as the strip (232 valid lanes of 256), and FHN in fp32 with two columns
-// per lane and a strip per wavefront (104 valid columns of 128 -- no exchange between wavefronts).  kThreeStepCols: the columns per
-// lane of the model's three-step kernel, 0 where there is none.
-#ifdef CRD_THREE_STEPS_GOLDBETER  // (probe build: the three-step pipeline for Goldbeter fp64 too -- profiles/r06/goldbeter_floor.txt)
-template <typename Real, int MODEL>
-constexpr int kThreeStepCols = (MODEL == CRD_MODEL_FHN || (MODEL == CRD_MODEL_GOLDBETER && sizeof(Real) == 8)) ? (sizeof(Real) == 8 ? 1 : 2) : 0;
-#else
-template <typename Real, int MODEL>
-constexpr int kThreeStepCols = MODEL == CRD_MODEL_FHN ? (sizeof(Real) == 8 ? 1 : 2) : 0;
-#endif
-template <typename Real, int MODEL>
-constexpr bool kCanThreeSteps = kThreeStepCols<Real, MODEL> != 0;
-
-template <typename Real, int MODEL>
-int resident_wavefronts(int cols, int steps = 1)
-{
-	if constexpr (kCanThreeSteps<Real, MODEL>)
-		if (steps == 3) return resident_wavefronts<Real, MODEL, kThreeStepCols<Real, MODEL>, 3>();
-	if constexpr (MODEL != kModelDiffusionOnly)  // (the diffusion-only variant has no two-step instantiation)
-		if (steps == 2) return cols == 2 ? resident_wavefronts<Real, MODEL, 2, 2>() : resident_wavefronts<Real, MODEL, 1, 2>();
-	return cols == 2 ? resident_wavefronts<Real, MODEL, 2, 1>() : resident_wavefronts<Real, MODEL, 1, 1>();
-}
-
-template <typename Real, int MODEL>
-int fused_chunk_rows(int nstrips, int rows, int chunk_mode, int cols, int steps = 1, int sw = kWavesPerBlock)  // 0: 32 rows, 1: one round, 2: 64 rows (two steps per launch: twice that), 3: as 1, blocks of `sw` = kWideWaves wavefronts
-{
-	bool one_round = chunk_mode == 1 || chunk_mode == 3;
-	const int slots = resident_wavefronts<Real, MODEL>(cols, steps);
-	// Two steps per launch: 16 fill rows per chunk instead of 8, and a pipeline bound by issue, not by the memory system: 128-row
-	// chunks (8192^2 fp64: 48 rows 0.301 ms per step, 64 0.289, 96 0.278, 128 0.267, 192 0.276, 256 0.276; fp32 alike,
-	// profiles/r04/two_step_tune.txt); chunk mode 2 is the 64-row alternative there.
-	int chunk = steps == 3 ? (chunk_mode == 2 ? 96 : 192) : steps == 2 ? (chunk_mode == 2 ? 64 : 128) : 32;  // (three steps: 24 fill rows per chunk)
-	while (chunk > 8 && (long)nstrips * ((rows + chunk - 1) / chunk) < (long)slots) chunk /= 2;
-	// Tiny launches: where even 8-row chunks make fewer blocks than half the CUs, 4-row chunks put twice as many CUs to work (256^2:
-	// 7.3 -> 6.4 us per step; the reference's 100 x 400 Goldbeter grid: 8.2 -> 6.5).  With more blocks than that the extra apron rows
-	// cost more than they bring (512^2: 8.9 -> 9.8 us, 400 x 1600: 11.1 -> 12.9; the edge bands of a ring share: no change).
-	if (chunk == 8 && (long)((nstrips + kWavesPerBlock - 1) / kWavesPerBlock) * ((rows + 7) / 8) < device_cus() / 2) chunk = 4;
-	if (const char *e = tuning::knob("CRD_FUSED_ONEROUND")) one_round = std::atoi(e) != 0;  // tuning knob
-	if (steps == 1 && chunk_mode == 2 && chunk == 32 && (long)nstrips * ((rows + 63) / 64) >= 2L * slots) chunk = 64;  // fewer apron rows recomputed: pays where fp64 issue binds (Goldbeter)
-	if (one_round && steps == 1) {
-		const long strip_blocks = (nstrips + kWavesPerBlock - 1) / kWavesPerBlock, fit = (slots / kWavesPerBlock) / strip_blocks;
-		const long need = fit >= 1 ? (rows + fit - 1) / fit : 0;
-		if (need > chunk && need <= 96) chunk = (int)need;
-	}
-	if (one_round && steps >= 2) {
-		// Two steps per launch are bound by issue, and what a launch loses is its last, partly filled round of resident blocks: chunks
-		// such that the launch is just under a WHOLE NUMBER of rounds -- the fewest rounds whose chunks stay within 288 rows (longer
-		// ones have fewer fill rows per row; 8192^2 fp64: 128 rows = 3.6 rounds 0.2667 ms per step, 155 = 2.97 rounds 0.2617, 235 =
-		// 1.96 rounds 0.2618, but 161 = 2.86 rounds 0.2669 and 241 = 1.90 rounds 0.2697; 16384^2 fp32: 128 rows 0.4948, 274 rows 0.4830;
-		// a rank's share of 1024 rows: one round of 61 rows; profiles/r04/whole_rounds.txt).
-		const long strip_blocks = (nstrips + sw - 1) / sw, resident_blocks = slots / sw;  // (sw: kWavesPerBlock, or the eight-wide block strip's kWideWaves)
-		for (long k = 1; k <= 8; k++) {
-			const long chunks = k * resident_blocks / strip_blocks;
-			if (chunks < 1) continue;
-			const long need = (rows + chunks - 1) / chunks;
-			// (The eight-wide block strip, one block per CU: 576 rows.  8192^2 is 17 strip blocks x 15 chunks of 547 rows = 0.996 rounds of 256
-			// resident blocks, 0.1954 ms per step; two rounds of 274-row chunks measured 0.2012, the four-wide plan's time -- what the wider block
-			// saves in apron lanes the second round's fill rows and tail give back; profiles/r08/block_strip_eight_ab.txt.)
-			if (need <= (sw == kWideWaves ? 576 : steps == 3 ? 432 : 288)) {
-				if (need >= 16) chunk = (int)need;
-				break;
-			}
-		}
-	}
-	if (const char *e = tuning::knob("CRD_FUSED_CHUNK")) {  // tuning knob
-		const int v = std::atoi(e);
-		if (v >= 1) chunk = v;
-	}
-	return chunk < rows ? chunk : rows;
-}
-
-// Launch-plan candidates the autotuner times: (chunks stretched to one round?, block -> item mapping).  Workgroups are dealt
-// round-robin to the 8 XCDs, each with its own L2.  Mapping 0 walks the items theta-first in dispatch order: neighbouring
-// items land on different XCDs and every apron column and row is fetched from beyond L2 by both items that need it (PMC:
-// 39.5 B per point, reads 1.47 x the plane).  Mapping 1 gives each XCD one contiguous run of items, i.e. a contiguous band of
-// the slab: theta-neighbours share an L2 and the apron columns are fetched once (36.6 B per point, reads 1.29 x).  Mapping 2
-// adds succession in phi -- the workgroup that takes a finished one's place continues with the next chunk in phi, whose first
-// rows its predecessor has just pulled into that L2 (34.9 B per point, reads 1.18 x).  Which plan is fastest depends on the
-// grid shape AND on the device: on 8192^2 fp64 mapping 1 measured -6.3 %, -0.7 % and +1.7 % against mapping 0 on three
-// MI355X of the same pool, mapping 2 -4.4 % on a fourth; one-round chunks -10 % (4096 x 1024) to +2 % (16384 x 2048 fp32) --
-// hence measured at run time, on the device and the shape at hand.  Every candidate computes bit-identical results.
-// Third dimension (round 3): columns per lane.  Two columns per lane halve the DPP moves and the apron share of a strip (8 of 128
-// columns instead of 8 of 64) and, in fp32, use the packed arithmetic; they also halve the wavefronts in flight for the same
-// bytes.  Which wins is again a matter of the kernel (fp32 / Goldbeter are issue-bound, FHN fp64 is not) and of the device.
-// Fourth dimension (round 3, late): non-temporal stores of the new state (row_store).  They keep L2 for what items share; which
-// mapping is fastest changes with them (the plain mapping gains most), so they are timed in combination.
-struct PlanCandidate {
-	int one_round, remap, cols, nt;  // one_round: the chunk mode -- 0 = 32 rows, 1 = stretched to one round, 2 = 64 rows, 3 = as 1 with eight wavefronts per block strip (kWideWaves)
-	int steps = 1;                   // RK4 steps per launch (2: fused_item_two_steps)
-};
-// (round 4: 64-row chunks also under mappings 1 / 2 and with two columns per lane -- where fp64 issue binds, Goldbeter, the recompute
-// factor of the apron rows is what is left to cut: (64 + 8) / 64 x 128 / 120 = 1.20 against (32 + 8) / 32 x 64 / 56 = 1.43)
-constexpr PlanCandidate kPlanCandidates[] = {
-    {0, 0, 1, 0}, {0, 1, 1, 0}, {0, 2, 1, 0}, {1, 0, 1, 0}, {1, 1, 1, 0}, {2, 0, 1, 0}, {2, 1, 1, 0}, {2, 2, 1, 0},
-    {0, 0, 2, 0}, {0, 1, 2, 0}, {0, 2, 2, 0}, {1, 0, 2, 0}, {1, 1, 2, 0}, {2, 0, 2, 0}, {2, 1, 2, 0}, {2, 2, 2, 0},
-    {0, 0, 1, 1}, {0, 1, 1, 1}, {0, 2, 1, 1}, {1, 0, 1, 1}, {1, 1, 1, 1}, {2, 0, 1, 1}, {2, 1, 1, 1}, {2, 2, 1, 1},
-    {0, 0, 2, 1}, {0, 1, 2, 1}, {0, 2, 2, 1}, {1, 0, 2, 1}, {1, 1, 2, 1}, {2, 0, 2, 1}, {2, 1, 2, 1}, {2, 2, 2, 1},
-    // fifth dimension (round 4): two steps per launch (128-row chunks, or 64), non-temporal stores
-    {0, 0, 1, 1, 2}, {0, 1, 1, 1, 2}, {0, 2, 1, 1, 2}, {1, 0, 1, 1, 2}, {1, 1, 1, 1, 2}, {2, 1, 1, 1, 2},
-    {0, 0, 2, 1, 2}, {0, 1, 2, 1, 2}, {0, 2, 2, 1, 2}, {1, 0, 2, 1, 2}, {1, 1, 2, 1, 2}, {2, 1, 2, 1, 2},
-    // sixth (round 6): three steps per launch, the block as the strip (FHN fp64: kCanThreeSteps), non-temporal stores
-    // (whole-rounds chunks win by 7 % -- 293 rows = two rounds of resident blocks on 8192^2 against 192 rows = three and a bit --, plain
-    // stores by half a per cent on some boxes)
-    {0, 0, 1, 1, 3}, {0, 1, 1, 1, 3}, {0, 2, 1, 1, 3}, {1, 0, 1, 1, 3}, {1, 1, 1, 1, 3}, {1, 0, 1, 0, 3}, {1, 1, 1, 0, 3},
-    // (round 8) ... and its eight-wide form, chunk mode 3: 488 valid lanes of 512, one block per CU, whole rounds of 256 resident blocks
-    // (8192^2: -2.9 / -3.3 % against the best four-wide plan in two runs; 4096^2, where 9 x 488 columns waste what 18 x 232 do: +2.4 / +3.0 %.  Plain stores: +0.5 %,
-    // no candidate.  profiles/r08/block_strip_eight_ab.txt)
-    {3, 0, 1, 1, 3}, {3, 1, 1, 1, 3}, {3, 2, 1, 1, 3},
-    // ... and in fp32: two columns per lane, a strip per wavefront (kThreeStepCols)
-    {0, 0, 2, 1, 3}, {0, 1, 2, 1, 3}, {0, 2, 2, 1, 3}, {1, 0, 2, 1, 3}, {1, 1, 2, 1, 3}, {2, 1, 2, 1, 3}};
-constexpr int kNumPlanCandidates = (int)(sizeof kPlanCandidates / sizeof kPlanCandidates[0]);
-
-template <typename Real, int MODEL>
-hipError_t launch_fused_t(const SlabDesc &d, const FusedCall &c, int row_begin, int row_end, int row_begin2, int row_end2, int js, int ny,
-                          hipStream_t st)
-{
-	clear_launch_status();
-	if (row_end <= row_begin) {
-		// nothing to launch: the events a caller bound to the launch are recorded on the stream instead, so that a wait on them sees
-		// this call and not an earlier one
-		if (c.geometry) return hipSuccess;
-		if (c.start_event)
-			if (hipError_t e = hipEventRecord(c.start_event, st); e != hipSuccess) return e;
-		if (c.done_event)
-			if (hipError_t e = hipEventRecord(c.done_event, st); e != hipSuccess) return e;
-		return hipSuccess;
-	}
-	if (row_end2 < row_begin2) row_end2 = row_begin2;
-	// Two steps per launch: plain steps only, and not the diffusion-only variant (no instantiation: that model is a plumbing case).
-	constexpr bool kCanTwoSteps = MODEL != kModelDiffusionOnly;
-	if (c.steps != 1 && (c.embed || !((c.steps == 2 && kCanTwoSteps) || (c.steps == 3 && kCanThreeSteps<Real, MODEL> && (kThreeStepCols<Real, MODEL> == 1 || d.nx % 2 == 0)))))
-		return hipErrorInvalidValue;
-	// (the kernels that address rows by 32-bit offsets into the plane: fused_steps_supported keeps such a launch from being asked for)
-	if (c.steps == 3 && kScalarRows<Real, MODEL, kThreeStepCols<Real, MODEL>, 3> && !fused_scalar_rows_addressable(d.nx, fused_addressed_rows(d), (long)sizeof(Real)))
-		return hipErrorInvalidValue;
-	// rows may extend into the ghost region (deep-halo steps), but the pipeline reads kStepHalo rows per step beyond them
-	if (!d.wrap && (row_begin < -(kGhost - c.steps * kStepHalo) || row_end > d.nyl + (kGhost - c.steps * kStepHalo))) return hipErrorInvalidValue;
-	const Slab<Real> s = typed<Real>(d);
-	FusedArgs<Real> a;
-	a.in_u = row0<Real>(c.y0.u, d.nx);
-	a.in_v = row0<Real>(c.y0.v, d.nx);
-	a.out_u = row0<Real>(c.yout.u, d.nx);
-	a.out_v = row0<Real>(c.yout.v, d.nx);
-	const step::Sizes hs(c.dt);
-	a.h1 = (Real)hs.h[0];
-	a.h2 = (Real)hs.h[1];
-	a.h3 = (Real)hs.h[2];
-	a.h6 = (Real)hs.h[3];
-	for (int k = 0; k < 5; k++) a.absorb[k] = c.absorb[k];
-	for (int k = 0; k < 4; k++) a.absorb2[k] = c.absorb2[k];
-	for (int k = 0; k < 4; k++) a.absorb3[k] = c.absorb3[k];
-	a.js = js;
-	a.ny = ny;
-	const int rows = row_end - row_begin, rows2 = row_end2 - row_begin2;
-	// two columns per lane need an even nx (a pair must not straddle the periodic seam; rows then are 8- / 16-byte aligned too)
-	const bool cols2_ok = !c.embed && d.nx % 2 == 0;
-	// (where nothing has been measured: the packed arithmetic for fp32, one column for fp64 -- fused_default_columns)
-	int cols_default = (cols2_ok && sizeof(Real) == 4) ? 2 : 1;
-	if (const char *e = tuning::knob("CRD_FUSED_COLS")) cols_default = (std::atoi(e) == 2 && cols2_ok) ? 2 : 1;
-	// Four adjacent strips per block marching in lockstep: 0.417 ms on 8192^2 fp64 against 0.441 without the barriers and
-	// 0.4205 with one barrier per four iterations (tools/tune_fused.py, interleaved in one process; fp32 0.219 vs 0.232,
-	// Goldbeter -- instruction-bound -- unchanged); 2 or 8 strips per block lose half of the gain, 3 / 5 / 6 more.
-	int sw = kWavesPerBlock;
-	if (const char *e = tuning::knob("CRD_FUSED_STRIPS")) {
-		const int v = std::atoi(e);
-		if (v >= 1 && v <= kMaxWavesPerBlock) sw = v;
-	}
-	const int sw_plain = sw;
-	a.sw = sw;
-	a.err_partials = c.err_partials ? c.err_partials + c.err_offset : nullptr;
-	a.err_lo = d.wrap ? INT32_MIN : 0;
-	a.err_hi = d.wrap ? INT32_MAX : d.nyl;
-	a.rtol = (Real)c.rtol;
-	a.atol = (Real)c.atol;
-	// the reaction block of a diffusion-only run is skipped, absorbing rows included (src/GoldbeterModel_torus.cpp:668)
-	constexpr bool kCanAbsorb = MODEL != kModelDiffusionOnly;
-	const bool absorb1 = kCanAbsorb && (c.absorb[0] || c.absorb[1] || c.absorb[2] || c.absorb[3] || (c.embed && c.absorb[4]));
-	const bool absorb12 = absorb1 || (kCanAbsorb && (c.absorb2[0] || c.absorb2[1] || c.absorb2[2] || c.absorb2[3])) ||
-	                      (kCanAbsorb && c.steps == 3 && (c.absorb3[0] || c.absorb3[1] || c.absorb3[2] || c.absorb3[3]));  // (any stage of any step of the launch)
-	// (fp32: the three-step pipeline with the absorbing-row selects does not fit the registers -- 256 and scratch; the steppers step
-	// such triples as a pair and a single step, run_steps: triple_absorbs)
-	if (c.steps == 3 && sizeof(Real) == 4 && absorb12) return hipErrorInvalidValue;
-	auto block = [&]() { return dim3(kLanes * sw); };
-
-	int cols = cols_default, steps = 1;
-	bool nt = false;
-	// The launch's geometry in two layers: configure() fixes the plan's choices, layout() cuts the rows in R -- the caller's, or
-	// a part of them (fire() below) -- into items accordingly.
-	int R[4] = {row_begin, row_end, row_begin2, row_end2}, plan_mode = 0, plan_remap = 0, chunk_override = 0;
-	auto layout = [&]() {
-		const int rows_a = R[1] - R[0], rows_b = R[3] - R[2];
-		const int nsb = (a.nstrips + sw - 1) / sw;
-		a.chunk = chunk_override > 0 ? std::min(chunk_override, rows_a + rows_b) : fused_chunk_rows<Real, MODEL>(a.nstrips, rows_a + rows_b, plan_mode, cols, steps, sw);
-		const int n1 = (rows_a + a.chunk - 1) / a.chunk, n2 = (rows_b + a.chunk - 1) / a.chunk;
-		a.nchunks = n1 + n2;
-		a.first2 = n2 > 0 ? n1 : a.nchunks;
-		a.r_begin[0] = R[0];
-		a.r_end[0] = R[1];
-		a.r_begin[1] = R[2];
-		a.r_end[1] = R[3];
-		a.nitems = a.nstrips * a.nchunks;
-		a.nblocks = nsb * a.nchunks;
-		a.remap = plan_remap;
-		if (const char *e = tuning::knob("CRD_FUSED_REMAP")) a.remap = std::atoi(e);
-		a.xs_lanes = 1;
-		if (a.remap == 2) {
-			const int per_xcd = resident_wavefronts<Real, MODEL>(cols, steps) / sw / kNumXcd;
-			if (rows_b > 0 || a.nchunks < 2 * kNumXcd || per_xcd < nsb) {
-				a.remap = 0;  // two row ranges, or too few chunks / slots for lanes: plain order
-			} else {
-				a.xs_lanes = per_xcd / nsb;
-				const int most = (a.nchunks + kNumXcd - 1) / kNumXcd;  // chunks of the best-served XCD
-				a.nblocks = kNumXcd * ((most + a.xs_lanes - 1) / a.xs_lanes) * nsb * a.xs_lanes;
-			}
-		}
-	};
-	// strips of the launch, given cols, steps and the block's width `w`
-	auto set_width = [&](int w) {
-		sw = a.sw = w;
-		const int valid = cols * kLanes - 2 * steps * (c.embed ? kApron + 1 : kApron);  // (the embedded estimators' fifth stage costs one more apron column per side)
-		a.nstrips = (d.nx + valid - 1) / valid;
-		if ((steps == 2 && cols == 1 && kCoop<Real, MODEL, 1, 2>) || (steps == 3 && kCoop<Real, MODEL, 1, 3>)) {  // the block as the strip: one apron around its sw wavefronts
-			const int block_valid = sw * kLanes - 2 * steps * kApron;
-			a.nstrips = sw * ((d.nx + block_valid - 1) / block_valid);
-		}
-	};
-	auto configure = [&](int one_round, int remap, int want_cols, int want_nt = 0, int want_steps = 1) {
-		steps = (want_steps == 3 && kCanThreeSteps<Real, MODEL> && (kThreeStepCols<Real, MODEL> == 1 || cols2_ok)) ? 3 : (want_steps >= 2 && kCanTwoSteps) ? 2 : 1;
-		nt = want_nt != 0;
-		if (const char *e = tuning::knob("CRD_FUSED_NT")) nt = std::atoi(e) != 0;
-		cols = (want_cols == 2 && cols2_ok) ? 2 : 1;
-		if (const char *e = tuning::knob("CRD_FUSED_COLS")) cols = (std::atoi(e) == 2 && cols2_ok) ? 2 : 1;
-		if (steps == 3) cols = kThreeStepCols<Real, MODEL>;  // (the three-step pipeline has ONE form per model and precision)
-		// Chunk mode 3, the eight-wide block strip: where the launch is the three-step fp64 FHN kernel's (kCanWide); everywhere else mode 1.
-		const bool wide = one_round == 3 && kCanWide<Real, MODEL, 1, 3> && steps == 3 && cols == 1 && !c.embed && sw_plain == kWavesPerBlock;
-		if (one_round == 3 && !wide) one_round = 1;
-		set_width(wide ? kWideWaves : sw_plain);
-		plan_mode = one_round;
-		plan_remap = remap;
-		layout();
-	};
-	auto fire = [&]() -> hipError_t {
-		if (c.embed) {
-			if (!c.err_partials || c.err_capacity < c.err_offset + a.nitems || !c.err_sum) return hipErrorInvalidValue;
-			auto with = [&](auto absorb_c, auto embed_c, auto nt_c) {
-				auto kernel = crd_rk4_fused_step_kernel<Real, MODEL, decltype(absorb_c)::value && kCanAbsorb, decltype(embed_c)::value, 1, decltype(nt_c)::value>;
-				// (the sum deferred to the caller -- another stream, launch_sum_partials: the event is this kernel's own completion)
-				if (c.err_defer_sum && c.done_event) hipExtLaunchKernelGGL(kernel, dim3(a.nblocks), block(), 0, st, nullptr, c.done_event, 0, s, a);
-				else kernel<<<a.nblocks, block(), 0, st>>>(s, a);
-			};
-			auto with_embed = [&](auto absorb_c, auto nt_c) {
-				if (c.embed == 2) with(absorb_c, std::integral_constant<int, 2>{}, nt_c);
-				else with(absorb_c, std::integral_constant<int, 1>{}, nt_c);
-			};
-			auto with_nt = [&](auto absorb_c) {
-				if (nt) with_embed(absorb_c, std::true_type{});
-				else with_embed(absorb_c, std::false_type{});
-			};
-			if (absorb1) with_nt(std::true_type{});
-			else with_nt(std::false_type{});
-			if (c.err_items_out) *c.err_items_out = a.nitems;
-			if (c.err_defer_sum) return launch_status();  // (the second launch of a cut attempt sums both launches' partials)
-			if (c.done_event) hipExtLaunchKernelGGL(crd_sum_partials_kernel, dim3(1), dim3(256), 0, st, nullptr, c.done_event, 0, (const double *)c.err_partials, c.err_offset + a.nitems, c.err_sum);
-			else crd_sum_partials_kernel<<<1, 256, 0, st>>>(c.err_partials, c.err_offset + a.nitems, c.err_sum);
-		} else {
-			// plain step: absorbing rows x columns per lane x store hint x steps per launch, all compile-time
-			bool last_launch = true, first_launch = true;  // (of this call: the ones a done_event / a start_event is bound to)
-			bool bad_width = false;
-			auto with = [&](auto absorb_c, auto cols_c, auto nt_c, auto steps_c) {
-				constexpr int kSteps = decltype(steps_c)::value;
-				constexpr int kLaunched = (kSteps == 3 ? kCanThreeSteps<Real, MODEL> && decltype(cols_c)::value == kThreeStepCols<Real, MODEL> &&
-				                                             !(sizeof(Real) == 4 && decltype(absorb_c)::value)  // (never launched: see above)
-				                                       : kCanTwoSteps) ? kSteps : 1;
-				constexpr bool kAbsorb = decltype(absorb_c)::value && kCanAbsorb;
-				auto go = [&](auto kernel) {
-					hipEvent_t e0 = first_launch ? c.start_event : nullptr, e1 = last_launch ? c.done_event : nullptr;
-					if (e0 || e1) hipExtLaunchKernelGGL(kernel, dim3(a.nblocks), block(), 0, st, e0, e1, 0, s, a);
-					else kernel<<<a.nblocks, block(), 0, st>>>(s, a);
-					first_launch = false;
-				};
-				if constexpr (kLaunched == 3 && kCanWide<Real, MODEL, decltype(cols_c)::value, 3> && !kAbsorb) {
-					if (sw == kWideWaves) {
-						go(crd_rk4_fused_step_kernel<Real, MODEL, false, 0, 1, decltype(nt_c)::value, 3, kWideWaves>);
-						return;
-					}
-				}
-				if (sw > kMaxWavesPerBlock) {  // (configure and the band cut below keep the eight-wide blocks to their own kernel)
-					bad_width = true;
-					return;
-				}
-				go(crd_rk4_fused_step_kernel<Real, MODEL, kAbsorb, 0, decltype(cols_c)::value, decltype(nt_c)::value, kLaunched>);
-			};
-			auto with_steps = [&](auto absorb_c, auto cols_c, auto nt_c) {
-				if (steps == 3) with(absorb_c, cols_c, nt_c, std::integral_constant<int, 3>{});
-				else if (steps == 2) with(absorb_c, cols_c, nt_c, std::integral_constant<int, 2>{});
-				else with(absorb_c, cols_c, nt_c, std::integral_constant<int, 1>{});
-			};
-			auto with_cols = [&](auto absorb_c, auto nt_c) {
-				if (cols == 2) with_steps(absorb_c, std::integral_constant<int, 2>{}, nt_c);
-				else with_steps(absorb_c, std::integral_constant<int, 1>{}, nt_c);
-			};
-			auto with_nt = [&](auto absorb_c) {
-				if (nt) with_cols(absorb_c, std::true_type{});
-				else with_cols(absorb_c, std::false_type{});
-			};
-			auto launch = [&](bool with_selects) {
-				if (with_selects) with_nt(std::true_type{});
-				else with_nt(std::false_type{});
-			};
-			if (steps >= 2 && absorb12) {
-				// (Three steps per launch alike: ONE launch of the kernel with the selects -- 246 registers against 244, two wavefronts per
-				// SIMD either way -- measured 0.2579 ms per step against 0.2180 with the cut and 0.2049 without absorbing rows: it is
-				// the kernel that holds both bodies that is slow, not its occupancy.)
-				// Two steps per launch with absorbing rows on.  The ABSORB kernel holds the body with the selects AND the one without
-				// (it decides per chunk), and the former's scalar registers spill into two vector registers of the whole kernel: 170
-				// VGPRs, two wavefronts per SIMD instead of three for EVERY item of the launch (+20 ... 38 % measured).  So the rows are
-				// cut: those whose pipeline can meet a global boundary row -- within 2 kApron rows of rows ny - 1 / 0, a band of 18 --
-				// go out first as a launch of their own (ABSORB kernel, 3-row items: it is the items' length, not their number, that
-				// sets such a launch's duration), the rest as launches of the select-free kernel.  Same arithmetic, same bits.
-				const int want[4] = {R[0], R[1], R[2], R[3]};
-				int with_sel[4][2], without[6][2], n_with = 0, n_without = 0;
-				bool fits = true;
-				for (int r = 0; r < 2 && fits; r++) {
-					int cursor = want[2 * r];
-					const int end = want[2 * r + 1];
-					for (int g = -1; g <= 1 && cursor < end; g++) {  // local rows of global rows ny - 1 and 0, one period down / here / one up
-						const int jb = (ny - 1 - js) + g * ny, lo = std::max(cursor, jb - steps * kApron), hi = std::min(end, jb + 2 + steps * kApron);
-						if (lo >= hi) continue;
-						if (cursor < lo) {
-							if (n_without == 6) fits = false;
-							else without[n_without][0] = cursor, without[n_without++][1] = lo;
-						}
-						if (n_with == 4) fits = false;
-						else with_sel[n_with][0] = lo, with_sel[n_with++][1] = hi;
-						cursor = hi;
-					}
-					if (cursor < end) {
-						if (n_without == 6) fits = false;
-						else without[n_without][0] = cursor, without[n_without++][1] = end;
-					}
-				}
-				// (the eight-wide block strip has no body with the selects: those launches go out four wide, the select-free ones eight wide)
-				const int sw_bulk = sw;
-				if (!fits || n_with == 0) {
-					if (sw_bulk != sw_plain) set_width(sw_plain), layout();
-					launch(true);
-					if (sw_bulk != sw_plain) set_width(sw_bulk), layout();
-				} else {
-					auto issue = [&](int (*piece)[2], int count, bool selects, int item_rows, bool final_pieces) {
-						for (int q = 0; q < count; q += 2) {
-							last_launch = final_pieces && q + 2 >= count;
-							R[0] = piece[q][0];
-							R[1] = piece[q][1];
-							R[2] = q + 1 < count ? piece[q + 1][0] : 0;
-							R[3] = q + 1 < count ? piece[q + 1][1] : 0;
-							chunk_override = item_rows;
-							set_width(selects ? sw_plain : sw_bulk);
-							layout();
-							launch(selects);
-						}
-					};
-					issue(with_sel, n_with, true, 3, n_without == 0);
-					issue(without, n_without, false, 0, true);
-					last_launch = true;
-					for (int q = 0; q < 4; q++) R[q] = want[q];
-					chunk_override = 0;
-					set_width(sw_bulk);
-					layout();
-				}
-			} else {
-				launch(steps >= 2 ? absorb12 : absorb1);
-			}
-			if (bad_width) return hipErrorInvalidConfiguration;
-		}
-		return launch_status();
-	};
-
-	// Launch plan: measured once per context on the first full-size launch (a launch reads one plane set and writes another, so
-	// repeating it is harmless: every candidate writes the same values), then reused for every launch of similar height.
-	FusedPlan *plan = c.plan;
-	const bool plannable = plan && rows2 == 0 && (long)rows * d.nx >= (1L << 20) && !tuning::enabled();  // (under CRD_TUNING the knobs decide)
-	if (plannable && !plan->tuned && plan->autotune && !c.geometry) {
-		hipEvent_t e0 = nullptr, e1 = nullptr;
-		// (nothing else may run on the device while candidates are timed: a halo exchange still in flight on the second stream
-		// made a ring context pick a different -- worse -- plan than a plain slab of the same shape)
-		hipError_t err = hipDeviceSynchronize();
-		if (err == hipSuccess) err = hipEventCreate(&e0);
-		if (err == hipSuccess) err = hipEventCreate(&e1);
-		// What a candidate is timed on: with a scratch plane set, launches that step yout -> scratch -> yout -> ... (each reads what
-		// its predecessor wrote, as consecutive steps do); without, repetitions of y0 -> yout.  The difference matters on slabs
-		// small enough for the memory-side cache: an input that is never overwritten stays there, and a plan that keeps its output
-		// out of the caches (non-temporal stores) then looks better than it steps.
-		const bool pingpong = c.tune_scratch.u != nullptr && c.tune_scratch.v != nullptr;
-		auto set_io = [&](const Planes &in, const Planes &out) {
-			a.in_u = row0<Real>(in.u, d.nx);
-			a.in_v = row0<Real>(in.v, d.nx);
-			a.out_u = row0<Real>(out.u, d.nx);
-			a.out_v = row0<Real>(out.v, d.nx);
-		};
-		int flip = 0;
-		auto fire_timed = [&]() -> hipError_t {
-			if (pingpong) {
-				if (flip) set_io(c.tune_scratch, c.yout);
-				else set_io(c.yout, c.tune_scratch);
-				flip ^= 1;
-			}
-			return fire();
-		};
-		if (pingpong && err == hipSuccess) {
-			configure(0, 0, cols_default, 0);
-			err = fire();  // yout holds a state to step on from
-		}
-		// Candidates are timed round-robin, kRounds times, and each keeps its best round: a device's clock drifts while the
-		// measurement runs (a Goldbeter launch sequence lost 15 % over five candidates timed one after the other), and a
-		// candidate must not win or lose by its place in the queue.
-		constexpr int kCandidates = kNumPlanCandidates, kRounds = 3;
-		// (a candidate that takes more steps per launch than the call reads more rows beyond the launch's: they must exist -- a launch of
-		// a multi-slab cycle that reaches far into the ghost region is measured with the candidates of its own step count only)
-		const bool room_for_two = d.wrap || (row_begin >= -(kGhost - 2 * kStepHalo) && row_end <= d.nyl + (kGhost - 2 * kStepHalo));
-		const bool two_steps_ok = kCanTwoSteps && !c.embed && c.steps == 1 && d.nyl >= 4 * kStepHalo && room_for_two;  // (the caller steps pairs once the plan says so)
-		const bool room_for_three = d.wrap || (row_begin >= -(kGhost - 3 * kStepHalo) && row_end <= d.nyl + (kGhost - 3 * kStepHalo));
-		const bool three_steps_ok = two_steps_ok && kCanThreeSteps<Real, MODEL> && (kThreeStepCols<Real, MODEL> == 1 || cols2_ok) && d.nyl >= 6 * kStepHalo &&
-		                            (d.wrap || sizeof(Real) == 4) && room_for_three &&
-		                            (!kScalarRows<Real, MODEL, kThreeStepCols<Real, MODEL>, 3> || fused_scalar_rows_addressable(d.nx, fused_addressed_rows(d), (long)sizeof(Real))) &&
-		                            !(sizeof(Real) == 4 && absorb12);  // (... or triples: single slabs, and in fp32 slabs of a run; fp32 without absorbing rows on)
-		float t_best[kCandidates];
-		bool live[kCandidates];
-		int reps = 3;
-		for (int k = 0; k < kCandidates; k++) {
-			t_best[k] = 0.f;
-			configure(kPlanCandidates[k].one_round, kPlanCandidates[k].remap, kPlanCandidates[k].cols, kPlanCandidates[k].nt, kPlanCandidates[k].steps);
-			live[k] = k == 0 || !(kPlanCandidates[k].one_round && a.chunk == fused_chunk_rows<Real, MODEL>(a.nstrips, rows, 0, cols, steps));  // (same as a 32-row plan)
-			if (live[k] && kPlanCandidates[k].one_round != plan_mode) live[k] = false;  // (chunk mode 3 where the eight-wide kernel does not run: that is mode 1's candidate)
-			if (live[k] && kPlanCandidates[k].steps != ((kPlanCandidates[k].steps == 3 ? three_steps_ok : two_steps_ok) ? steps : 1)) live[k] = false;  // (several steps per launch: plain steps)
-			if (live[k] && steps == 2 && cols == 2 && sizeof(Real) == 8) live[k] = false;  // (256 VGPRs, one wavefront per SIMD: measured 0.347 against 0.312 ms)
-			if (live[k] && kPlanCandidates[k].remap != a.remap) live[k] = false;  // (the mapping fell back to dispatch order)
-			if (live[k] && kPlanCandidates[k].cols != cols) live[k] = false;      // (two columns per lane not possible here, or pinned by a knob)
-			if (live[k] && (kPlanCandidates[k].nt != 0) != nt) live[k] = false;   // (pinned by a knob)
-		}
-		for (int round = 0; round < kRounds && err == hipSuccess; round++)
-			for (int k = 0; err == hipSuccess && k < kCandidates; k++) {
-				if (!live[k]) continue;
-				configure(kPlanCandidates[k].one_round, kPlanCandidates[k].remap, kPlanCandidates[k].cols, kPlanCandidates[k].nt, kPlanCandidates[k].steps);
-				float ms = 0.f;
-				for (int pass = 0; pass < 2 && err == hipSuccess; pass++) {
-					err = fire_timed();  // warm-up of this variant
-					if (err == hipSuccess) err = hipEventRecord(e0, st);
-					for (int r = 0; err == hipSuccess && r < reps; r++) err = fire_timed();
-					if (err == hipSuccess) err = hipEventRecord(e1, st);
-					if (err == hipSuccess) err = hipEventSynchronize(e1);
-					if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-					if (round > 0 || k > 0 || reps > 3 || ms >= 4.0f || ms <= 0.f) break;
-					reps = (int)(12.0f / ms) + 1 < 40 ? (int)(12.0f / ms) + 1 : 40;  // time about four milliseconds' worth per candidate and round, then again
-				}
-				if (err != hipSuccess) break;
-				ms /= (float)(reps * steps);  // per STEP: a two-step launch does twice the work
-				if ((plan->autotune >= 2 || tuning::verbose()))
-					std::fprintf(stderr, "libcrd autotune: %d x %d rows, round %d, chunk mode %d (%d rows), mapping %d, %d column(s) per lane, %s stores, %d step(s) per launch: %.4f ms per step (%d launches timed)\n",
-					             d.nx, rows, round, kPlanCandidates[k].one_round, a.chunk, a.remap, cols, nt ? "non-temporal" : "plain", steps, ms, reps);
-				if (t_best[k] == 0.f || ms < t_best[k]) t_best[k] = ms;
-			}
-		// Final: with two dozen candidates a few per cent apart, the fastest of the short bursts above is as often the luckiest as
-		// the best, and a burst runs at clocks a sustained run does not keep.  The plain plan and the three fastest candidates are
-		// therefore timed again, ~16 ms each and twice round, and the final alone decides between them.
-		constexpr int kFinalists = 4, kFinalRounds = 2;
-		int finalist[kFinalists] = {0, -1, -1, -1};
-		for (int f = 1; f < kFinalists; f++)
-			for (int k = 1; k < kCandidates; k++) {
-				if (!live[k] || t_best[k] <= 0.f || k == finalist[1] || k == finalist[2]) continue;
-				if (finalist[f] < 0 || t_best[k] < t_best[finalist[f]]) finalist[f] = k;
-			}
-		float t_final[kFinalists] = {0.f, 0.f, 0.f, 0.f};
-		for (int round = 0; round < kFinalRounds && err == hipSuccess; round++)
-			for (int f = 0; err == hipSuccess && f < kFinalists; f++) {
-				const int k = finalist[f];
-				if (k < 0 || t_best[k] <= 0.f) continue;
-				configure(kPlanCandidates[k].one_round, kPlanCandidates[k].remap, kPlanCandidates[k].cols, kPlanCandidates[k].nt, kPlanCandidates[k].steps);
-				const int reps2 = (int)(16.0f / t_best[k]) + 1 < 400 ? (int)(16.0f / t_best[k]) + 1 : 400;
-				float ms = 0.f;
-				err = fire_timed();
-				if (err == hipSuccess) err = hipEventRecord(e0, st);
-				for (int r = 0; err == hipSuccess && r < reps2; r++) err = fire_timed();
-				if (err == hipSuccess) err = hipEventRecord(e1, st);
-				if (err == hipSuccess) err = hipEventSynchronize(e1);
-				if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-				if (err != hipSuccess) break;
-				ms /= (float)(reps2 * steps);
-				if ((plan->autotune >= 2 || tuning::verbose()))
-					std::fprintf(stderr, "libcrd autotune: %d x %d rows, final %d, chunk mode %d (%d rows), mapping %d, %d column(s) per lane, %s stores, %d step(s) per launch: %.4f ms per step (%d launches timed)\n",
-					             d.nx, rows, round, kPlanCandidates[k].one_round, a.chunk, a.remap, cols, nt ? "non-temporal" : "plain", steps, ms, reps2);
-				if (t_final[f] == 0.f || ms < t_final[f]) t_final[f] = ms;
-			}
-		int best_k = 0;
-		float base = t_best[0], best = t_best[0];
-		if (t_final[0] > 0.f) {
-			base = best = t_final[0];
-			for (int f = 1; f < kFinalists; f++)
-				if (finalist[f] >= 0 && t_final[f] > 0.f && t_final[f] < best) {
-					best = t_final[f];
-					best_k = finalist[f];
-				}
-		}
-		if (e0) (void)hipEventDestroy(e0);
-		if (e1) (void)hipEventDestroy(e1);
-		set_io(c.y0, c.yout);  // (the launch this call was made for follows below)
-		if (err != hipSuccess) return err;
-		if (best > 0.985f * base) best_k = 0;  // a candidate has to beat the plain plan by more than timing noise
-		plan->tuned = 1;
-		plan->one_round = kPlanCandidates[best_k].one_round;
-		plan->remap = kPlanCandidates[best_k].remap;
-		plan->cols = kPlanCandidates[best_k].cols;
-		plan->nt = kPlanCandidates[best_k].nt;
-		plan->steps = kPlanCandidates[best_k].steps;
-		plan->rows = rows;
-		plan->ms_default = base;
-		plan->ms_best = best_k ? best : base;
-	}
-	// A measured plan applies to the launches it was measured on (heights within a tenth of it: the sweeps of a deep-halo cycle are).
-	// Launches it was not measured on -- edge bands, short ranges -- still take its columns per lane: that choice is about the
-	// kernel's arithmetic, not about the launch's shape.  A PINNED plan (crd_set_launch_plan) is an instruction, not a measurement:
-	// every single-range launch of the context takes all of it, of whatever size (chunk mode and mapping fall back inside configure
-	// where the launch is too small for them), two-range launches its columns per lane and store hint.
-	const bool pinned = plan && plan->tuned && plan->pinned && !tuning::enabled();
-	const bool use_plan = (plannable && plan->tuned && 10L * rows >= 9L * plan->rows && 10L * rows <= 11L * plan->rows) || (pinned && rows2 == 0);
-	configure(use_plan ? plan->one_round : 0, use_plan ? plan->remap : 0, (plan && plan->tuned) ? plan->cols : cols_default, (use_plan || pinned) ? plan->nt : 0, c.steps);
-	if (c.geometry) {
-		FusedGeometry &g = *c.geometry;
-		const int apron = steps * (c.embed ? kApron + 1 : kApron);
-		g.real_bytes = (int)sizeof(Real);
-		g.model = MODEL;
-		g.absorb = steps >= 2 ? 0 : (absorb1 ? 1 : 0);  // (several steps with absorbing rows on: the bulk goes out as the select-free kernel)
-		g.embed = c.embed;
-		g.cols = cols;
-		g.nt = nt ? 1 : 0;
-		g.steps = steps;
-		g.strips = a.nstrips;
-		g.chunk_rows = a.chunk;
-		g.chunks = a.nchunks;
-		g.blocks = a.nblocks;
-		g.waves_per_block = sw;
-		g.chunk_mode = plan_mode;
-		g.fill_iterations = 2 * apron;
-		g.iterations_per_trip = c.embed ? CRD_EMBED_SLOTS : 4;
-		g.lanes = kLanes;
-		g.lanes_valid = (cols * kLanes - 2 * apron) / cols;
-		if ((steps == 2 && cols == 1 && kCoop<Real, MODEL, 1, 2>) || (steps == 3 && kCoop<Real, MODEL, 1, 3>)) g.lanes_valid = (sw * kLanes - 2 * apron) / sw;  // the block as the strip: 60 (58) of 64 on average
-		g.mapping = a.remap;
-		g.wave_iterations = (long)a.nstrips * ((long)(rows + rows2) + (long)a.nchunks * 2 * apron);
-		return hipSuccess;
-	}
-	return fire();
-}
 
 }  // namespace
 
-// the fp32 half of launch_fused_step (crd_fused_f32.hip)
-hipError_t launch_fused_step_f32(const SlabDesc &d, const FusedCall &c, int row_begin, int row_end, int row_begin2, int row_end2, hipStream_t s);
-
 }  // namespace crd
+

@@ -67,7 +67,7 @@ const char *stage_kernel_name(int precision, int model);
 
 // Whole RK4 step in one launch (all four stages on chip); reads y0 with kGhost ghost rows, writes yout rows
 // [row_begin, row_end) and, if non-empty, [row_begin2, row_end2).  absorb[k] = t_stage_k < tBoundary for the four stages.
-// How the one-launch step cuts a slab into work items and deals them to the XCDs (crd_fused.hip: kPlanCandidates), measured
+// How the one-launch step cuts a slab into work items and deals them to the XCDs (crd_fused_plan.h: kPlanCandidates), measured
 // on the first full-size launch of a context when autotune is set.  Every plan computes bit-identical results.
 struct FusedPlan {
 	int autotune = 1;                      // 0: never measure; 1: measure on the first full-size launch; 2: ... and print every timing to stderr
@@ -158,6 +158,7 @@ inline bool fused_scalar_rows_addressable(long nx, long rows, long real_bytes)
 }
 long fused_addressed_rows(const SlabDesc &d);  // rows of a plane a launch can address: the slab's own, and its ghost rows unless phi wraps inside it
 int fused_max_items(const SlabDesc &d);
+int device_cus();  // compute units of a device of this node (the GPUs of a node are alike)
 
 // Layout adaptors between the AoS boundary layout (host precision: f64 or device precision) and SoA planes.
 hipError_t launch_aos_to_planes(int precision, int src_is_f64, const void *aos, Planes dst, int nx, int nyl, hipStream_t s);

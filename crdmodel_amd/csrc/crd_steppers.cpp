@@ -114,7 +114,7 @@ int staged_step_blocks(crd_ctx *const *cs, int n, double t, double dt)
 	return CRD_OK;
 }
 
-// Fused stepper on several slabs: ONE exchange every E = exchange_every steps (crd_set_exchange_period; default 8), G = 4 E ghost
+// Fused stepper on several slabs: ONE exchange every E = exchange_every steps (crd_set_exchange_period; default kDefaultExchangeEvery = 8, kTallSlabExchangeEvery = 10 where every slab has 256 rows or more), G = 4 E ghost
 // rows of both fields.  Step q of a cycle (q = 0 right after an exchange) produces rows [-e, nyl + e) with e = 4 (E-1-q): the
 // still-valid part of the ghost region is recomputed redundantly (same kernel, same inputs, so bit-identical to what the owning
 // slab computes) instead of being communicated.  The last step of a cycle (e = 0) is split

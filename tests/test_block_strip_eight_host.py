@@ -1,5 +1,5 @@
 """The theta cut of the block-strip kernels for blocks of four and of eight wavefronts, in plain Python mirroring the host code
-(crd_fused_impl.h: configure / set_width for the strip count, fused_item_multi_step for x0, place, span and lane_stores): every column
+(crd_fused_plan.h: strip_count for the strip count; crd_fused_impl.h: fused_item_multi_step for x0, place, span and lane_stores): every column
 of the grid is stored exactly once, for every nx from 64 to 2048.  And the set of widths at which a wavefront of the last block holds
 only parked lanes, derived from x0 -- what tests/test_gpu_block_strip_eight.py takes its hazard widths from.
 

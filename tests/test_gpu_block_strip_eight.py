@@ -1,4 +1,4 @@
-"""Launch-plan chunk mode 3: the three-step fp64 FHN block strip with EIGHT wavefronts around one apron (crd_fused_impl.h: kWideWaves;
+"""Launch-plan chunk mode 3: the three-step fp64 FHN block strip with EIGHT wavefronts around one apron (crd_fused_impl.h: kWideWaves; crd_fused_plan.h: choose;
 488 valid lanes of 512, one block per CU).  Every test pins plans with crd_set_launch_plan and asserts bit equality (np.array_equal on
 both fields) against the same problem stepped one step per launch under the plain plan (0, 0, 1, 1, 1).  FHN fp64 on the torus; the initial
 state is the reference rule's travelling wave plus a seeded perturbation of every point (on the wave's flat parts a wrong neighbour

@@ -7,8 +7,8 @@
         [--json profiles/r05/kernel_table.json]
     tools/kernel_regs.py --check --asm build/y-hip-amdgcn-amd-amdhsa-gfx950.s ...  # the two contracts alone, over EVERY kernel: exit 0 / 3 / 4
         (every kernel is reported and held to the LDS read hazards; the vmcnt contract -- no vector memory skipped on the execution mask --
-        binds the kernels that fill LDS by DMA, the only ones whose waits count operations by hand: a unit that includes crd_fused_impl.h
-        also EMITS its error-sum kernel, whose one store under `if (threadIdx.x == 0)` is skipped by design)
+        binds the kernels that fill LDS by DMA, the only ones whose waits count operations by hand: a unit that includes
+        crd_fused_launch.h also EMITS its error-sum kernel, whose one store under `if (threadIdx.x == 0)` is skipped by design)
 
 The loop is the kernel's largest loop by vector instructions (the pipeline's steady state: the unrolled iterations of one trip);
 counts are static -- instructions in the loop body between its header label and its back edge, whatever branches inside it skip.
@@ -306,8 +306,8 @@ def check_only(kernels):
         bad = []
         if k["async_lds_read_hazards"]:
             bad.append("%d register(s) with LDS reads in flight touched before the asm block that waits for them" % k["async_lds_read_hazards"])
-        # (the vmcnt contract is the ring pipelines': a kernel without LDS-DMA fills counts nothing by hand -- the error-sum kernel a unit
-        # inherits from crd_fused_impl.h stores under `if (threadIdx.x == 0)`, rightly)
+        # (the vmcnt contract is the ring pipelines': a kernel without LDS-DMA fills counts nothing by hand -- the error-sum kernel of
+        # crd_fused_launch.h stores under `if (threadIdx.x == 0)`, rightly)
         skipped = k["exec_skipped_vmem"] if k["lds_dma"] else 0
         if skipped:
             bad.append("%d vector-memory region(s) skipped on the execution mask" % skipped)
