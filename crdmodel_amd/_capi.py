@@ -120,6 +120,20 @@ class PsolveOptions(C.Structure):
     _fields_ = [("pre", C.c_int32), ("post", C.c_int32), ("coarse", C.c_int32), ("max_levels", C.c_int32), ("omega", C.c_double)]
 
 
+class LsolveOptions(C.Structure):
+    """crd_lsolve_options"""
+
+    _fields_ = [("part", C.c_int32), ("precondition", C.c_int32), ("restart", C.c_int32), ("max_iters", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
+                ("psolve", PsolveOptions)]
+
+
+class LsolveStats(C.Structure):
+    """crd_lsolve_stats"""
+
+    _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32), ("restarts", C.c_int32), ("matvecs", C.c_int32), ("psolves", C.c_int32), ("breakdown", C.c_int32),
+                ("r_norm", C.c_double), ("res_norm", C.c_double)]
+
+
 OBSERVE_MAX_PROBES = 16  # CRD_OBSERVE_MAX_PROBES
 
 
@@ -197,6 +211,11 @@ _SIGNATURES = {
     "crd_psolve_info": (C.c_int, [_vp, C.POINTER(PsolveOptions), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "crd_psolve_device": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(PsolveOptions), _vp, _vp]),
     "crd_psolve_host": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(PsolveOptions), _vp, _vp]),
+    "crd_lsolve_defaults": (C.c_int, [C.POINTER(LsolveOptions)]),
+    "crd_lsolve_info": (C.c_int, [_vp, C.POINTER(LsolveOptions), C.POINTER(C.c_int64)]),
+    "crd_lsolve_device": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(LsolveOptions), _vp, _vp, _vp, C.POINTER(LsolveStats)]),
+    "crd_lsolve_host": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(LsolveOptions), _vp, _vp, _vp, C.POINTER(LsolveStats)]),
+    "crd_krylov_probe_dots": (C.c_int, [_vp, _vp, C.c_int, _vp, C.POINTER(C.c_double)]),
     "crd_set_stepper": (C.c_int, [_vp, C.c_int]),
     "crd_step_rk4": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64]),
     "crd_synchronize": (C.c_int, [_vp]),

@@ -101,6 +101,7 @@ struct StreamSet {
 struct crd_recorder;  // crd_recorder.cpp
 namespace crd {
 struct PsolveWorkspace;  // crd_multigrid.cpp
+struct LsolveWorkspace;  // crd_krylov.cpp
 }
 
 struct crd_ctx {
@@ -125,6 +126,7 @@ struct crd_ctx {
 	void *stage_v = nullptr;  // ... and for the direction v of crd_jtimes_host (lazy, crd_jacobian.cpp)
 	size_t stage_v_bytes = 0;
 	crd::PsolveWorkspace *psolve = nullptr;  // levels of crd_psolve_*: planes and coefficient tables (lazy, crd_multigrid.cpp)
+	crd::LsolveWorkspace *lsolve = nullptr;  // basis, work vectors and scalars of crd_lsolve_* (lazy, crd_krylov.cpp)
 	void *ghost_lo = nullptr, *ghost_hi = nullptr;   // var0 of rows -1 / nyl for the AoS RHS (multi-slab)
 	void *edge_lo = nullptr, *edge_hi = nullptr;     // var0 of rows 0 / nyl-1 packed from an AoS vector
 	// theta-blocks (d0 > 1): var0 of the columns beside the block (ghost) and of its own first / last column (edge), nyl reals each,
@@ -232,6 +234,7 @@ inline bool absorbing(const crd_ctx *c, double t_stage) { return step::absorbing
 int resolve_stepper(const crd_ctx *c);  // CRD_STEPPER_STAGED / _FUSED, or -1 when the requested one is unavailable
 int check_group(crd_ctx *const *ctxs, int n);
 void psolve_release(crd_ctx *c);  // crd_multigrid.cpp: frees the workspace of crd_psolve_* (crd_destroy)
+void lsolve_release(crd_ctx *c);  // crd_krylov.cpp: likewise the workspace of crd_lsolve_*
 
 // crd_halo.cpp: fill ghost rows [-depth, 0) and [nyl, nyl + depth) of plane `plane_index` from the ring neighbours, on the comm streams
 int exchange_stage_input(crd_ctx *const *cs, int n, int plane_index, int depth, bool with_v);

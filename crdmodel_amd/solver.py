@@ -306,6 +306,32 @@ class Slab:
         self._check(lib().crd_psolve_info(self._h, C.byref(opt), C.byref(levels), nx, ny, C.byref(nbytes)), "crd_psolve_info")
         return levels.value, [(nx[k], ny[k]) for k in range(levels.value)], nbytes.value
 
+    @classmethod
+    def _lsolve_options(cls, part="diffusion", precondition=True, restart=30, max_iters=200, rtol=1e-8, atol=0.0, **psolve_options):
+        opt = capi.LsolveOptions()
+        opt.part, opt.precondition, opt.restart, opt.max_iters, opt.rtol, opt.atol = _part(part), int(precondition), restart, max_iters, rtol, atol
+        opt.psolve = cls._psolve_options(**dict(dict(pre=2, post=2, coarse=8, max_levels=16, omega=0.8), **psolve_options))
+        return opt
+
+    def lsolve(self, t, gamma, r, y=None, part="diffusion", precondition=True, restart=30, max_iters=200, rtol=1e-8, atol=0.0, **psolve_options):
+        """(z, stats) of (I - gamma J_part(t, y)) z = r by restarted GMRES on the device, right-preconditioned with the cycle of
+        Slab.psolve (crd_lsolve_host).  r and y are laid out like the state; y is needed for part "full" only.  stats is the
+        crd_lsolve_stats structure: converged, iterations, restarts, matvecs, psolves, breakdown, r_norm, res_norm.  Running out of
+        max_iters is not an error: stats.converged is 0 and z the last iterate."""
+        r = self._vector(r)
+        y = None if y is None else self._vector(y)
+        z, st = np.empty_like(r), capi.LsolveStats()
+        opt = self._lsolve_options(part, precondition, restart, max_iters, rtol, atol, **psolve_options)
+        self._check(lib().crd_lsolve_host(self._h, t, gamma, C.byref(opt), None if y is None else y.ctypes.data, r.ctypes.data, z.ctypes.data, C.byref(st)),
+                    "crd_lsolve_host")
+        return z, st
+
+    def lsolve_info(self, part="diffusion", precondition=True, restart=30, max_iters=200, rtol=1e-8, atol=0.0, **psolve_options):
+        """Device bytes of the workspace Slab.lsolve with these options keeps on the context (crd_lsolve_info)."""
+        opt, nbytes = self._lsolve_options(part, precondition, restart, max_iters, rtol, atol, **psolve_options), C.c_int64()
+        self._check(lib().crd_lsolve_info(self._h, C.byref(opt), C.byref(nbytes)), "crd_lsolve_info")
+        return nbytes.value
+
     # -- time stepping -----------------------------------------------------------------------------------------
     def set_stepper(self, stepper):
         s = STEPPERS[stepper] if isinstance(stepper, str) else stepper

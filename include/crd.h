@@ -343,6 +343,53 @@ int crd_psolve_info(crd_ctx *ctx, const crd_psolve_options *opt, int32_t *levels
 int crd_psolve_device(crd_ctx *ctx, double t, double gamma, const crd_psolve_options *opt, const void *r_aos_dev, void *z_aos_dev);
 int crd_psolve_host(crd_ctx *ctx, double t, double gamma, const crd_psolve_options *opt, const void *r_aos, void *z_aos);
 
+/* The linear solve of an implicit stage: (I - gamma J_part(t, y)) z = r by restarted, right-preconditioned GMRES(restart) on the
+ * device, from z = 0.  Vectors are those of crd_jtimes_*: AoS, the context's precision.  It solves A M u = r, z = M u, with
+ * A v = v - gamma J_part v through the launch of crd_jtimes_device and M the cycle of crd_psolve_device for I - gamma J_D(t) with the
+ * options `psolve` (precondition = 1), or the identity (precondition = 0).  With the preconditioner on the right the residual the
+ * iteration carries is the residual of the system itself: it stops when ||r - A z|| <= rtol ||r|| + atol, 2-norms over the whole vector.
+ *   A new Krylov vector w = A M V_j is orthogonalised against V_0 .. V_j by classical Gram-Schmidt applied twice, in four launches:
+ *   multi-dot h = V^T w (one pass over w per 8 basis vectors, double accumulators, per-block partials summed in a fixed order),
+ *   multi-axpy w -= V h with the partials of ||w||^2 from the same pass, and both again; the Hessenberg column is the sum of the two
+ *   coefficient sets.  The host reads that column -- j + 2 doubles, the one device-to-host copy of an inner iteration -- keeps the
+ *   Givens rotations and solves the small least-squares problem; a cycle ends with z += M (sum_i y_i V_i), one M for the cycle.
+ *   Breakdown: when ||w|| after the orthogonalisation is at most 2 u ||A M V_j|| (u the unit roundoff of the precision, ||A M V_j|| taken
+ *   as the 2-norm of the column), the column is final: the basis is not extended, nothing is divided by that norm, the solve has converged.
+ *   CRD_PART_DIFFUSION: J_D acts on var0 alone, so the iteration runs on var0 (var1 of every Krylov vector is +0) and z_var1 = r_var1
+ *   bit for bit; y is not read and may be NULL.  CRD_PART_FULL takes J(t, y) and needs y.
+ * gamma == 0 returns z = r exactly without iterating; r == 0 returns z = 0 with 0 iterations.  Reaching max_iters (inner iterations
+ * in total) is NOT an error: the call returns 0 with converged = 0 and z the last iterate.  Every loop is bounded by restart and max_iters.
+ * opt == NULL: the defaults (DIFFUSION, preconditioned, restart 30, max_iters 200, rtol 1e-8, atol 0, crd_psolve_defaults).
+ * CRD_EINVAL, before any device work: gamma negative or not finite; part CRD_PART_REACTION or none of the three; restart outside
+ * 1 .. 64; max_iters < 1; rtol or atol negative or not finite; z aliasing r or y; y == NULL with CRD_PART_FULL; psolve options that
+ * crd_psolve_* refuses.  CRD_ESTATE: a context that is one of several slabs and theta-block contexts, as for crd_psolve_*.
+ * Workspace: restart + 1 basis vectors, two work vectors and the reductions' partials, allocated by the first call on the context
+ * for the largest restart seen so far and freed by crd_destroy (CRD_ENOMEM if it cannot be had); crd_lsolve_info reports the device
+ * bytes a call with `opt` needs (the preconditioner's own workspace is crd_psolve_info's).  Launches go on the context's compute
+ * stream, and the call WAITS for it -- it reads scalars every inner iteration -- so _device too returns with z complete.
+ * stats (may be NULL): r_norm = ||r||; res_norm = the iteration's own residual norm at exit; restarts = cycles begun after the first;
+ * matvecs / psolves = launches of J v / of the cycle. */
+typedef struct crd_lsolve_options {
+	int32_t part;          /* CRD_PART_DIFFUSION (default) or CRD_PART_FULL */
+	int32_t precondition;  /* 1 (default): M = the crd_psolve cycle for I - gamma J_D; 0: none */
+	int32_t restart;       /* default 30; 1 .. 64 */
+	int32_t max_iters;     /* default 200; inner iterations in total */
+	double rtol, atol;     /* default 1e-8, 0 */
+	crd_psolve_options psolve;
+} crd_lsolve_options;
+typedef struct crd_lsolve_stats {
+	int32_t converged, iterations, restarts, matvecs, psolves, breakdown;
+	double r_norm, res_norm;
+} crd_lsolve_stats;
+int crd_lsolve_defaults(crd_lsolve_options *opt);
+int crd_lsolve_info(crd_ctx *ctx, const crd_lsolve_options *opt, int64_t *workspace_bytes);
+int crd_lsolve_device(crd_ctx *ctx, double t, double gamma, const crd_lsolve_options *opt, const void *y_aos_dev, const void *r_aos_dev, void *z_aos_dev,
+                      crd_lsolve_stats *stats);
+int crd_lsolve_host(crd_ctx *ctx, double t, double gamma, const crd_lsolve_options *opt, const void *y_aos, const void *r_aos, void *z_aos, crd_lsolve_stats *stats);
+/* For the test suite's gate on the reductions alone: out[i] = <V_i, w>, i < count (1 .. 65), as the solve's multi-dot forms it.
+ * vectors: `count` AoS vectors back to back, w: one, all HOST memory in the context's precision; out: `count` doubles. */
+int crd_krylov_probe_dots(crd_ctx *ctx, const void *vectors, int count, const void *w, double *out);
+
 /* Fast path that never leaves the GPU: nsteps classical RK4 steps of size dt on the context's resident state,
  * stage k of step n evaluated at t0 + n dt + c_k dt (replaces the ARKode(...) call, src/FHNmodel_torus.cpp:423).
  * Asynchronous; crd_synchronize() waits.  With several slabs every context of the run must make the same call: stepping is
