@@ -25,6 +25,8 @@ MODELS = {"fhn": MODEL_FHN, "goldbeter": MODEL_GOLDBETER}
 SURFACES = {"torus": SURFACE_TORUS, "flat": SURFACE_FLAT}
 STEPPERS = {"auto": STEPPER_AUTO, "staged": STEPPER_STAGED, "fused": STEPPER_FUSED}
 PARTS = {"full": PART_FULL, "diffusion": PART_DIFFUSION, "reaction": PART_REACTION}
+IMEX_EULER, IMEX_ARS222, IMEX_ARS443 = 0, 1, 2
+IMEX_SCHEMES = {"euler": IMEX_EULER, "ars222": IMEX_ARS222, "ars443": IMEX_ARS443}
 
 
 class Params(C.Structure):
@@ -134,6 +136,19 @@ class LsolveStats(C.Structure):
                 ("r_norm", C.c_double), ("res_norm", C.c_double)]
 
 
+class ImexOptions(C.Structure):
+    """crd_imex_options"""
+
+    _fields_ = [("scheme", C.c_int32), ("reserved", C.c_int32), ("lsolve", LsolveOptions)]
+
+
+class ImexStats(C.Structure):
+    """crd_imex_stats"""
+
+    _fields_ = [("steps", C.c_int64), ("solves", C.c_int64), ("iterations", C.c_int64), ("failed_step", C.c_int64), ("max_iterations", C.c_int32),
+                ("failed_stage", C.c_int32), ("t", C.c_double), ("worst_residual", C.c_double), ("max_abs_u", C.c_double)]
+
+
 OBSERVE_MAX_PROBES = 16  # CRD_OBSERVE_MAX_PROBES
 
 
@@ -216,6 +231,9 @@ _SIGNATURES = {
     "crd_lsolve_device": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(LsolveOptions), _vp, _vp, _vp, C.POINTER(LsolveStats)]),
     "crd_lsolve_host": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(LsolveOptions), _vp, _vp, _vp, C.POINTER(LsolveStats)]),
     "crd_krylov_probe_dots": (C.c_int, [_vp, _vp, C.c_int, _vp, C.POINTER(C.c_double)]),
+    "crd_imex_defaults": (C.c_int, [C.POINTER(ImexOptions)]),
+    "crd_imex_info": (C.c_int, [_vp, C.POINTER(ImexOptions), C.POINTER(C.c_int64)]),
+    "crd_step_imex": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64, C.POINTER(ImexOptions), C.POINTER(ImexStats)]),
     "crd_set_stepper": (C.c_int, [_vp, C.c_int]),
     "crd_step_rk4": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64]),
     "crd_synchronize": (C.c_int, [_vp]),

@@ -102,6 +102,7 @@ struct crd_recorder;  // crd_recorder.cpp
 namespace crd {
 struct PsolveWorkspace;  // crd_multigrid.cpp
 struct LsolveWorkspace;  // crd_krylov.cpp
+struct ImexWorkspace;    // crd_imex.cpp
 }
 
 struct crd_ctx {
@@ -127,6 +128,7 @@ struct crd_ctx {
 	size_t stage_v_bytes = 0;
 	crd::PsolveWorkspace *psolve = nullptr;  // levels of crd_psolve_*: planes and coefficient tables (lazy, crd_multigrid.cpp)
 	crd::LsolveWorkspace *lsolve = nullptr;  // basis, work vectors and scalars of crd_lsolve_* (lazy, crd_krylov.cpp)
+	crd::ImexWorkspace *imex = nullptr;      // the step's vectors of crd_step_imex (lazy, crd_imex.cpp)
 	void *ghost_lo = nullptr, *ghost_hi = nullptr;   // var0 of rows -1 / nyl for the AoS RHS (multi-slab)
 	void *edge_lo = nullptr, *edge_hi = nullptr;     // var0 of rows 0 / nyl-1 packed from an AoS vector
 	// theta-blocks (d0 > 1): var0 of the columns beside the block (ghost) and of its own first / last column (edge), nyl reals each,
@@ -235,6 +237,7 @@ int resolve_stepper(const crd_ctx *c);  // CRD_STEPPER_STAGED / _FUSED, or -1 wh
 int check_group(crd_ctx *const *ctxs, int n);
 void psolve_release(crd_ctx *c);  // crd_multigrid.cpp: frees the workspace of crd_psolve_* (crd_destroy)
 void lsolve_release(crd_ctx *c);  // crd_krylov.cpp: likewise the workspace of crd_lsolve_*
+void imex_release(crd_ctx *c);    // crd_imex.cpp: likewise the workspace of crd_step_imex
 
 // crd_halo.cpp: fill ghost rows [-depth, 0) and [nyl, nyl + depth) of plane `plane_index` from the ring neighbours, on the comm streams
 int exchange_stage_input(crd_ctx *const *cs, int n, int plane_index, int depth, bool with_v);

@@ -1,0 +1,236 @@
+// crd_imex.cpp -- crd_step_imex (include/crd.h): IMEX additive Runge-Kutta steps with the diffusion part implicit.  This file owns the
+// step's vectors, kept on the context, and the order of launches: f_D (crd_rhs_part_device), the linear solve (crd_lsolve_device) and
+// the stage close (crd_imex.hip) that carries everything else.  The schemes are crd_imex_tables.h's.  Host code only.
+#include <cmath>
+
+#include "crd_ctx.h"
+#include "crd_imex.h"
+#include "crd_imex_tables.h"
+
+namespace crd {
+
+// y_n, R, k_1 .. k_s, FR_0 .. FR_{s-1} and r (the solve's right-hand side, in the slot of FR_s), the last close's partial maxima: one
+// allocation, made by the first crd_step_imex call, made again when a call's scheme has more stages, freed by crd_destroy.
+struct ImexWorkspace {
+	int stages = 0;
+	void *base = nullptr;
+	void *yn = nullptr, *R = nullptr, *k[imex::kMaxStages + 1] = {}, *FR[imex::kMaxStages + 1] = {};
+	double *partials = nullptr;
+};
+
+void imex_release(crd_ctx *c)
+{
+	if (!c || !c->imex) return;
+	if (c->imex->base) (void)hipFree(c->imex->base);
+	delete c->imex;
+	c->imex = nullptr;
+}
+
+}  // namespace crd
+
+using namespace crd;
+
+namespace {
+
+constexpr size_t kAlign = 256;
+size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+size_t vector_bytes(const crd_ctx *c) { return 2 * (size_t)c->nx * (size_t)c->nyl * c->real_size; }
+size_t workspace_bytes(const crd_ctx *c, int stages) { return (2 * (size_t)stages + 3) * aligned(vector_bytes(c)) + aligned(kImexBlocks * sizeof(double)); }
+
+int ensure_workspace(crd_ctx *c, int stages)
+{
+	if (c->imex && c->imex->stages >= stages) return CRD_OK;
+	HIP_TRY(c, hipStreamSynchronize(c->compute));
+	imex_release(c);
+	void *base = nullptr;
+	hipError_t e = hipMalloc(&base, workspace_bytes(c, stages));
+	if (e != hipSuccess) {
+		(void)hipGetLastError();
+		return fail(c, e == hipErrorOutOfMemory ? CRD_ENOMEM : CRD_EHIP, std::string("hipMalloc(imex workspace): ") + hipGetErrorString(e));
+	}
+	ImexWorkspace *w = new ImexWorkspace;
+	w->stages = stages;
+	w->base = base;
+	c->imex = w;
+	char *at = static_cast<char *>(base);
+	const size_t vec = aligned(vector_bytes(c));
+	auto take = [&] {
+		void *p = at;
+		at += vec;
+		return p;
+	};
+	w->yn = take();
+	w->R = take();
+	for (int i = 1; i <= stages; i++) w->k[i] = take();
+	for (int i = 0; i <= stages; i++) w->FR[i] = take();
+	w->partials = reinterpret_cast<double *>(at);
+	return CRD_OK;
+}
+
+// What the call refuses before any device work; *o the options it runs with, *T their scheme.
+int check_call(crd_ctx *c, double t0, double dt, int64_t nsteps, const crd_imex_options *opt, crd_imex_options *o, imex::Tableau *T)
+{
+	if (opt) *o = *opt;
+	else (void)crd_imex_defaults(o);
+	if (!imex::tableau(o->scheme, T)) return fail(c, CRD_EINVAL, "imex: scheme must be CRD_IMEX_EULER, CRD_IMEX_ARS222 or CRD_IMEX_ARS443");
+	if (o->lsolve.part != CRD_PART_DIFFUSION) return fail(c, CRD_EINVAL, "imex: lsolve.part must be CRD_PART_DIFFUSION (the implicit part is the diffusion operator)");
+	if (!(dt > 0.0) || !std::isfinite(dt) || !std::isfinite(t0)) return fail(c, CRD_EINVAL, "imex: dt must be positive and finite, t0 finite");
+	if (nsteps < 0) return fail(c, CRD_EINVAL, "imex: nsteps must not be negative");
+	if (int rc = crd_lsolve_info(c, &o->lsolve, nullptr)) {  // its options, and the contexts it refuses: several slabs, theta-blocks
+		const std::string why = c->err;
+		return fail(c, rc, "imex: " + why);
+	}
+	if (c->recorder) return fail(c, CRD_ESTATE, "imex: a run recorder is open on this context; crd_step_imex takes no samples");
+	return CRD_OK;
+}
+
+struct Stepper {
+	crd_ctx *c;
+	const crd_imex_options &o;
+	const imex::Tableau &T;
+	double dt;
+	crd_imex_stats st{};
+	ImexWorkspace *w = nullptr;
+	bool f32 = false;
+
+	int absorb_at(double t) const { return absorbing(c, t) && !c->desc.just_diffusion ? 1 : 0; }
+
+	// the close of stage i at time t: FR_i and R_{i+1}, or (i = s) Y_s into R
+	int close(int i, double t)
+	{
+		ImexClose a;
+		a.R = i == 0 ? w->yn : w->R;
+		a.k = i == 0 ? nullptr : w->k[i];
+		a.yn = w->yn;
+		a.hg = imex::rounded(dt * T.gamma, f32);
+		a.absorb = absorb_at(t);
+		if (i == T.stages) {
+			a.last = 1;
+			a.out = w->R;
+			a.partials = w->partials;
+			a.max_out = c->scalar_sink();
+		} else {
+			a.FR = w->FR[i];
+			a.Rnext = w->R;
+			imex::Term terms[2 * imex::kMaxStages];
+			const int n = imex::row_terms(T, i + 1, dt, f32, terms);
+			for (int q = 0; q < n; q++) {
+				const imex::Term &m = terms[q];
+				if (m.j < i) {
+					if (a.nterms >= kImexMaxTerms) return fail(c, CRD_EINVAL, "imex: a row with more stored terms than the stage close takes");
+					a.term[a.nterms] = m.explicit_part ? w->FR[m.j] : w->k[m.j];
+					a.coef[a.nterms++] = m.coef;
+				} else if (m.explicit_part) {
+					a.cE = m.coef;
+				} else {
+					a.cI = m.coef;
+				}
+			}
+		}
+		HIP_TRY(c, launch_imex_close(c->p.precision, c->desc, a, c->compute));
+		return CRD_OK;
+	}
+
+	int stopped(int64_t n, int stage, const std::string &why)
+	{
+		st.failed_step = n;
+		st.failed_stage = stage;
+		return fail(c, CRD_ESTATE, "imex: step " + std::to_string(n) + ", stage " + std::to_string(stage) + ": " + why);
+	}
+
+	int step(int64_t n, double t)
+	{
+		if (int rc = close(0, t)) return rc;
+		const double hg = imex::rounded(dt * T.gamma, f32);
+		for (int i = 1; i <= T.stages; i++) {
+			const double ti = t + T.c[i] * dt;
+			void *r = w->FR[T.stages];
+			if (int rc = crd_rhs_part_device(c, ti, CRD_PART_DIFFUSION, w->R, r)) return rc;
+			crd_lsolve_stats ls{};
+			if (int rc = crd_lsolve_device(c, ti, hg, &o.lsolve, nullptr, r, w->k[i], &ls)) return rc;
+			st.solves++;
+			st.iterations += ls.iterations;
+			if (ls.iterations > st.max_iterations) st.max_iterations = ls.iterations;
+			if (ls.r_norm > 0.0 && !(ls.res_norm / ls.r_norm <= st.worst_residual)) st.worst_residual = ls.res_norm / ls.r_norm;
+			if (!ls.converged) return stopped(n, i, "the linear solve did not converge in " + std::to_string(ls.iterations) + " iterations");
+			if (int rc = close(i, ti)) return rc;
+		}
+		double *sink = c->scalar_sink();
+		if (sink != c->scalar_host) HIP_TRY(c, hipMemcpyAsync(c->scalar_host, sink, sizeof(double), hipMemcpyDeviceToHost, c->compute));
+		HIP_TRY(c, hipStreamSynchronize(c->compute));
+		const double m = c->scalar_host[0];
+		if (!std::isfinite(m)) return stopped(n, T.stages, "the new state is not finite");
+		st.max_abs_u = m;
+		std::swap(w->yn, w->R);  // Y_s is y_{n+1}
+		return CRD_OK;
+	}
+
+	int run(double t0, int64_t nsteps)
+	{
+		f32 = c->p.precision != CRD_PRECISION_F64;
+		st.failed_step = -1;
+		st.failed_stage = -1;
+		st.t = t0;
+		if (int rc = set_device(c)) return rc;
+		if (nsteps == 0) return crd_state_max_abs(c, &st.max_abs_u);
+		if (int rc = ensure_workspace(c, T.stages)) return rc;
+		w = c->imex;
+		arkode::drop(c->dense, c->ark);  // stepping on from the state handed back, not from the integrator's internal one
+		c->cycle_pos = -1;
+		HIP_TRY(c, launch_planes_to_aos(c->p.precision, f32 ? 0 : 1, c->planes(crd_ctx::Y), w->yn, c->nx, c->nyl, c->compute));
+		int rc = CRD_OK;
+		for (int64_t n = 0; n < nsteps && rc == CRD_OK; n++) {
+			rc = step(n, t0 + (double)n * dt);
+			if (rc == CRD_OK) st.steps = n + 1;
+		}
+		st.t = t0 + (double)st.steps * dt;
+		// the resident state: that of the last completed step
+		const std::string why = c->err;
+		if (st.steps > 0) {
+			hipError_t e = launch_aos_to_planes(c->p.precision, f32 ? 0 : 1, w->yn, c->planes(crd_ctx::Y), c->nx, c->nyl, c->compute);
+			if (e == hipSuccess) e = hipStreamSynchronize(c->compute);
+			if (e != hipSuccess && rc == CRD_OK) return fail(c, CRD_EHIP, std::string("imex: storing the state: ") + hipGetErrorString(e));
+		}
+		if (rc != CRD_OK) c->err = why;
+		return rc;
+	}
+};
+
+}  // namespace
+
+extern "C" {
+
+int crd_imex_defaults(crd_imex_options *opt)
+{
+	if (!opt) return CRD_EINVAL;
+	opt->scheme = CRD_IMEX_ARS222;
+	opt->reserved = 0;
+	return crd_lsolve_defaults(&opt->lsolve);
+}
+
+int crd_imex_info(crd_ctx *c, const crd_imex_options *opt, int64_t *bytes)
+{
+	if (!c) return fail(nullptr, CRD_EINVAL, "imex: no context");
+	crd_imex_options o;
+	imex::Tableau T;
+	if (int rc = check_call(c, 0.0, 1.0, 0, opt, &o, &T)) return rc;
+	int64_t solve = 0;
+	if (int rc = crd_lsolve_info(c, &o.lsolve, &solve)) return rc;
+	if (bytes) *bytes = (int64_t)workspace_bytes(c, T.stages) + solve;
+	return CRD_OK;
+}
+
+int crd_step_imex(crd_ctx *c, double t0, double dt, int64_t nsteps, const crd_imex_options *opt, crd_imex_stats *stats)
+{
+	if (!c) return fail(nullptr, CRD_EINVAL, "imex: no context");
+	crd_imex_options o;
+	imex::Tableau T;
+	if (int rc = check_call(c, t0, dt, nsteps, opt, &o, &T)) return rc;
+	TraceRange range("crd_step_imex");
+	Stepper s{c, o, T, dt};
+	const int rc = s.run(t0, nsteps);
+	if (stats) *stats = s.st;
+	return rc;
+}
+
+}  // extern "C"

@@ -3,7 +3,8 @@
 // reference programs (src/FHNmodel_torus.cpp:148-497 and siblings); invoked through one of the alias names
 // FHNmodel_torus / FHNmodel_flat / GoldbeterModel_torus / GoldbeterModel_flat it takes exactly one argument, like
 // they do.  Time integration is fixed-step RK4 on the GPU (libcrd) by default; --adaptive runs the reference's integrator,
-// ARKode's default explicit pair and controller restated (CRD_ADAPT_ARKODE), --adaptive-rk43 the RK4(3) pair of earlier rounds.
+// ARKode's default explicit pair and controller restated (CRD_ADAPT_ARKODE), --adaptive-rk43 the RK4(3) pair of earlier rounds,
+// --imex euler|ars222|ars443 IMEX steps with the diffusion part implicit at the run's fixed dt (crd_step_imex; a lone single slab).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -22,7 +23,7 @@
 
 namespace {
 
-void banner(const crd_run_config &cfg, const crd_grid &g, int n_slabs, int64_t nxl0, int64_t nyl0, double s0, double s1, double dt, int64_t steps_per_output)
+void banner(const crd_run_config &cfg, const crd_grid &g, int n_slabs, int64_t nxl0, int64_t nyl0, double s0, double s1, double dt, int64_t steps_per_output, int imex)
 {
 	// Same lines as src/FHNmodel_torus.cpp:249-275 (and the Goldbeter variant, src/GoldbeterModel_torus.cpp:266-303),
 	// with rtol / atol replaced by the fixed step.
@@ -50,6 +51,9 @@ void banner(const crd_run_config &cfg, const crd_grid &g, int n_slabs, int64_t n
 	if (fhn && torus) std::cout << "   Wave inside = " << cfg.wave_inside << "\n";
 	if (cfg.adaptive == 2) std::cout << "   integrator = adaptive RK4(3) on GPU\n   rtol = " << cfg.rtol << "\n   atol = " << cfg.atol << "\n";
 	else if (cfg.adaptive) std::cout << "   integrator = ARKode-style ERK on GPU (Zonneveld 5(3)4, PID controller)\n   rtol = " << cfg.rtol << "\n   atol = " << cfg.atol << "\n";
+	else if (imex >= 0)
+		std::cout << "   integrator = IMEX " << (imex == CRD_IMEX_EULER ? "Euler" : imex == CRD_IMEX_ARS222 ? "ARS(2,2,2)" : "ARS(4,4,3)") << " on GPU (diffusion implicit), dt = " << dt << " ("
+		          << steps_per_output << " steps per output)\n";
 	else std::cout << "   integrator = classical RK4 on GPU, dt = " << dt << " (" << steps_per_output << " steps per output)\n";
 	if (!fhn && p.just_diffusion == 1) {
 		std::cout << "   Diffusion Only\n\n";
@@ -576,10 +580,11 @@ struct LoneTally {
 	long long adaptive_steps = 0, adaptive_rejected = 0;
 	double stepping_s = 0.0;
 	long long steps_taken = 0;
+	long long imex_solves = 0, imex_iterations = 0;  // --imex: linear solves and their GMRES iterations
 };
 
 // Step all contexts over output interval iout and wait for them.  Returns the library's status.
-int step_interval(const crd_run_config &cfg, const Cadence &c, int iout, LoneRun *run, LoneTally *tally)
+int step_interval(const Options &o, const crd_run_config &cfg, const Cadence &c, int iout, LoneRun *run, LoneTally *tally)
 {
 	const double t = iout * c.dTout;
 	const auto step_t0 = std::chrono::steady_clock::now();
@@ -592,6 +597,15 @@ int step_interval(const crd_run_config &cfg, const Cadence &c, int iout, LoneRun
 		tally->adaptive_steps += as.accepted;
 		tally->adaptive_rejected += as.rejected;
 		tally->steps_taken += as.accepted + as.rejected;
+	} else if (o.imex >= 0) {
+		crd_imex_options io;
+		crd_imex_defaults(&io);
+		io.scheme = o.imex;
+		crd_imex_stats is{};
+		rc = crd_step_imex(run->ctx[0], t, c.dt, c.steps_per_output, &io, &is);
+		tally->steps_taken += is.steps;
+		tally->imex_solves += is.solves;
+		tally->imex_iterations += is.iterations;
 	} else {
 		rc = crd_group_step_rk4(run->ctx.data(), run->G, t, c.dt, c.steps_per_output);
 		tally->steps_taken += c.steps_per_output;
@@ -663,10 +677,10 @@ void progress_line(const Options &o, int iout, int Nt, Progress *p)
 bool output_interval(const Options &o, const crd_run_config &cfg, const crd_grid &g, const Cadence &c, int iout, LoneRun *run, LoneTally *tally, Progress *progress, int *status)
 {
 	bool blown = false;
-	int rc = step_interval(cfg, c, iout, run, tally);
+	int rc = step_interval(o, cfg, c, iout, run, tally);
 	rc = download_interval(o, iout, rc, run, &blown);
 	if (rc != CRD_OK || blown) {
-		if (rc != CRD_OK) die("crd_group_step_rk4", rc, run->ctx[0]);
+		if (rc != CRD_OK) die(o.imex >= 0 ? "crd_step_imex" : "crd_group_step_rk4", rc, run->ctx[0]);
 		std::cerr << "Solver failure, stopping integration\n";  // src/FHNmodel_torus.cpp:433
 		*status = 1;
 		return false;
@@ -709,7 +723,12 @@ void rate_summary(const Options &o, const crd_run_config &cfg, const crd_grid &g
 	const long long steps_taken = tally.steps_taken;
 	const double stepping_s = tally.stepping_s;
 	if (cfg.adaptive) std::cout << "\n   steps = " << tally.adaptive_steps << " (+" << tally.adaptive_rejected << " rejected)";
-	if (steps_taken > 0 && stepping_s > 0.0) {
+	if (o.imex >= 0 && steps_taken > 0 && stepping_s > 0.0) {
+		char line[256];
+		std::snprintf(line, sizeof line, "\n   rate: %lld IMEX steps in %.6f s of stepping = %.1f steps/s; %lld linear solves, %lld GMRES iterations", steps_taken, stepping_s,
+		              (double)steps_taken / stepping_s, tally.imex_solves, tally.imex_iterations);
+		std::cout << line;
+	} else if (steps_taken > 0 && stepping_s > 0.0) {
 		// compulsory-byte model of a step: both fields read once and written once (the one-launch stepper's traffic; the four
 		// stage kernels move 8 x that)
 		crd_launch_plan lp{};
@@ -722,6 +741,16 @@ void rate_summary(const Options &o, const crd_run_config &cfg, const crd_grid &g
 		std::cout << line;
 	}
 	std::cout << "\n   ----------------------\n";
+}
+
+// What --imex cannot be combined with in the ini, and the fixed step it needs: refused before any device is touched.
+void check_imex_config(const Options &o, const crd_run_config &cfg)
+{
+	if (o.imex < 0) return;
+	if (cfg.n_gpus > 1) usage_error("--imex steps a lone single-slab run: the ini asks for [Solver] gpus = " + std::to_string(cfg.n_gpus) + " (pass --gpus 1)");
+	if (cfg.adaptive) usage_error("--imex steps at the run's fixed dt: the ini asks for [Solver] adaptive = " + std::to_string(cfg.adaptive) + " (pass --fixed)");
+	if (!(cfg.dt > 0))
+		usage_error("--imex needs the run's fixed step: give --dt DT or a positive [Solver] dt (dt = 0 asks for dtSafety x the stable step of RK4, which is what an IMEX run is there to exceed)");
 }
 
 // A lone run, or its phi-slabs (or theta x phi blocks) stepped together in this process.
@@ -754,9 +783,9 @@ int run_lone(const Options &o, const crd_run_config &cfg)
 		if (run.recut) crd_block_extents(g.nx, g.ny, f / run.fd1, run.fd0, f % run.fd1, run.fd1, &b.is, &b.ie, &b.js, &b.je);
 		else b = run.crect[(size_t)f];
 	}
-	if (!o.quiet) banner(cfg, g, run.F, run.frect[0].ie - run.frect[0].is + 1, run.frect[0].je - run.frect[0].js + 1, s0, s1, c.dt, c.steps_per_output);
+	if (!o.quiet) banner(cfg, g, run.F, run.frect[0].ie - run.frect[0].is + 1, run.frect[0].je - run.frect[0].js + 1, s0, s1, c.dt, c.steps_per_output, o.imex);
 	if (open_files(o, cfg, g, &run) || upload(o, cfg, g, &run)) return 1;
-	if (!cfg.adaptive && plan_launches(o, &run)) return 1;
+	if (!cfg.adaptive && o.imex < 0 && plan_launches(o, &run)) return 1;
 	if (o.observe) {
 		// fixed steps: every stride-th step of the run; error-controlled: one sample per output
 		const ObserveRequest r = observe_request(o, c, cfg.adaptive != 0);
@@ -849,5 +878,6 @@ int main(int argc, char *argv[])
 
 	crd_run_config cfg;
 	if (load_config(&o, launcher, &cfg)) return 1;
+	check_imex_config(o, cfg);
 	return o.ensemble.empty() ? run_lone(o, cfg) : run_ensemble(o, cfg);
 }

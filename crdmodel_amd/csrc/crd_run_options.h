@@ -45,6 +45,9 @@ struct Options {
 	std::vector<std::pair<int, long long>> sections;  // (CRD_SECTION_*, index)
 	bool observe_cycles = false;
 	double cycle_threshold = 0.0;
+	// --imex euler|ars222|ars443: a lone single-slab run stepped by crd_step_imex (CRD_IMEX_*) at the run's fixed dt; -1: not given.
+	// (Not in the usage text, whose bytes the recorded refusals of tests/golden/driver_refusals.json pin: README.md and INTEGRATION.md name it.)
+	int imex = -1;
 };
 
 [[noreturn]] inline void usage(const char *argv0, bool alias)
@@ -239,6 +242,18 @@ inline void check_ensemble_options(const Options &o)
 		}
 }
 
+// What --imex cannot be combined with on the command line, looked at after everything above: a command line without --imex is refused as
+// ever.  What the ini adds is check_imex_config's (crd_run.cpp).
+inline void check_imex_options(const Options &o)
+{
+	if (o.imex < 0) return;
+	if (!o.ensemble.empty()) usage_error("--imex steps a lone single-slab run: not with --ensemble");
+	if (o.gpus > 1) usage_error("--imex steps a lone single-slab run: not with --gpus " + std::to_string(o.gpus));
+	if (o.d0 > 0 || o.decomp_mpi || o.block_contexts) usage_error("--imex steps a lone single-slab run: not with --decomp / --block-contexts");
+	if (o.observe) usage_error("--imex takes no recorder samples: not with --observe");
+	if (o.adaptive == 1 || o.adaptive == 2) usage_error("--imex steps at the run's fixed dt: not with --adaptive / --adaptive-rk43");
+}
+
 // The command line of an invocation as crd_run (an alias takes the ini alone: main).  --gpus, --devices and --dt take whatever atoi /
 // atof make of their value.
 inline void parse_options(int argc, char *argv[], Options *out)
@@ -294,6 +309,10 @@ inline void parse_options(int argc, char *argv[], Options *out)
 			const std::string v = next();
 			o.observe_cycles = true;
 			o.cycle_threshold = finite_number(v, "--observe-cycles takes a threshold, a number (got '" + v + "')");
+		} else if (s == "--imex") {
+			const std::string v = next();
+			o.imex = v == "euler" ? CRD_IMEX_EULER : v == "ars222" ? CRD_IMEX_ARS222 : v == "ars443" ? CRD_IMEX_ARS443 : -1;
+			if (o.imex < 0) usage_error("--imex takes euler, ars222 or ars443 (got '" + v + "')");
 		} else if (s == "--decomp") {
 			const std::string v = next();
 			if (v == "mpi") o.decomp_mpi = true;
@@ -310,6 +329,7 @@ inline void parse_options(int argc, char *argv[], Options *out)
 	}
 	if (o.model < 0 || o.surface < 0 || o.ini.empty() || o.precision == -2 || o.stepper == -2) usage(argv[0], false);
 	check_ensemble_options(o);
+	check_imex_options(o);
 }
 
 // --probe I,J and --section row:J | column:I against the grid they are recorded on; `of` names the member (" of member k") where the

@@ -342,6 +342,31 @@ class Slab:
         if sync:
             self.synchronize()
 
+    def _imex_options(self, scheme, lsolve_options):
+        opt = capi.ImexOptions()
+        opt.scheme = capi.IMEX_SCHEMES[scheme] if isinstance(scheme, str) else scheme
+        opt.lsolve = self._lsolve_options(**lsolve_options)
+        return opt
+
+    def step_imex(self, t0, dt, nsteps, scheme="ars222", **lsolve_options):
+        """nsteps IMEX steps of size dt on the resident state, the diffusion part implicit (crd_step_imex): scheme "euler", "ars222" or
+        "ars443" (or a CRD_IMEX_* value); lsolve_options are Slab.lsolve's and reach every stage's solve.  Returns the crd_imex_stats
+        structure: steps, t, solves, iterations, max_iterations, failed_step, failed_stage, worst_residual, max_abs_u.  A solve that
+        does not converge raises CrdError (CRD_ESTATE) with that structure as its `stats`; the state is the last completed step's."""
+        opt, st = self._imex_options(scheme, lsolve_options), capi.ImexStats()
+        rc = lib().crd_step_imex(self._h, t0, dt, nsteps, C.byref(opt), C.byref(st))
+        if rc != capi.OK:
+            err = CrdError(rc, "crd_step_imex", lib().crd_last_error(self._h).decode())
+            err.stats = st
+            raise err
+        return st
+
+    def imex_info(self, scheme="ars222", **lsolve_options):
+        """Device bytes crd_step_imex with these options keeps on the context, the solve's workspace included (crd_imex_info)."""
+        opt, nbytes = self._imex_options(scheme, lsolve_options), C.c_int64()
+        self._check(lib().crd_imex_info(self._h, C.byref(opt), C.byref(nbytes)), "crd_imex_info")
+        return nbytes.value
+
     def step_rk4_timed(self, t0, dt, nsteps):
         ms, kms, lps = C.c_double(), C.c_double(), C.c_int()
         self._check(lib().crd_step_rk4_timed(self._h, t0, dt, nsteps, C.byref(ms), C.byref(kms), C.byref(lps)), "crd_step_rk4_timed")

@@ -402,6 +402,52 @@ int crd_krylov_probe_dots(crd_ctx *ctx, const void *vectors, int count, const vo
 int crd_set_stepper(crd_ctx *ctx, int stepper);
 int crd_step_rk4(crd_ctx *ctx, double t0, double dt, int64_t nsteps);
 
+/* IMEX stepping: nsteps steps of size dt of an additive Runge-Kutta scheme on the context's resident state, the diffusion part f_D
+ * implicit and the kinetics f_R explicit, so that dt is not bound by crd_stable_dt's diffusion limit (the kinetics' own explicit
+ * limit remains).  Step n starts at t_n = t0 + n dt, as crd_step_rk4 forms it.  Three built-in schemes of the Ascher-Ruuth-Spiteri
+ * type -- stage 0 is Y_0 = y_n, the implicit matrix has a zero first column and ONE diagonal value gamma, y_{n+1} is the last stage,
+ * c is shared:
+ *   CRD_IMEX_EULER   s = 1, order 1: A^E = [1], A^I = [1]
+ *   CRD_IMEX_ARS222  s = 2, order 2: gamma = 1 - 1/sqrt(2), delta = 1 - 1/(2 gamma), c = (0, gamma, 1),
+ *                    A^E rows (gamma), (delta, 1 - delta); A^I rows (gamma), (1 - gamma, gamma)
+ *   CRD_IMEX_ARS443  s = 4, order 3: gamma = 1/2, c = (0, 1/2, 2/3, 1/2, 1),
+ *                    A^E rows (1/2), (11/18, 1/18), (5/6, -5/6, 1/2), (1/4, 7/4, 3/4, -7/4)
+ *                    A^I rows (1/2), (1/6, 1/2), (-1/2, 1/2, 1/2), (3/2, -3/2, 1/2, 1/2)
+ * (A^E columns 0 .. i - 1, A^I columns 1 .. i of stage i = 1 .. s).  f_D is linear, so no Newton iteration: with hE_ij = dt A^E_ij,
+ * hI_ij = dt A^I_ij and dt gamma formed in double and rounded to the context's precision, one step is
+ *   FR_0 = f_R(t_n, y_n);  R_1 = fma(hE_10, FR_0, y_n);  and for i = 1 .. s at t_i = t_n + c_i dt:
+ *     r = f_D(t_i, R_i)                      crd_rhs_part_device(CRD_PART_DIFFUSION)
+ *     k_i = (I - dt gamma J_D(t_i))^-1 r     crd_lsolve_device with `lsolve`, from z = 0: k_i = f_D(Y_i)
+ *     Y_i = fma(dt gamma, k_i, R_i);  FR_i = f_R(t_i, Y_i), the bits of crd_rhs_part_*(CRD_PART_REACTION) on Y_i;
+ *     R_{i+1} = y_n, then for j = 0 .. i ascending fma(hE_{i+1,j}, FR_j, .) and fma(hI_{i+1,j}, k_j, .), terms whose coefficient
+ *     is exactly zero skipped -- one kernel, one pass (crd_imex.hip); at i = s it stores Y_s, the new state, and nothing else.
+ * The operator and the held rows are those of each stage's own time (zero rows while t_i < tBoundary), as in crd_rhs_part_* and
+ * crd_lsolve_*.  The call WAITS for its work, as crd_lsolve_* does.
+ * A solve that does not converge within lsolve.max_iters, or a state whose max |var0| is not finite, ends the call with CRD_ESTATE:
+ * the resident state is that of the last completed step and stats says where it stopped.
+ * Refused before any device work -- CRD_EINVAL: an unknown scheme; lsolve.part other than CRD_PART_DIFFUSION; dt not positive or not
+ * finite; t0 not finite; nsteps < 0; lsolve options crd_lsolve_* refuses.  CRD_ESTATE: a context that is one of several slabs,
+ * theta-block contexts, and a context with a run recorder open on it.  opt == NULL: crd_imex_defaults.
+ * Workspace: y_n, R, s vectors k_j and s + 1 vectors FR_j (the last one holds r) besides crd_lsolve_*'s own, allocated by the first
+ * call, kept on the context, freed by crd_destroy; crd_imex_info reports the bytes of both together.
+ * stats (may be NULL): steps completed; t = t0 + steps dt; solves and GMRES iterations in total; max_iterations of one solve;
+ * failed_step / failed_stage (-1: none); worst_residual = the largest res_norm / r_norm of a solve; max_abs_u = max |var0| of the
+ * final state (what crd_state_max_abs reports). */
+enum { CRD_IMEX_EULER = 0, CRD_IMEX_ARS222 = 1, CRD_IMEX_ARS443 = 2 };
+typedef struct crd_imex_options {
+	int32_t scheme;    /* CRD_IMEX_*; default CRD_IMEX_ARS222 */
+	int32_t reserved;
+	crd_lsolve_options lsolve;  /* crd_lsolve_defaults; part must be CRD_PART_DIFFUSION */
+} crd_imex_options;
+typedef struct crd_imex_stats {
+	int64_t steps, solves, iterations, failed_step;
+	int32_t max_iterations, failed_stage;
+	double t, worst_residual, max_abs_u;
+} crd_imex_stats;
+int crd_imex_defaults(crd_imex_options *opt);
+int crd_imex_info(crd_ctx *ctx, const crd_imex_options *opt, int64_t *workspace_bytes);
+int crd_step_imex(crd_ctx *ctx, double t0, double dt, int64_t nsteps, const crd_imex_options *opt, crd_imex_stats *stats);
+
 /* The exchange period E of the one-launch stepper on several slabs: E steps between two halo exchanges, each of 4 E ghost rows
  * of both fields; in between every slab recomputes the shrinking ghost region redundantly (same kernel, same inputs: bit-identical
  * to what the owner computes).  3 <= E <= 16; default 10 where every slab of the run has 256 rows or more, else 8.  A property of the RUN: every context of a LOCAL group / every rank of a
