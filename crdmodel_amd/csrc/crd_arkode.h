@@ -1,6 +1,6 @@
 // crd_arkode.h -- ARKode's step-size controller (CRD_ADAPT_ARKODE) and its per-step bookkeeping, restated from its documentation;
 // oracle/arkode_erk.py has the same rules with the same names, and the tests compare the two attempt by attempt.  Host code only,
-// shared by the single-context integrator (crd_steppers.cpp: integrate_adaptive_impl) and the ensemble's (crd_ensemble.cpp), so that
+// shared by the single-context integrator (crd_adaptive.cpp: AdaptiveRun) and the ensemble's (crd_ensemble.cpp), so that
 // both take the same decisions from the same norms -- and, at the end, what both keep around the controller: the dense-output record,
 // the rotation of the state planes and their relabelling when a call ends.  Not part of the ABI.
 #pragma once

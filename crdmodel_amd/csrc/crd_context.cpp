@@ -1,6 +1,6 @@
 // crd_context.cpp -- the device context behind the C ABI: lifecycle, communicator wiring, state transfer and the f() entry
 // points.  Host code only (compiled by hipcc for the HIP runtime API); kernels live in crd_kernels.hip / crd_fused.hip, the
-// halo transports in crd_halo.cpp, the steppers in crd_steppers.cpp.
+// halo transports in crd_halo.cpp, the steppers in crd_steppers.cpp, the error-controlled integrator in crd_adaptive.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -757,7 +757,7 @@ int crd_get_launch_geometry(crd_ctx *c, crd_launch_geometry *out)
 	crd::step::stage_flags(c->last_step_t, c->last_step_dt > 0.0 ? c->last_step_dt : 0.0, c->p.t_boundary, 4, call.absorb);
 	call.absorb[4] = call.absorb[3];
 	call.steps = c->plan.tuned ? fused_steps_supported(c->p.precision, c->desc, c->plan.steps) : 1;
-	// (fp32 triples any stage of which has the absorbing rows on are stepped as a pair and a single step: run_steps, triple_absorbs)
+	// (fp32 triples any stage of which has the absorbing rows on are stepped as a pair and a single step: crd_schedule.h, launch_steps)
 	if (call.steps == 3 && c->p.precision != CRD_PRECISION_F64 && (call.absorb[0] || call.absorb[1] || call.absorb[2] || call.absorb[3])) call.steps = 2;
 	call.plan = &c->plan;
 	call.geometry = &g;

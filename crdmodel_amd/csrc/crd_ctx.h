@@ -1,7 +1,8 @@
 // crd_ctx.h -- the device context behind the C ABI and the helpers its translation units share (not part of the ABI):
 //   crd_context.cpp   lifecycle, communicator wiring, state transfer, the f() entry points
 //   crd_halo.cpp      RCCL binding and the halo transports
-//   crd_steppers.cpp  fixed-step RK4 drivers (staged / fused, single slab / deep-halo multi-slab) and the adaptive integrator
+//   crd_steppers.cpp  fixed-step RK4 drivers (staged / fused, single slab / deep-halo multi-slab; the launch schedule: crd_schedule.h)
+//   crd_adaptive.cpp  the error-controlled integrator
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -248,8 +249,11 @@ int prime_halo(crd_ctx *const *cs, int n, int plane_index, int depth, bool with_
 
 // crd_steppers.cpp
 FusedCall make_fused_call(const crd_ctx *c, double t, double dt, int src, int dst);
-int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, int *timed_launches, crd_recorder *rec = nullptr);
+int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, int *timed_launches, crd_recorder *rec);
 void decide_cycle_start(crd_ctx *const *all, int n_all);  // call once per stepping call, before run_steps (and before any issuing thread starts)
+// ... the ring's vote (RCCL runs), which crd_adaptive.cpp takes on whether to resume: enqueue the reduction, wait for it
+int begin_cycle_agreement(crd_ctx *c, int mine);
+int finish_cycle_agreement(crd_ctx *c, int *agreed);
 
 // crd_recorder.cpp: what the stepping calls ask of a run recorder
 int recorder_of_call(crd_ctx *const *cs, int n, crd_recorder **out);  // the recorder of the call's contexts (or null); CRD_ESTATE unless the call covers its whole group

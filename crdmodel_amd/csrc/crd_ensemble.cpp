@@ -834,7 +834,7 @@ int ensure_adaptive(crd_ensemble *e)
 	return CRD_OK;
 }
 
-// What one member does during one call (crd_steppers.cpp: what integrate_adaptive_impl keeps in locals).
+// What one member does during one call (crd_adaptive.cpp: what AdaptiveRun keeps for a context's call).
 struct MemberRun {
 	crd_adaptive_stats st{};
 	double t = 0.0, t_prev = 0.0, h_cap = 0.0, t_boundary = 0.0;

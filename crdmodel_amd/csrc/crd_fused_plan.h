@@ -48,7 +48,7 @@ struct StepSite {
 // measured nothing on a rank's share and keeps pairs there --, else two where the two-step kernels do, else one.
 // (The fp64 block strip addresses its rows by 32-bit offsets into the plane, kScalarRows: beyond that span, pairs.  fp32: the three-step
 // pipeline with the absorbing-row selects does not fit the registers -- 256 and scratch; the steppers step such triples as a pair and a
-// single step, run_steps: triple_absorbs.)
+// single step, crd_schedule.h: launch_steps.)
 inline int steps_per_launch(const KernelTraits &k, const StepSite &s, int want)
 {
 	if (s.embed) return 1;  // (several steps per launch: plain steps only)

@@ -2,7 +2,7 @@
 // the absorbing-row flags.  Host code only and no HIP include, shared by every stepper of contexts and of ensembles (.cpp and .hip units
 // alike): a member of an ensemble goes through a lone context's arithmetic bit by bit, and on the host that is these expressions and
 // no others.  The step's own time is the caller's (t0 + s dt, (t + dt) + ..., ((t + dt) + dt) + ...): those forms differ by roundings
-// the steppers rely on (crd_steppers.cpp: pair_is_exact).  Not part of the ABI.
+// the steppers rely on (crd_schedule.h: pair_is_exact).  Not part of the ABI.
 #pragma once
 
 namespace crd {

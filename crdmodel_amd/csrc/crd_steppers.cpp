@@ -1,5 +1,6 @@
 // crd_steppers.cpp -- the time-stepping drivers behind the C ABI: classical RK4 with the staged or the fused kernels on one
-// slab or on the slabs of a run (deep-halo exchange cycles), and the error-controlled RK4(3) integrator.  Host code only.
+// slab or on the slabs of a run (deep-halo exchange cycles), the setters and the timed entry points.  Which launch comes next is
+// crd_schedule.h's; the error-controlled integrator is crd_adaptive.cpp.  Host code only.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -7,6 +8,7 @@
 #include <thread>
 
 #include "crd_ctx.h"
+#include "crd_schedule.h"
 
 namespace crd {
 
@@ -114,7 +116,7 @@ int staged_step_blocks(crd_ctx *const *cs, int n, double t, double dt)
 	return CRD_OK;
 }
 
-// Fused stepper on several slabs: ONE exchange every E = exchange_every steps (crd_set_exchange_period; default kDefaultExchangeEvery = 8, kTallSlabExchangeEvery = 10 where every slab has 256 rows or more), G = 4 E ghost
+// Fused stepper on several slabs: ONE exchange every E = exchange_every steps (crd_set_exchange_period; by default 8, 10 where every slab has 256 rows or more: crd_create), G = 4 E ghost
 // rows of both fields.  Step q of a cycle (q = 0 right after an exchange) produces rows [-e, nyl + e) with e = 4 (E-1-q): the
 // still-valid part of the ghost region is recomputed redundantly (same kernel, same inputs, so bit-identical to what the owning
 // slab computes) instead of being communicated.  The last step of a cycle (e = 0) is split
@@ -148,116 +150,121 @@ int wait_for_halo(crd_ctx *c)
 	return CRD_OK;
 }
 
-// One launch of the cycle on every context of the call: `nsub` steps (1, or 2 with a two-steps-per-launch plan: the pair must not
-// straddle an exchange, q + nsub <= E) from cycle position q.  H = 4 nsub rows are consumed beyond the rows produced.
-int fused_launch_multi(crd_ctx *const *cs, int n, double t, double dt, int src, int dst, int q, int nsub, bool timed_step, bool last_launch_of_call, int max_nsub = 2)
-{
-	const int E = cycle_steps(cs[0]), G = cycle_ghost(cs[0]), B = cycle_band(cs[0]);
-	const int H = kStepHalo * nsub;
-	const int ext = kStepHalo * (E - q - nsub);  // ghost rows still valid once this launch has run
-	auto call_of = [&](crd_ctx *c, double tt, int from, int to, int steps) {
+// One launch of the cycle on every context of the call: `nsub` steps (1, or 2 / 3 with a plan of several steps per launch: the launch
+// must not straddle an exchange, q + nsub <= E) from cycle position q.  What the launch's three cases share:
+struct CycleLaunch {
+	double t, dt;
+	int src, dst, q, nsub, max_nsub;
+	bool timed_step, last_launch_of_call;
+	int E, G, B;
+	int H() const { return kStepHalo * nsub; }              // rows consumed beyond the rows produced
+	int ext() const { return kStepHalo * (E - q - nsub); }  // ghost rows still valid once this launch has run
+	FusedCall call(const crd_ctx *c, double tt, int from, int to, int steps) const
+	{
 		FusedCall call = make_fused_call(c, tt, dt, from, to);
 		call.steps = steps;
 		return call;
-	};
-	if (q + nsub < E) {
-		for (int k = 0; k < n; k++) {
-			crd_ctx *c = cs[k];
-			if (int rc = set_device(c)) return rc;
-			const FusedCall call = call_of(c, t, src, dst, nsub);
-			const bool timed = timed_step && !c->ev_k.empty();
-			if (c->ghost_deferred) {
-				// Halo slack 2 (crd_set_halo_slack): the exchange gets a THIRD sweep to land under.  The cycle's first launch has only
-				// produced its rows that read owned rows; this one does the same -- rows [B, nyl - B) only, B = the band the
-				// exchange sends from / the neighbours pull from, which nobody may overwrite before the exchange is through -- and
-				// only then the compute stream waits, finishes the first launch (the rows that read ghost rows) and this one (its edges).
-				const int n0 = c->deferred_nsub, H0 = kStepHalo * n0, ext0 = kStepHalo * (E - n0);
-				const FusedCall call0 = call_of(c, c->deferred_t, dst, src, n0);  // the first launch read this launch's output plane and wrote its input plane
-				HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, B, c->nyl - B, 0, 0, c->compute));
-				if (int rc = wait_for_halo(c)) return rc;
-				HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call0, -ext0, H0, c->nyl - H0, c->nyl + ext0, c->compute));
-				HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -ext, B, c->nyl - B, c->nyl + ext, c->compute));
-				c->ghost_deferred = false;
-				continue;
-			}
-			if (q > 0) {
-				// (nothing to record: the next launch runs on the same stream)
-				if (timed) HIP_TRY(c, hipEventRecord(c->ev_k[0], c->compute));
-				HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -ext, c->nyl + ext, 0, 0, c->compute));
-				if (timed) HIP_TRY(c, hipEventRecord(c->ev_k[1], c->compute));
-				if (timed) c->timed_rows = c->nyl + 2 * ext;  // what crd_dominant_kernel_rows reports for this launch
-				if (timed) c->timed_steps = nsub;
-				continue;
-			}
-			// First launch after an exchange.  Output rows [H, nyl - H) read owned rows only, so they are launched straight behind
-			// the interior sweep of the previous launch: the exchange gets this sweep as extra time to land.
-			const bool split = c->nyl >= 4 * B;
-			if (split) HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, H, c->nyl - H, 0, 0, c->compute));
-			if (split && c->halo_slack >= 2 && !last_launch_of_call && q + nsub + max_nsub < E) {  // (whatever the next launch takes -- up to max_nsub steps --, it is not the cycle's last)
-				c->ghost_deferred = true;  // the wait and the rows that read ghost rows follow behind the NEXT launch's owned-only rows
-				c->deferred_t = t;
-				c->deferred_nsub = nsub;
-				continue;
-			}
-			if (int rc = wait_for_halo(c)) return rc;
-			// the rows that read ghost rows: [-ext, H) and [nyl - H, nyl + ext) in one launch
-			if (split) HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -ext, H, c->nyl - H, c->nyl + ext, c->compute));
-			else HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -ext, c->nyl + ext, 0, 0, c->compute));
-		}
+	}
+	FusedCall call(const crd_ctx *c) const { return call(c, t, src, dst, nsub); }
+};
+
+// Middle of the cycle: one full-height sweep (nothing to record: the next launch runs on the same stream).
+int cycle_middle(crd_ctx *c, const CycleLaunch &L)
+{
+	const FusedCall call = L.call(c);
+	const bool timed = L.timed_step && !c->ev_k.empty();
+	if (timed) HIP_TRY(c, hipEventRecord(c->ev_k[0], c->compute));
+	HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -L.ext(), c->nyl + L.ext(), 0, 0, c->compute));
+	if (timed) HIP_TRY(c, hipEventRecord(c->ev_k[1], c->compute));
+	if (timed) c->timed_rows = c->nyl + 2 * L.ext();  // what crd_dominant_kernel_rows reports for this launch
+	if (timed) c->timed_steps = L.nsub;
+	return CRD_OK;
+}
+
+// First launch after an exchange.  Output rows [H, nyl - H) read owned rows only, so they are launched straight behind the interior
+// sweep of the previous launch: the exchange gets this sweep as extra time to land.
+int cycle_first(crd_ctx *c, const CycleLaunch &L)
+{
+	const FusedCall call = L.call(c);
+	const int H = L.H(), ext = L.ext();
+	const bool split = c->nyl >= 4 * L.B;
+	if (split) HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, H, c->nyl - H, 0, 0, c->compute));
+	if (split && c->halo_slack >= 2 && !L.last_launch_of_call && L.q + L.nsub + L.max_nsub < L.E) {  // (whatever the next launch takes -- up to max_nsub steps --, it is not the cycle's last)
+		c->ghost_deferred = true;  // the wait and the rows that read ghost rows follow behind the NEXT launch's owned-only rows
+		c->deferred_t = L.t;
+		c->deferred_nsub = L.nsub;
 		return CRD_OK;
 	}
-	// last launch of the cycle: edge bands, exchange released behind them, interior under the exchange
+	if (int rc = wait_for_halo(c)) return rc;
+	// the rows that read ghost rows: [-ext, H) and [nyl - H, nyl + ext) in one launch
+	if (split) HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -ext, H, c->nyl - H, c->nyl + ext, c->compute));
+	else HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -ext, c->nyl + ext, 0, 0, c->compute));
+	return CRD_OK;
+}
+
+// ... its deferred form.  Halo slack 2 (crd_set_halo_slack): the exchange gets a THIRD sweep to land under.  The cycle's first launch
+// has only produced its rows that read owned rows; this one does the same -- rows [B, nyl - B) only, B = the band the exchange sends
+// from / the neighbours pull from, which nobody may overwrite before the exchange is through -- and only then the compute stream
+// waits, finishes the first launch (the rows that read ghost rows) and this one (its edges).
+int cycle_first_deferred(crd_ctx *c, const CycleLaunch &L)
+{
+	const FusedCall call = L.call(c);
+	const int B = L.B, ext = L.ext(), n0 = c->deferred_nsub, H0 = kStepHalo * n0, ext0 = kStepHalo * (L.E - n0);
+	const FusedCall call0 = L.call(c, c->deferred_t, L.dst, L.src, n0);  // the first launch read this launch's output plane and wrote its input plane
+	HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, B, c->nyl - B, 0, 0, c->compute));
+	if (int rc = wait_for_halo(c)) return rc;
+	HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call0, -ext0, H0, c->nyl - H0, c->nyl + ext0, c->compute));
+	HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -ext, B, c->nyl - B, c->nyl + ext, c->compute));
+	c->ghost_deferred = false;
+	return CRD_OK;
+}
+
+// Last launch of the cycle: edge bands, exchange released behind them, interior under the exchange.
+int cycle_last(crd_ctx *const *cs, int n, const CycleLaunch &L)
+{
+	const int B = L.B;
 	for (int k = 0; k < n; k++) {
 		crd_ctx *c = cs[k];
 		if (int rc = set_device(c)) return rc;
-		FusedCall call = call_of(c, t, src, dst, nsub);
+		FusedCall call = L.call(c);
 		call.done_event = c->ev_edges;  // (set by the launch's own completion: no record, no bubble in front of the interior launch)
 		if (c->nyl >= 4 * B) HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, 0, B, c->nyl - B, c->nyl, c->compute));
 		else HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, 0, c->nyl, 0, 0, c->compute));
 	}
-	if (int rc = exchange_stage_input(cs, n, dst, G, true)) return rc;
+	if (int rc = exchange_stage_input(cs, n, L.dst, L.G, true)) return rc;
 	for (int k = 0; k < n; k++) {
 		crd_ctx *c = cs[k];
 		if (int rc = set_device(c)) return rc;
-		if (c->nyl >= 4 * B) {
-			const FusedCall call = call_of(c, t, src, dst, nsub);
-			HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, B, c->nyl - B, 0, 0, c->compute));
-		}
+		if (c->nyl >= 4 * B) HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, L.call(c), B, c->nyl - B, 0, 0, c->compute));
 	}
 	return CRD_OK;
 }
 
-// May steps s and s + 1 of a call go out as ONE two-step launch?  The kernel takes the second step's absorbing-row flags from
-// t + dt (make_fused_call); the stepping loops form that step's time as t0 + (s + 1) dt, which may differ by a rounding -- which
-// matters only where a stage time lands within an ulp of tBoundary.  Such a pair is stepped singly, so that paired and unpaired
-// stepping take the same decisions.
-bool same_flags(const crd_ctx *c, double ta, double tb, double dt)  // do steps of size dt at ta and at tb take the same absorbing decisions?
+int fused_launch_multi(crd_ctx *const *cs, int n, const CycleLaunch &L)
 {
-	int fa[4], fb[4];
-	step::stage_flags(ta, dt, c->p.t_boundary, 4, fa);
-	step::stage_flags(tb, dt, c->p.t_boundary, 4, fb);
-	return std::equal(fa, fa + 4, fb);
+	if (L.q + L.nsub >= L.E) return cycle_last(cs, n, L);
+	for (int k = 0; k < n; k++) {
+		crd_ctx *c = cs[k];
+		if (int rc = set_device(c)) return rc;
+		if (int rc = c->ghost_deferred ? cycle_first_deferred(c, L) : L.q > 0 ? cycle_middle(c, L) : cycle_first(c, L)) return rc;
+	}
+	return CRD_OK;
 }
-bool pair_is_exact(const crd_ctx *c, double t0, int64_t s, double dt)
+
+// Step of an exchange cycle whose single full-slab launch is the one timed in a multi-slab fused run (step 0 is split in two).
+constexpr int kTimedCycleStep = 1;
+
+int ensure_timing_events(crd_ctx *c)
 {
-	const double t = t0 + (double)s * dt;
-	return same_flags(c, t0 + (double)(s + 1) * dt, t + dt, dt);
+	while ((int)c->ev_k.size() < 2 * step::kMaxTimedLaunches) {
+		hipEvent_t e;
+		HIP_TRY(c, hipEventCreate(&e));
+		c->ev_k.push_back(e);
+	}
+	return CRD_OK;
 }
-// Does any stage of the three steps from t on have the absorbing rows on?  (The fp32 three-step kernel has no instantiation with the
-// selects -- it would not fit the registers: 256 + scratch --; such triples are stepped as a pair and a single step.)
-bool triple_absorbs(const crd_ctx *c, double t, double dt)
-{
-	int f[4];
-	for (double tk : {t, t + dt, (t + dt) + dt})
-		if (step::stage_flags(tk, dt, c->p.t_boundary, 4, f)) return true;
-	return false;
-}
-// ... and steps s, s + 1, s + 2 as one three-step launch: the third step's flags come from (t + dt) + dt.
-bool triple_is_exact(const crd_ctx *c, double t0, int64_t s, double dt)
-{
-	const double t = t0 + (double)s * dt;
-	return pair_is_exact(c, t0, s, dt) && same_flags(c, t0 + (double)(s + 2) * dt, (t + dt) + dt, dt);
-}
+
+}  // namespace
 
 // RCCL runs: one decision for the whole ring on where in the exchange cycle the call starts (see crd_ctx::agree_dev).  begin_
 // enqueues the reduction on the comm stream and returns; finish_ waits for it.  Every rank of the run makes both calls in every
@@ -284,22 +291,6 @@ int finish_cycle_agreement(crd_ctx *c, int *agreed)
 	return CRD_OK;
 }
 
-constexpr int kMaxTimedLaunches = 64;
-// Step of an exchange cycle whose single full-slab launch is the one timed in a multi-slab fused run (step 0 is split in two).
-constexpr int kTimedCycleStep = 1;
-
-int ensure_timing_events(crd_ctx *c)
-{
-	while ((int)c->ev_k.size() < 2 * kMaxTimedLaunches) {
-		hipEvent_t e;
-		HIP_TRY(c, hipEventCreate(&e));
-		c->ev_k.push_back(e);
-	}
-	return CRD_OK;
-}
-
-}  // namespace
-
 void decide_cycle_start(crd_ctx *const *all, int n_all)
 {
 	int q0 = all[0]->cycle_pos;
@@ -324,20 +315,210 @@ FusedCall make_fused_call(const crd_ctx *c, double t, double dt, int src, int ds
 	return call;
 }
 
-// The stepping loop shared by crd_step_rk4 / crd_step_rk4_timed / the group call.
+namespace {
+
+// What a stepping call was asked for, and the run recorder's part in it (rec_stride 0: none).  With a recorder only the grouping of
+// steps into launches changes: no pair, triple or deferred launch straddles a sample -- `lim(s)` is where the steps that may share a
+// launch with step s end.  Times are formed from t0 and the step's index in the call as ever.
+struct StepCall {
+	crd_ctx *const *cs;
+	int n;
+	double t0, dt;
+	int64_t nsteps;
+	bool timing;
+	crd_recorder *rec;
+	int64_t rec_stride, rec_steps;
+	int stepper;
+	double time(int64_t s) const { return t0 + (double)s * dt; }
+	int64_t lim(int64_t s) const { return step::sample_limit(s, nsteps, rec_stride, rec_steps); }
+	int sample(int64_t s, int plane) const { return step::sample_due(s, rec_stride, rec_steps) ? recorder_sample(rec, plane, time(s)) : CRD_OK; }  // s: steps taken so far
+};
+
+// A call that ends on an odd number of fused launches has its result in SA: swap the plane pointers.
+void result_into_Y(crd_ctx *const *cs, int n, int cur)
+{
+	for (int k = 0; k < n && cur != crd_ctx::Y; k++) {
+		std::swap(cs[k]->plane[crd_ctx::Y][0], cs[k]->plane[crd_ctx::SA][0]);
+		std::swap(cs[k]->plane[crd_ctx::Y][1], cs[k]->plane[crd_ctx::SA][1]);
+	}
+}
+
+// theta-blocks: staged kernels, every block of the run in this one call
+int run_blocks(const StepCall &a)
+{
+	crd_ctx *const *cs = a.cs;
+	if (cs[0]->halo != CRD_HALO_LOCAL || a.n != cs[0]->n_slabs) return fail(cs[0], CRD_ESTATE, "theta-blocks step as a LOCAL group holding every block of the run");
+	for (int k = 0; k < a.n; k++) cs[k]->cycle_pos = -1;
+	if (a.nsteps > 0)
+		if (int rc = prime_block_halo(cs, a.n, crd_ctx::Y)) return rc;
+	for (int64_t s = 0; s < a.nsteps; s++)
+		if (int rc = staged_step_blocks(cs, a.n, a.time(s), a.dt)) return rc;
+	for (int k = 0; k < a.n; k++) {
+		if (int rc = set_device(cs[k])) return rc;
+		HIP_TRY(cs[k], hipStreamWaitEvent(cs[k]->compute, cs[k]->ev_halo, 0));
+	}
+	return CRD_OK;
+}
+
+int run_single(const StepCall &a, int *timed_out)
+{
+	crd_ctx *c = a.cs[0];
+	if (int rc = set_device(c)) return rc;
+	const bool f64 = c->p.precision == CRD_PRECISION_F64;  // (its three-step kernel has the instantiation with the absorbing rows' selects)
+	int cur = crd_ctx::Y, timed = 0;
+	for (int64_t s = 0; s < a.nsteps;) {
+		const double t = a.time(s);
+		hipEvent_t *kb = nullptr, *ke = nullptr;
+		// The plan may say "two steps per launch" (measured -- by this call's first launch, perhaps --, or pinned): pairs while two steps
+		// are left, a single-step launch for an odd last one; a three-step plan: triples while three steps are left, then a pair or a
+		// single step (crd_schedule.h).
+		const int per_launch = (a.stepper == CRD_STEPPER_FUSED && c->plan.tuned) ? fused_steps_supported(c->p.precision, c->desc, c->plan.steps) : 1;
+		int rc, took = step::launch_steps(per_launch, f64, a.t0, a.dt, c->p.t_boundary, s, a.lim(s));
+		if (a.timing && step::timed_here(step::timed_kind(per_launch, f64, a.t0, a.dt, c->p.t_boundary, a.nsteps), took, s, a.nsteps, timed)) {
+			kb = &c->ev_k[(size_t)(2 * timed)];
+			ke = &c->ev_k[(size_t)(2 * timed + 1)];
+			timed++;
+			c->timed_steps = took;
+		}
+		if (a.stepper == CRD_STEPPER_STAGED) {
+			rc = staged_step_self(c, t, a.dt, kb, ke);
+		} else {
+			const int dst = (cur == crd_ctx::Y) ? crd_ctx::SA : crd_ctx::Y;
+			rc = fused_step_self(c, t, a.dt, cur, dst, kb, ke, took);
+			cur = dst;
+		}
+		if (rc) return rc;
+		s += took;
+		if (int rs = a.sample(s, a.stepper == CRD_STEPPER_STAGED ? (int)crd_ctx::Y : cur)) return rs;
+	}
+	result_into_Y(a.cs, 1, cur);
+	*timed_out = timed;
+	return CRD_OK;
+}
+
+// Where in the exchange cycle does the resident state stand?  If the previous call left it mid-cycle (or right after an exchange) the
+// ghost rows are as good as they need to be and this call carries on from there; otherwise -- new state, staged stepper, slabs that
+// disagree -- it starts with an exchange.  (A 20-step call on an 8192 x 1024 slab is 1.2 ms: an exposed exchange in front of it is
+// several per cent.)
+// Under RCCL (`ring`) that decision has to be the RING's, not this rank's: a rank that alone holds a new state (an upload on that
+// rank only, a failed call) would prime its halo while its neighbours carry on, and the ring's send / receive sequences would no
+// longer pair.  So the ranks reduce their positions first.  The reduction (and the host's wait for it) hides under the call's first
+// step wherever that step involves no exchange of its own (q0 = 0 .. E - 4: the step is issued speculatively into the scratch planes
+// and simply issued again, behind an exchange, if the ring turns out to disagree): *agreement_pending.
+int resolve_cycle_start(const StepCall &a, bool fused, bool ring, int E, int *q0_out, bool *agreement_pending)
+{
+	crd_ctx *const *cs = a.cs;
+	crd_ctx *lead = cs[0];
+	int q0 = fused ? lead->cycle_start : -1;  // (decide_cycle_start: one decision for every slab of the run)
+	if (a.nsteps > 0) {
+		for (int k = 0; k < a.n; k++) cs[k]->cycle_pos = -1;  // until this call has gone through
+		for (int k = 0; k < a.n; k++) cs[k]->ghost_deferred = false;  // (a call always finishes what its last step deferred)
+		if (ring) {
+			if (int rc = begin_cycle_agreement(lead, q0)) return rc;
+			*agreement_pending = true;
+			if (q0 < 0 || q0 >= E - 3) {  // nothing to issue ahead of the answer (the call's first launch may be the cycle's last: a pair, or -- fp32 -- a triple)
+				if (int rc = finish_cycle_agreement(lead, &q0)) return rc;
+				*agreement_pending = false;
+			}
+		}
+		if (q0 < 0) {
+			if (ring && lead->cycle_start >= 0) lead->agreement_restarts++;
+			if (int rc = prime_halo(cs, a.n, crd_ctx::Y, fused ? cycle_ghost(lead) : 1, fused)) return rc;
+			q0 = 0;
+		}
+	}
+	*q0_out = q0;
+	return CRD_OK;
+}
+
+// The ring disagreed with the position the call's first launch was issued from: some rank holds a new state, every rank starts
+// afresh.  The launch just issued wrote the scratch planes only (plane Y is untouched) and is overwritten by the one the caller
+// issues again from step 0, in stream order.
+int start_afresh(const StepCall &a)
+{
+	a.cs[0]->agreement_restarts++;
+	for (int k = 0; k < a.n; k++) a.cs[k]->ghost_deferred = false;  // (the launch issued ahead of the answer is void, and so is what it deferred)
+	return prime_halo(a.cs, a.n, crd_ctx::Y, cycle_ghost(a.cs[0]), true);
+}
+
+int run_slabs(const StepCall &a, int *timed_out)
+{
+	crd_ctx *const *cs = a.cs;
+	crd_ctx *lead = cs[0];
+	const int n = a.n;
+	const bool fused = (a.stepper == CRD_STEPPER_FUSED);
+	const int E = cycle_steps(lead);
+	for (int k = 0; k < n; k++)
+		if (cs[k]->exchange_every != E) return fail(lead, CRD_EINVAL, "contexts of one run disagree on the exchange period");
+	int q0 = -1;
+	bool agreement_pending = false;
+	if (int rc = resolve_cycle_start(a, fused, fused && n == 1 && lead->halo == CRD_HALO_RCCL, E, &q0, &agreement_pending)) return rc;
+	int cur = crd_ctx::Y, timed = 0;
+	// Two steps per launch where the lead context's plan says so (measured, or pinned): pairs that do not straddle an exchange.
+	// Where the exchanges fall in the step sequence does not depend on the pairing, so the ranks of a ring / the threads of a group
+	// may pair differently (each by its own plan) and still meet at the same collectives.
+	// Three where the three-step kernel takes slabs (fp32: a strip per wavefront; fp64's block strip measured nothing on a rank's
+	// share and keeps pairs: fused_steps_supported), by the same rule -- a triple never straddles an exchange either.
+	bool pairs = fused && lead->plan.tuned && lead->plan.steps >= 2;
+	for (int k = 0; k < n; k++) pairs = pairs && fused_two_steps_supported(cs[k]->desc);
+	bool triples = pairs && lead->plan.steps == 3;
+	for (int k = 0; k < n; k++) triples = triples && fused_steps_supported(cs[k]->p.precision, cs[k]->desc, 3) == 3;
+	for (int64_t s = 0; s < a.nsteps;) {
+		const int q = (int)((s + q0) % E);
+		const int64_t end = a.lim(s);
+		const int nsub = step::launch_steps(triples ? 3 : pairs ? 2 : 1, false, a.t0, a.dt, lead->p.t_boundary, s, end, q, E);
+		bool finishes_deferred = false;
+		for (int k = 0; k < n; k++) finishes_deferred = finishes_deferred || cs[k]->ghost_deferred;
+		const bool timed_step = a.timing && !timed && step::timed_slab_launch(fused, q, nsub, E, finishes_deferred, s, a.nsteps);
+		if (fused) {
+			const int dst = (cur == crd_ctx::Y) ? crd_ctx::SA : crd_ctx::Y;
+			const CycleLaunch L{a.time(s), a.dt, cur, dst, q, nsub, triples ? 3 : 2, timed_step, s + nsub == end, E, cycle_ghost(lead), cycle_band(lead)};
+			if (int rc = fused_launch_multi(cs, n, L)) return rc;
+			cur = dst;
+		} else if (int rc = staged_step_multi(cs, n, a.time(s), a.dt, timed_step)) {
+			return rc;
+		}
+		if (timed_step) timed = 1;
+		s += nsub;
+		if (agreement_pending) {  // the first launch is on its way: now hear what the ring says
+			int agreed = -1;
+			if (int rc = finish_cycle_agreement(lead, &agreed)) return rc;
+			agreement_pending = false;
+			if (agreed != q0) {
+				if (int rc = start_afresh(a)) return rc;
+				q0 = 0, cur = crd_ctx::Y, timed = 0, s = 0;
+			}
+		}
+		// (the sample reads owned rows, which only this compute stream writes: it is behind the cycle's last step wherever that step
+		// was split around an exchange, and the exchange itself -- the second stream -- writes ghost rows only)
+		if (int rs = a.sample(s, fused ? cur : (int)crd_ctx::Y)) return rs;
+	}
+	// (several issuing threads: the neighbours read this thread's plane pointers while they enqueue their pulls)
+	if (lead->bar && !lead->bar->wait()) return fail(lead, CRD_ESTATE, "another slab's issuing thread failed");
+	result_into_Y(cs, n, cur);
+	// leave the compute stream of every context ordered behind its last band launch and exchange
+	for (int k = 0; k < n; k++) {
+		if (int rc = set_device(cs[k])) return rc;
+		HIP_TRY(cs[k], hipStreamWaitEvent(cs[k]->compute, cs[k]->ev_edges, 0));
+		HIP_TRY(cs[k], hipStreamWaitEvent(cs[k]->compute, cs[k]->ev_halo, 0));
+	}
+	if (fused && a.nsteps > 0)
+		for (int k = 0; k < n; k++) cs[k]->cycle_pos = (int)((q0 + a.nsteps) % E);
+	*timed_out = timed;
+	return CRD_OK;
+}
+
+}  // namespace
+
+// The stepping loop shared by crd_step_rk4 / crd_step_rk4_timed / the group call: validation and the recorder's room here, then the
+// run by layout.  A call that would overrun the recorder is refused whole, before anything is launched.
 int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, int *timed_launches, crd_recorder *rec)
 {
 	crd_ctx *lead = cs[0];
 	if (nsteps < 0 || !(dt > 0.0) || !std::isfinite(t0)) return fail(lead, CRD_EINVAL, "bad t0 / dt / nsteps");
-	// A run recorder (crd_recorder_open) takes a sample behind every step whose count since it was opened is a multiple of its stride.
-	// Only the grouping of steps into launches changes: no pair, triple or deferred launch straddles a sample -- `lim(s)` is where the
-	// steps that may share a launch with step s end.  Times are formed from t0 and the step's index in the call as ever.  A call that
-	// would overrun the recorder is refused whole, before anything is launched.
 	const int64_t rec_stride = rec ? recorder_stride(rec) : 0, rec_steps = rec ? recorder_steps(rec) : 0;
 	if (rec)
 		if (int rc = recorder_room(rec, (rec_steps + nsteps) / rec_stride - rec_steps / rec_stride)) return rc;
-	auto lim = [&](int64_t s) { return rec ? std::min<int64_t>(nsteps, s + (rec_stride - (rec_steps + s) % rec_stride)) : nsteps; };
-	auto sample_due = [&](int64_t s) { return rec && s > 0 && (rec_steps + s) % rec_stride == 0; };  // s: steps of this call taken so far
 	const int stepper = resolve_stepper(lead);
 	if (stepper < 0) return fail(lead, CRD_EINVAL, "fused stepper not available for this configuration");
 	for (int k = 0; k < n; k++) arkode::drop(cs[k]->dense, cs[k]->ark);  // stepping on from the state handed back, not from the integrator's internal one
@@ -347,173 +528,14 @@ int run_steps(crd_ctx *const *cs, int n, double t0, double dt, int64_t nsteps, i
 		for (int k = 0; k < n; k++) cs[k]->cycle_pos = -1;  // the staged stepper keeps one ghost row of one field current, not the deep halo
 	for (int k = 0; k < n; k++)
 		if (resolve_stepper(cs[k]) != stepper) return fail(lead, CRD_EINVAL, "contexts of one run disagree on the stepper");
+	const StepCall a{cs, n, t0, dt, nsteps, timed_launches != nullptr, rec, rec_stride, rec_steps, stepper};
 	int timed = 0;
-	const bool single = (lead->halo == CRD_HALO_SELF);
 	if (lead->d0 > 1) {
-		// theta-blocks: staged kernels, every block of the run in this one call
-		if (lead->halo != CRD_HALO_LOCAL || n != lead->n_slabs) return fail(lead, CRD_ESTATE, "theta-blocks step as a LOCAL group holding every block of the run");
-		for (int k = 0; k < n; k++) cs[k]->cycle_pos = -1;
-		if (nsteps > 0)
-			if (int rc = prime_block_halo(cs, n, crd_ctx::Y)) return rc;
-		for (int64_t s = 0; s < nsteps; s++)
-			if (int rc = staged_step_blocks(cs, n, t0 + (double)s * dt, dt)) return rc;
-		for (int k = 0; k < n; k++) {
-			if (int rc = set_device(cs[k])) return rc;
-			HIP_TRY(cs[k], hipStreamWaitEvent(cs[k]->compute, cs[k]->ev_halo, 0));
-		}
+		if (int rc = run_blocks(a)) return rc;
 		if (timed_launches) *timed_launches = 0;
 		return CRD_OK;
 	}
-	if (single) {
-		crd_ctx *c = lead;
-		if (int rc = set_device(c)) return rc;
-		int cur = crd_ctx::Y;
-		for (int64_t s = 0; s < nsteps;) {
-			const double t = t0 + (double)s * dt;
-			hipEvent_t *kb = nullptr, *ke = nullptr;
-			// The plan may say "two steps per launch" (measured, or pinned): pairs while two steps are left, a single-step launch
-			// for an odd last one (pair_is_exact: see there).
-			const int per_launch = (stepper == CRD_STEPPER_FUSED && c->plan.tuned) ? fused_steps_supported(c->p.precision, c->desc, c->plan.steps) : 1;
-			const bool pairing = per_launch >= 2;
-			// (a three-step plan: triples while three steps are left, then a pair or a single step)
-			const int64_t end = lim(s);
-			const bool triple = per_launch == 3 && s + 3 <= end && triple_is_exact(c, t0, s, dt) && (c->p.precision == CRD_PRECISION_F64 || !triple_absorbs(c, t, dt));
-			int rc, took = triple ? 3 : (pairing && s + 2 <= end && pair_is_exact(c, t0, s, dt)) ? 2 : 1;
-			// every fourth step at most: an event pair around EVERY launch of a short run would sit inside the region being timed.  Only
-			// launches of the plan's own kind are timed (a pairing plan's odd last step, or a pair stepped singly, goes out as a one-step
-			// launch: another kernel, which must not enter the average; runs too short to hold a pair time what there is).
-			const int64_t want = std::min<int64_t>(kMaxTimedLaunches, std::max<int64_t>(1, nsteps / 4));
-			const bool triples_here = per_launch == 3 && nsteps >= 3 && (c->p.precision == CRD_PRECISION_F64 || !triple_absorbs(c, t0, dt));  // (the kind of launch the call starts with)
-			const int kind = triples_here ? 3 : (pairing && nsteps >= 2) ? 2 : 1;
-			if (timed_launches && timed < want && took == kind && (s * want / std::max<int64_t>(nsteps, 1)) >= timed && ((s % 4) >= 1 || nsteps < 4)) {
-				kb = &c->ev_k[(size_t)(2 * timed)];
-				ke = &c->ev_k[(size_t)(2 * timed + 1)];
-				timed++;
-				c->timed_steps = took;
-			}
-			if (stepper == CRD_STEPPER_STAGED) {
-				rc = staged_step_self(c, t, dt, kb, ke);
-			} else {
-				const int dst = (cur == crd_ctx::Y) ? crd_ctx::SA : crd_ctx::Y;
-				rc = fused_step_self(c, t, dt, cur, dst, kb, ke, took);
-				cur = dst;
-			}
-			if (rc) return rc;
-			s += took;
-			if (sample_due(s))
-				if (int rs = recorder_sample(rec, stepper == CRD_STEPPER_STAGED ? (int)crd_ctx::Y : cur, t0 + (double)s * dt)) return rs;
-		}
-		if (cur != crd_ctx::Y) {  // odd number of fused steps: the result sits in SA; swap the plane pointers
-			std::swap(c->plane[crd_ctx::Y][0], c->plane[crd_ctx::SA][0]);
-			std::swap(c->plane[crd_ctx::Y][1], c->plane[crd_ctx::SA][1]);
-		}
-	} else {
-		const bool fused = (stepper == CRD_STEPPER_FUSED);
-		const int E = cycle_steps(lead);
-		for (int k = 0; k < n; k++)
-			if (cs[k]->exchange_every != E) return fail(lead, CRD_EINVAL, "contexts of one run disagree on the exchange period");
-		// Where in the exchange cycle does the resident state stand?  If the previous call left it mid-cycle (or right after an
-		// exchange) the ghost rows are as good as they need to be and this call carries on from there; otherwise -- new state,
-		// staged stepper, slabs that disagree -- it starts with an exchange.  (A 20-step call on an 8192 x 1024 slab is 1.2 ms:
-		// an exposed exchange in front of it is several per cent.)
-		int q0 = fused ? lead->cycle_start : -1;  // (decide_cycle_start: one decision for every slab of the run)
-		// Under RCCL that decision has to be the RING's, not this rank's: a rank that alone holds a new state (an upload on that
-		// rank only, a failed call) would prime its halo while its neighbours carry on, and the ring's send / receive sequences
-		// would no longer pair.  So the ranks reduce their positions first.  The reduction (and the host's wait for it) hides
-		// under the call's first step wherever that step involves no exchange of its own (q0 = 0 .. E - 4: the step is issued
-		// speculatively into the scratch planes and simply issued again, behind an exchange, if the ring turns out to disagree).
-		const bool ring = fused && n == 1 && lead->halo == CRD_HALO_RCCL;
-		bool agreement_pending = false;
-		if (nsteps > 0) {
-			for (int k = 0; k < n; k++) cs[k]->cycle_pos = -1;  // until this call has gone through
-			for (int k = 0; k < n; k++) cs[k]->ghost_deferred = false;  // (a call always finishes what its last step deferred)
-			if (ring) {
-				if (int rc = begin_cycle_agreement(lead, q0)) return rc;
-				agreement_pending = true;
-				if (q0 < 0 || q0 >= E - 3) {  // nothing to issue ahead of the answer (the call's first launch may be the cycle's last: a pair, or -- fp32 -- a triple)
-					if (int rc = finish_cycle_agreement(lead, &q0)) return rc;
-					agreement_pending = false;
-				}
-			}
-			if (q0 < 0) {
-				if (ring && lead->cycle_start >= 0) lead->agreement_restarts++;
-				if (int rc = prime_halo(cs, n, crd_ctx::Y, fused ? cycle_ghost(lead) : 1, fused)) return rc;
-				q0 = 0;
-			}
-		}
-		int cur = crd_ctx::Y;
-		// Two steps per launch where the lead context's plan says so (measured, or pinned): pairs that do not straddle an exchange.
-		// Where the exchanges fall in the step sequence does not depend on the pairing, so the ranks of a ring / the threads of a group
-		// may pair differently (each by its own plan) and still meet at the same collectives.
-		// Three where the three-step kernel takes slabs (fp32: a strip per wavefront; fp64's block strip measured nothing on a rank's
-		// share and keeps pairs: fused_steps_supported), by the same rule -- a triple never straddles an exchange either.
-		bool pairs = fused && lead->plan.tuned && lead->plan.steps >= 2;
-		for (int k = 0; k < n; k++) pairs = pairs && fused_two_steps_supported(cs[k]->desc);
-		bool triples = pairs && lead->plan.steps == 3;
-		for (int k = 0; k < n; k++) triples = triples && fused_steps_supported(cs[k]->p.precision, cs[k]->desc, 3) == 3;
-		for (int64_t s = 0; s < nsteps;) {
-			const int q = (int)((s + q0) % E);
-			const double t_s = t0 + (double)s * dt;
-			// (a launch is the cycle's first -- which waits for the halo -- or its last -- which sends the next --, never both: at E = 3 a
-			// triple from q = 0 would be; found by tests/long_oracle_sweep.py)
-			const int64_t end = lim(s);
-			const int nsub = (triples && s + 3 <= end && q + 3 <= E && (q > 0 || E > 3) && triple_is_exact(lead, t0, s, dt) && !triple_absorbs(lead, t_s, dt))
-			                     ? 3
-			                     : (pairs && s + 2 <= end && q + 2 <= E && pair_is_exact(lead, t0, s, dt)) ? 2 : 1;
-			// time one launch of the dominant kernel mid-run (fused: a launch of the cycle that is one full-height sweep, i.e. neither
-			// the split first nor the split last one, nor the one that finishes a first whose ghost readers were deferred -- whatever
-			// the two launches take, one step or two)
-			bool finishes_deferred = false;
-			for (int k = 0; k < n; k++) finishes_deferred = finishes_deferred || cs[k]->ghost_deferred;
-			const bool middle = q >= 1 && q + nsub < E && !finishes_deferred;
-			const bool timed_step = timed_launches && !timed && (fused ? (middle && (s >= nsteps / 2 || s + E >= nsteps)) : s >= nsteps / 2);
-			const double t = t0 + (double)s * dt;
-			if (fused) {
-				const int dst = (cur == crd_ctx::Y) ? crd_ctx::SA : crd_ctx::Y;
-				if (int rc = fused_launch_multi(cs, n, t, dt, cur, dst, q, nsub, timed_step, s + nsub == end, triples ? 3 : 2)) return rc;
-				cur = dst;
-			} else if (int rc = staged_step_multi(cs, n, t, dt, timed_step)) {
-				return rc;
-			}
-			if (timed_step) timed = 1;
-			s += nsub;
-			if (agreement_pending) {  // the first launch is on its way: now hear what the ring says
-				int agreed = -1;
-				if (int rc = finish_cycle_agreement(lead, &agreed)) return rc;
-				agreement_pending = false;
-				if (agreed != q0) {
-					// Some rank holds a new state: every rank starts afresh.  The launch just issued wrote the scratch planes only (plane Y
-					// is untouched) and is overwritten by the one issued again below, in stream order.
-					lead->agreement_restarts++;
-					for (int k = 0; k < n; k++) cs[k]->ghost_deferred = false;  // (the launch issued ahead of the answer is void, and so is what it deferred)
-					if (int rc = prime_halo(cs, n, crd_ctx::Y, cycle_ghost(lead), true)) return rc;
-					q0 = 0;
-					cur = crd_ctx::Y;
-					timed = 0;
-					s = 0;
-				}
-			}
-			// (the sample reads owned rows, which only this compute stream writes: it is behind the cycle's last step wherever that step
-			// was split around an exchange, and the exchange itself -- the second stream -- writes ghost rows only)
-			if (sample_due(s))
-				if (int rs = recorder_sample(rec, fused ? cur : (int)crd_ctx::Y, t0 + (double)s * dt)) return rs;
-		}
-		// (several issuing threads: the neighbours read this thread's plane pointers while they enqueue their pulls)
-		if (lead->bar && !lead->bar->wait()) return fail(lead, CRD_ESTATE, "another slab's issuing thread failed");
-		if (cur != crd_ctx::Y)
-			for (int k = 0; k < n; k++) {
-				std::swap(cs[k]->plane[crd_ctx::Y][0], cs[k]->plane[crd_ctx::SA][0]);
-				std::swap(cs[k]->plane[crd_ctx::Y][1], cs[k]->plane[crd_ctx::SA][1]);
-			}
-		// leave the compute stream of every context ordered behind its last band launch and exchange
-		for (int k = 0; k < n; k++) {
-			if (int rc = set_device(cs[k])) return rc;
-			HIP_TRY(cs[k], hipStreamWaitEvent(cs[k]->compute, cs[k]->ev_edges, 0));
-			HIP_TRY(cs[k], hipStreamWaitEvent(cs[k]->compute, cs[k]->ev_halo, 0));
-		}
-		if (fused && nsteps > 0)
-			for (int k = 0; k < n; k++) cs[k]->cycle_pos = (int)((q0 + nsteps) % E);
-	}
+	if (int rc = lead->halo == CRD_HALO_SELF ? run_single(a, &timed) : run_slabs(a, &timed)) return rc;
 	if (timed_launches) *timed_launches = timed;
 	if (rec) recorder_advance(rec, nsteps);
 	return CRD_OK;
@@ -588,7 +610,7 @@ static int group_step(crd_ctx *const *ctxs, int n, double t0, double dt, int64_t
 	for (int k = 0; k < n; k++) ctxs[k]->bar = &bar;
 	std::vector<int> rcs((size_t)nthreads, CRD_OK);
 	auto work = [&](int q) {
-		rcs[(size_t)q] = run_steps(ctxs + first[(size_t)q], first[(size_t)q + 1] - first[(size_t)q], t0, dt, nsteps, timed ? &timed_of[(size_t)q] : nullptr);
+		rcs[(size_t)q] = run_steps(ctxs + first[(size_t)q], first[(size_t)q + 1] - first[(size_t)q], t0, dt, nsteps, timed ? &timed_of[(size_t)q] : nullptr, nullptr);  // (a recorded group runs on one thread, above)
 		if (rcs[(size_t)q] != CRD_OK) bar.leave_failed();
 	};
 	std::vector<std::thread> pool;
@@ -602,479 +624,6 @@ static int group_step(crd_ctx *const *ctxs, int n, double t0, double dt, int64_t
 			return rcs[(size_t)q];
 		}
 	return CRD_OK;
-}
-
-int crd_adaptive_defaults(crd_adaptive_options *o)
-{
-	if (!o) return CRD_EINVAL;
-	o->rtol = 1.e-5;   // src/FHNmodel_torus.cpp:197
-	o->atol = 1.e-10;  // :198
-	o->h0 = 0.0;
-	o->safety = 0.96;
-	o->bias = 1.5;
-	o->growth = 20.0;
-	o->shrink = 0.1;
-	o->max_steps = 200000;  // :372
-	o->h_max = 0.0;         // automatic: the diffusion-stability bound
-	o->dense_output = 1;    // ARK_NORMAL, :423
-	o->method = CRD_ADAPT_ARKODE;  // the reference's integrator: ARKodeInit(mem, f, NULL, ...) = default explicit table, order 4 (:362)
-	return CRD_OK;
-}
-
-// f(t, plane src) -> plane dst on every slab (bare RHS with the stage kernel; multi-slab: one ghost row of var0 first).
-static int rhs_on_planes(crd_ctx *const *cs, int n, double t, int src, int dst)
-{
-	const bool multi = cs[0]->halo != CRD_HALO_SELF;
-	if (multi)
-		if (int rc = prime_halo(cs, n, src, 1, false)) return rc;
-	for (int k = 0; k < n; k++) {
-		crd_ctx *c = cs[k];
-		if (int rc = set_device(c)) return rc;
-		StageCall call{};
-		call.stage = 0;
-		call.absorb = absorbing(c, t) ? 1 : 0;
-		call.yin = c->planes(src);
-		call.yout = c->planes(dst);
-		if (multi) HIP_TRY(c, hipStreamWaitEvent(c->compute, c->ev_halo, 0));
-		HIP_TRY(c, launch_stage(c->p.precision, c->desc, call, 0, c->nyl, c->compute));
-	}
-	return CRD_OK;
-}
-
-// One scalar per slab (left in c->scalar_dev by work already enqueued on the compute streams) combined over the run: the sum or
-// the maximum, identical on every rank (RCCL: ncclAllReduce; LOCAL groups: added / compared on the host in slab order).
-static int collect_scalar(crd_ctx *const *cs, int n, bool take_max, double *out)
-{
-	// The producers wrote to scalar_sink(): host memory, or -- RCCL runs -- device memory that is reduced over the ranks first and
-	// copied to the page-locked buffer (a copy to pageable memory goes through the runtime's staging buffer: ~10 us per attempt of an
-	// error-controlled run on a small grid).  Every slab's work is enqueued before the first one is waited for.
-	for (int k = 0; k < n; k++) {
-		crd_ctx *c = cs[k];
-		if (c->scalar_sink() == c->scalar_host) continue;
-		if (int rc = set_device(c)) return rc;
-		if (c->halo == CRD_HALO_RCCL) NCCL_TRY(c, g_rccl.AllReduce(c->scalar_dev, c->scalar_dev, 1, ncclDouble, take_max ? ncclMax : ncclSum, c->nccl, c->compute));
-		HIP_TRY(c, hipMemcpyAsync(c->scalar_host, c->scalar_dev, sizeof(double), hipMemcpyDeviceToHost, c->compute));
-	}
-	double acc = 0.0;
-	for (int k = 0; k < n; k++) {
-		crd_ctx *c = cs[k];
-		if (int rc = set_device(c)) return rc;
-		HIP_TRY(c, hipStreamSynchronize(c->compute));
-		const double part = c->scalar_host[0];
-		if (take_max) acc = (part > acc || part != part) ? part : acc;
-		else acc += part;
-	}
-	*out = acc;
-	return CRD_OK;
-}
-
-// ARKode's step-size controller (CRD_ADAPT_ARKODE) and its bookkeeping: crd_arkode.h (shared with the ensemble's integrator).
-
-// arkHin: ARKode's estimate of the first step from y'' along a forward Euler trial step, on the planes: f0 -> SB, trial state ->
-// SA, f(trial) -> ACC (all three are scratch on a fresh state).
-static int arkode_initial_step(crd_ctx *const *cs, int n, double t0, double tout, int cur, const crd_adaptive_options &o, double n_components, double *h0)
-{
-	crd_ctx *lead = cs[0];
-	arkode::Hin H;
-	if (!arkode::hin_start(H, t0, tout)) return fail(lead, CRD_EINVAL, arkode::kHinTooClose);
-	if (int rc = rhs_on_planes(cs, n, t0, cur, crd_ctx::SB)) return rc;
-	for (int k = 0; k < n; k++) {
-		crd_ctx *c = cs[k];
-		if (int rc = set_device(c)) return rc;
-		HIP_TRY(c, launch_hin_bound(c->p.precision, c->planes(cur), c->planes(crd_ctx::SB), c->nx, c->nyl, o.rtol, o.atol, c->scalar_sink(), c->compute));
-	}
-	double hub_inv = 0.0;
-	if (int rc = collect_scalar(cs, n, true, &hub_inv)) return rc;
-	arkode::hin_bound(H, hub_inv);
-	while (!H.done) {
-		const double hg = H.hg;
-		for (int k = 0; k < n; k++) {
-			crd_ctx *c = cs[k];
-			if (int rc = set_device(c)) return rc;
-			HIP_TRY(c, launch_axpy_planes(c->p.precision, c->planes(cur), c->planes(crd_ctx::SB), hg, c->planes(crd_ctx::SA), c->nx, c->nyl, c->compute));
-		}
-		if (int rc = rhs_on_planes(cs, n, t0 + hg, crd_ctx::SA, crd_ctx::ACC)) return rc;
-		for (int k = 0; k < n; k++) {
-			crd_ctx *c = cs[k];
-			if (int rc = set_device(c)) return rc;
-			HIP_TRY(c, launch_ydd_sumsq(c->p.precision, c->planes(cur), c->planes(crd_ctx::SB), c->planes(crd_ctx::ACC), hg, o.rtol, o.atol, c->nx, c->nyl, c->err_partials,
-			                            c->scalar_sink(), c->compute));
-		}
-		double sum = 0.0;
-		if (int rc = collect_scalar(cs, n, false, &sum)) return rc;
-		arkode::hin_ydd(H, std::sqrt(sum / n_components));
-	}
-	*h0 = H.h0;
-	return CRD_OK;
-}
-
-// Error-controlled integration of all slabs of a run (n = 1: a single-slab or RCCL context; n > 1: a LOCAL group).
-static int integrate_adaptive_impl(crd_ctx *const *cs, int n, double t0, double tout, const crd_adaptive_options *opt_in, crd_adaptive_stats *stats)
-{
-	crd_ctx *lead = cs[0];
-	TraceRange range("crd_integrate_adaptive");
-	crd_adaptive_options o;
-	crd_adaptive_defaults(&o);
-	if (opt_in) o = *opt_in;
-	if (!arkode::options_valid(o, t0, tout))
-		return fail(lead, CRD_EINVAL, "bad adaptive options / time interval");
-	if (lead->d0 > 1) return fail(lead, CRD_EINVAL, "the error-controlled integrators need phi-slabs (theta-blocks step with the staged RK4 only)");
-	const bool multi = lead->halo != CRD_HALO_SELF;
-	const bool arkode_method = o.method == CRD_ADAPT_ARKODE;
-	const bool dense = o.dense_output != 0 || arkode_method;  // ARKode's ARK_NORMAL never shortens a step for an output time
-	for (int k = 0; k < n; k++) {
-		crd_ctx *c = cs[k];
-		if (!fused_step_supported(c->p.precision, c->desc)) return fail(lead, CRD_EINVAL, "slab too small for the fused step kernel");
-		if (int rc = set_device(c)) return rc;
-		if (!c->err_partials) {  // two slots: an attempt and the one launched ahead of its verdict
-			c->err_capacity = std::max(fused_max_items(c->desc), 256);  // (256: the block partials of the initial-step norm)
-			HIP_TRY(c, hipMalloc((void **)&c->err_partials, 2 * sizeof(double) * (size_t)c->err_capacity));
-			for (int q = 0; q < 2; q++) {
-				HIP_TRY(c, hipEventCreateWithFlags(&c->ev_attempt[q], hipEventDisableTiming));
-				HIP_TRY(c, hipEventCreateWithFlags(&c->ev_norm[q], hipEventDisableTiming));
-			}
-		}
-		if (dense)
-			for (int f = 0; f < 2; f++)
-				if (!c->plane[crd_ctx::OUT][f])
-					if (int rc = alloc_plane(c, crd_ctx::OUT, f)) return rc;
-	}
-	for (int k = 0; k < n; k++) cs[k]->cycle_pos = -1;  // the integrator exchanges as it needs; a fixed-step call afterwards starts afresh
-	crd_adaptive_stats st{};
-	const double h_cap = arkode::h_cap(o, lead->p);
-	const double n_components = 2.0 * (double)lead->g.nx * (double)lead->g.ny;  // WRMS norm over the whole grid
-	constexpr int kEmbedHalo = kStepHalo + 1;                                     // the fifth stage reads one more row
-
-	// Three state planes take turns as y_n, y_{n+1} and scratch: Y and SA (and OUT with dense output).
-	double t = t0;
-	arkode::Rotation R = arkode::Rotation::fresh(dense);
-	double t_prev = t0;
-	bool resume = dense && arkode::resumes(lead->dense, lead->ark, t0, arkode_method);
-	for (int k = 0; k < n; k++)  // (every slab of a group must still hold the step: an upload to one of them alone ends the carry-over for all)
-		resume = resume && cs[k]->dense.pending && cs[k]->dense.t_out == lead->dense.t_out && cs[k]->dense.t_np1 == lead->dense.t_np1;
-	// Under RCCL that decision has to be the RING's (round-3 advice): crd_state_upload on one rank only is allowed between calls, and a
-	// rank that alone started afresh would run arkHin's exchanges and reductions while its neighbours skip them -- the ring's
-	// collectives would no longer pair.  One ncclAllReduce(min) of the ranks' votes: every rank resumes, or none does.
-	if (lead->halo == CRD_HALO_RCCL && n == 1) {
-		int all = 0;
-		if (int rc = begin_cycle_agreement(lead, resume ? 0 : -1)) return rc;
-		if (int rc = finish_cycle_agreement(lead, &all)) return rc;
-		if (resume && all != 0) lead->agreement_restarts++;
-		resume = resume && all == 0;
-	}
-	for (int k = 0; k < n; k++)
-		if (!resume) cs[k]->dense.pending = false;
-	// The interpolant of the step R.prev -> R.cur (t_n -> t_np1; SB = f_n, ACC = f_{n+1}) at tout into the remaining state plane; then
-	// the step is recorded and the planes are re-labelled (arkode::end_of_call).
-	auto hand_back = [&](double t_n, double t_np1) -> int {
-		const double hstep = t_np1 - t_n;
-		for (int k = 0; k < n; k++) {
-			crd_ctx *c = cs[k];
-			if (int rc = set_device(c)) return rc;
-			HIP_TRY(c, launch_hermite(c->p.precision, c->planes(R.prev), c->planes(R.cur), c->planes(crd_ctx::SB), c->planes(crd_ctx::ACC), c->planes(R.interpolant()), c->nx,
-			                          c->nyl, (tout - t_n) / hstep, hstep, c->compute));
-		}
-		for (int k = 0; k < n; k++) arkode::end_of_call(R, true, cs[k]->dense, tout, t_n, t_np1).apply(cs[k]->plane);
-		return CRD_OK;
-	};
-	auto &A = lead->ark;  // (every context of the run gets a copy at the end)
-	double h = 0.0;
-	if (resume) {
-		st.t_internal = lead->dense.t_np1;
-		if (tout <= lead->dense.t_np1) {  // still inside the step the integrator has already taken: interpolate again
-			R.reinterpolate();
-			if (int rc = hand_back(lead->dense.t_n, lead->dense.t_np1)) return rc;
-			st.t = tout;
-			st.h_next = arkode_method ? A.hprime : std::fmin(o.h0 > 0.0 ? o.h0 : 0.8 * crd_stable_dt(&lead->p), h_cap);
-			if (stats) *stats = st;
-			return CRD_OK;
-		}
-		t = lead->dense.t_np1;
-		R.resume();
-	}
-	if (arkode_method) {
-		if (!resume) {  // a fresh state: ARKodeInit
-			arkode::init(A, t0, o.h0);
-			if (arkode::needs_estimate(A, t0, tout))
-				if (int rc = arkode_initial_step(cs, n, t0, tout, R.cur, o, n_components, &A.h)) return rc;
-			arkode::first_step(A, h_cap);
-		}
-		h = A.h;
-	} else {
-		h = std::fmin(o.h0 > 0.0 ? o.h0 : 0.8 * crd_stable_dt(&lead->p), h_cap);
-	}
-	st.h_first = arkode_method ? arkode::first_attempt(A) : h;
-
-	// Ghost rows of each plane's present content that are still valid (multi-slab; a single slab wraps in the kernel).  The
-	// integrator exchanges kAdaptGhost rows of the state it is about to step from when fewer than the attempt's five are left, and
-	// every attempt produces its rows AND the ghost-region rows its input still covers -- the deep halo of the fixed stepper, by
-	// attempts: one exchange per kAdaptGhost / 5 accepted steps instead of one per attempt (a rejected attempt re-runs on the same
-	// input).  Only owned rows count towards the error norm (FusedArgs::err_lo / err_hi), so every rank still sees the same sum.
-	int shortest = lead->nyl;
-	for (int k = 0; k < lead->d1; k++) {
-		int64_t a0, a1;
-		if (crd_slab_extents(lead->g.ny, k, lead->d1, &a0, &a1) == CRD_OK) shortest = (int)std::min<int64_t>(shortest, a1 - a0 + 1);
-	}
-	const int kAdaptGhost = kEmbedHalo * std::max(1, std::min((kGhost - kStepHalo) / kEmbedHalo, shortest / kEmbedHalo));  // 60 rows: 12 attempts
-	int ext_of[crd_ctx::NPLANES];
-	for (int &e : ext_of) e = multi ? 0 : (1 << 20);
-	// One attempt of size hh at time tt from plane `src` into plane `dst`, enqueued only: the kernel, the fixed-order sum of its
-	// partials, and -- on the second stream, behind an event -- the reduction over the ranks and the copy of the scalar to
-	// page-locked memory.  `slot` (0 / 1) names the buffers; finish_attempt(slot) waits for the scalar.
-	// The two attempt slots (an attempt and the one launched ahead of its verdict) have scalars of their own -- elements 2 and 3; 0 is
-	// collect_scalar's / crd_state_max_abs's, which run on the compute stream with no ordering against a slot's second-stream work.
-	constexpr int kAttemptScalar = 2;
-	bool in_flight[2] = {false, false};  // launched and not yet waited for
-	auto launch_attempt = [&](double tt, double hh, int src, int dst, int slot) -> int {
-		// The attempt behind an exchange is cut in two (round 5): its rows that read owned rows only, [5, nyl - 5), are launched straight
-		// behind the exchange's release and run UNDER it; the rest -- the edge rows and the ghost-region rows -- follow behind the halo
-		// event as one small launch, and the one sum kernel behind that adds both launches' partials.  (Uncut, the 2 x 7.9 MB of an
-		// 8192-column slab's 60 ghost rows travelled with nothing to hide under: 167 us per exchange, 13 us per attempt.)
-		bool under_exchange = false;
-		if (ext_of[src] < kEmbedHalo) {
-			if (int rc = prime_halo(cs, n, src, kAdaptGhost, true)) return rc;
-			under_exchange = true;
-			for (int k = 0; k < n; k++) under_exchange = under_exchange && cs[k]->nyl >= 8 * kEmbedHalo;
-			if (!under_exchange)
-				for (int k = 0; k < n; k++) {
-					if (int rc = set_device(cs[k])) return rc;
-					HIP_TRY(cs[k], hipStreamWaitEvent(cs[k]->compute, cs[k]->ev_halo, 0));
-				}
-			ext_of[src] = kAdaptGhost;
-		}
-		const int e = multi ? ext_of[src] - kEmbedHalo : 0;
-		for (int k = 0; k < n; k++) {
-			crd_ctx *c = cs[k];
-			if (int rc = set_device(c)) return rc;
-			FusedCall call = make_fused_call(c, tt, hh, src, dst);
-			call.embed = arkode_method ? 2 : 1;
-			if (arkode_method) step::stage_flags(tt, hh, c->p.t_boundary, 5, call.absorb);  // the fifth stage's time: t + 3/4 h (Zonneveld); RK4(3)'s is t + h, the fourth's
-			call.plan = arkode_method ? &c->plan_arkode : &c->plan_embed;
-			call.rtol = o.rtol;
-			call.atol = o.atol;
-			call.err_partials = c->err_partials + (size_t)slot * (size_t)c->err_capacity;
-			call.err_capacity = c->err_capacity;
-			const bool reduce_on_device = c->halo == CRD_HALO_RCCL;
-			// (the slot's previous user may have been launched ahead and never waited for: its sum and reduction on the second stream must be
-			// through with the slot's partials and scalar before this attempt writes them -- only then: a slot whose attempt the host has
-			// waited for (finish_attempt) is quiet, and a cross-stream wait in front of every attempt is a bubble of its own)
-			if (in_flight[slot]) HIP_TRY(c, hipStreamWaitEvent(c->compute, c->ev_norm[slot], 0));
-			// The sum of the partials runs on the SECOND stream behind the step kernel's own completion signal, so that the compute stream
-			// carries step kernels only, back to back: a one-block kernel between two sweeps cost its 8 us and 5 more of dispatch latency
-			// it is too short to hide (kernel-trace timelines, profiles/r05/adaptive_attempt_timeline_kernel_trace.txt).
-			// (The RK4(3) pair launches nothing ahead of a verdict: there the hop to the second stream is latency added to every attempt --
-			// 76 -> 86 us measured -- and the sum stays behind its sweep on the compute stream.)
-			const bool sum_off_stream = arkode_method;
-			double *const sum_to = reduce_on_device ? c->scalar_dev + kAttemptScalar + slot : c->scalar_host + kAttemptScalar + slot;
-			call.err_sum = sum_to;
-			call.err_defer_sum = sum_off_stream;
-			call.done_event = sum_off_stream || reduce_on_device ? c->ev_attempt[slot] : c->ev_norm[slot];
-			int items = 0, inner_items = 0;
-			call.err_items_out = &items;
-			if (under_exchange) {
-				FusedCall inner = call;
-				inner.done_event = nullptr;
-				inner.err_defer_sum = true;  // (the second launch, or the second stream, sums both launches' partials)
-				inner.err_items_out = &inner_items;
-				HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, inner, kEmbedHalo, c->nyl - kEmbedHalo, 0, 0, c->compute));
-				HIP_TRY(c, hipStreamWaitEvent(c->compute, c->ev_halo, 0));
-				call.err_offset = inner_items;
-				HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -e, kEmbedHalo, c->nyl - kEmbedHalo, c->nyl + e, c->compute));
-			} else {
-				HIP_TRY(c, launch_fused_step(c->p.precision, c->desc, call, -e, c->nyl + e, 0, 0, c->compute));
-			}
-			if (sum_off_stream || reduce_on_device) HIP_TRY(c, hipStreamWaitEvent(c->comm, c->ev_attempt[slot], 0));
-			if (reduce_on_device) {
-				if (sum_off_stream) HIP_TRY(c, launch_sum_partials(call.err_partials, inner_items + items, sum_to, nullptr, c->comm));
-				NCCL_TRY(c, g_rccl.AllReduce(c->scalar_dev + kAttemptScalar + slot, c->scalar_dev + kAttemptScalar + slot, 1, ncclDouble, ncclSum, c->nccl, c->comm));  // (every rank gets the same bits, hence takes the same decision)
-				HIP_TRY(c, launch_scalar_to_host(c->scalar_dev + kAttemptScalar + slot, c->scalar_host + kAttemptScalar + slot, c->ev_norm[slot], c->comm));
-			} else if (sum_off_stream) {
-				HIP_TRY(c, launch_sum_partials(call.err_partials, inner_items + items, sum_to, c->ev_norm[slot], c->comm));  // (straight into page-locked memory)
-			}
-		}
-		ext_of[dst] = multi ? e : (1 << 20);
-		in_flight[slot] = true;
-		return CRD_OK;
-	};
-	auto finish_attempt = [&](int slot, double *sum) -> int {
-		double acc = 0.0;
-		for (int k = 0; k < n; k++) {  // (LOCAL groups: the slabs' sums added on the host in slab order)
-			crd_ctx *c = cs[k];
-			if (int rc = set_device(c)) return rc;
-			HIP_TRY(c, hipEventSynchronize(c->ev_norm[slot]));
-			acc += c->scalar_host[kAttemptScalar + slot];
-		}
-		in_flight[slot] = false;
-		*sum = acc;
-		return CRD_OK;
-	};
-	auto attempt = [&](double hh, int dst, double *sum) -> int {  // launch and wait (the RK4(3) pair's loop)
-		if (int rc = launch_attempt(t, hh, R.cur, dst, 0)) return rc;
-		return finish_attempt(0, sum);
-	};
-
-	bool after_reject = false;
-	int rc = CRD_OK;
-	int64_t steps_this_call = 0;
-	struct {
-		bool live;
-		double h;
-		int src, dst, slot;
-	} ahead = {false, 0.0, -1, -1, 0};  // the attempt launched ahead of its predecessor's verdict (CRD_ADAPT_ARKODE)
-	int next_slot = 0;
-	while (t < tout && rc == CRD_OK && arkode_method) {
-		// ---- CRD_ADAPT_ARKODE: one step = attempts until the error test passes (arkStep), then arkPrepareNextStep / arkCompleteStep ----
-		if (const char *why = arkode::begin_step(A, t, steps_this_call, o.max_steps)) {
-			rc = fail(lead, CRD_ESTATE, why);
-			break;
-		}
-		const int dst = R.spare;
-		double dsm = 0.0;
-		for (int nef = 0;;) {
-			// This attempt -- unless it is already in flight: the previous step launched it ahead of its own verdict (below).
-			int my_slot;
-			if (ahead.live && ahead.h == A.h && ahead.src == R.cur && ahead.dst == dst) {
-				my_slot = ahead.slot;
-				st.launched_ahead++;
-			} else {
-				my_slot = next_slot;
-				next_slot ^= 1;
-				if ((rc = launch_attempt(t, A.h, R.cur, dst, my_slot))) break;
-			}
-			ahead.live = false;
-			// The step after this one, launched BEFORE this one's error norm is known, on the assumption the integrator makes most of
-			// the time on these grids: the attempt passes and the step size stays (the controller's dead band, or the cap).  If that
-			// turns out wrong the launch is void -- it wrote a plane nobody needs (the one that becomes scratch once this step is
-			// accepted; if this step is rejected, y_{n-1} in it is not needed either: the interpolant is built on the LAST step) --
-			// and the next attempt is simply issued afresh.  The host's wait for the norm (reduction over the ranks, copy, wake-up)
-			// then hides under a kernel that is already running.  No exchange is ever issued ahead.
-			const int after = R.ahead();
-			if (after >= 0 && t + A.h < tout && steps_this_call + 1 < o.max_steps && ext_of[dst] >= kEmbedHalo) {
-				if ((rc = launch_attempt(t + A.h, A.h, dst, after, next_slot))) break;
-				ahead = {true, A.h, dst, after, next_slot};
-				next_slot ^= 1;
-			}
-			double sum = 0.0;
-			if ((rc = finish_attempt(my_slot, &sum))) break;
-			dsm = std::sqrt(sum / n_components);
-			st.err_last = dsm;
-#ifdef CRD_TUNING_BUILD
-			if (std::getenv("CRD_ADAPT_TRACE")) std::fprintf(stderr, "libcrd attempt: t %.17g h %.17g sum %.17g\n", t, A.h, sum);
-#endif
-			if (dsm <= 1.0) break;  // (a NaN fails the test)
-			ahead.live = false;     // a failed step: what was launched ahead of it is void
-			if (!arkode::reject(A, dsm, &nef, o, h_cap, st)) {
-				rc = fail(lead, CRD_ESTATE, arkode::kErrFailure);
-				break;
-			}
-		}
-		if (rc != CRD_OK) break;
-		t_prev = t;
-		arkode::accept(A, dsm, o, h_cap, t, st);
-		steps_this_call++;
-		R.accept(dst, dense);
-	}
-	while (t < tout && rc == CRD_OK && !arkode_method) {
-		// ---- CRD_ADAPT_RK43: the embedded pair and I-controller of rounds 1-2 ----
-		if (st.accepted + st.rejected >= o.max_steps) {
-			rc = fail(lead, CRD_ESTATE, "adaptive integration: max_steps attempts taken before reaching tout");
-			break;
-		}
-		double hh = h;
-		bool clipped = false;
-		if (!dense && (t + hh >= tout || tout - (t + hh) < 1e-12 * std::fabs(tout))) {  // land on tout exactly; absorb a sliver of a last step
-			hh = tout - t;
-			clipped = true;
-		}
-		if (!(hh > 1e-14 * std::fmax(std::fabs(t), 1e-300)) && !(t == 0.0 && hh > 0.0)) {
-			rc = fail(lead, CRD_ESTATE, "adaptive integration: step size underflow");
-			break;
-		}
-		const int dst = R.spare;
-		double sum = 0.0;
-		if ((rc = attempt(hh, dst, &sum))) break;
-		const double err = o.bias * std::sqrt(sum / n_components);
-		st.err_last = err;
-		double eta;
-		if (!(err == err) || std::isinf(err)) eta = o.shrink;  // NaN / inf: the step blew up
-		else if (err <= 0.0) eta = o.growth;
-		else eta = std::fmin(o.growth, std::fmax(o.shrink, o.safety * std::pow(err, -0.25)));
-		if (err <= 1.0) {
-			t_prev = t;
-			t = clipped ? tout : t + hh;
-			R.accept(dst, dense);
-			st.accepted++;
-			if (after_reject) eta = std::fmin(eta, 1.0);  // no growth right after a rejection
-			after_reject = false;
-			if (!clipped || st.accepted == 1) {
-				st.h_last = hh;
-				st.h_min = (st.h_min == 0.0) ? hh : std::fmin(st.h_min, hh);
-				st.h_max = std::fmax(st.h_max, hh);
-			}
-			if (!clipped) h = hh * eta;
-			else h = std::fmax(h, hh * eta);  // a step shortened to hit tout says nothing against the step it replaced
-			h = std::fmin(h, h_cap);
-		} else {
-			st.rejected++;
-			after_reject = true;
-			h = hh * std::fmin(eta, 0.9);
-		}
-	}
-	// No launch outlives the call -- neither a void one (issued ahead of a verdict that then went the other way) nor, on an error exit,
-	// the attempt that was being waited for: their reductions and copies on the second stream still write the slots' scalars.
-	for (int slot = 0; slot < 2; slot++)
-		if (in_flight[slot]) {
-			double ignored;
-			(void)finish_attempt(slot, &ignored);
-		}
-	st.t_internal = t;
-	if (rc == CRD_OK && dense && R.prev >= 0 && t >= tout) {
-		// ARK_NORMAL: the step t_prev -> t has reached or passed tout.  f at both ends, then the cubic Hermite interpolant at tout.
-		if ((rc = rhs_on_planes(cs, n, t_prev, R.prev, crd_ctx::SB)) == CRD_OK && (rc = rhs_on_planes(cs, n, t, R.cur, crd_ctx::ACC)) == CRD_OK &&
-		    (rc = hand_back(t_prev, t)) == CRD_OK)
-			t = tout;
-	} else {  // no dense output (or a zero-length interval, or an error): hand back the state reached
-		for (int k = 0; k < n; k++) arkode::end_of_call(R, false, cs[k]->dense, tout, t_prev, t).apply(cs[k]->plane);
-	}
-	if (arkode_method) {
-		A.live = rc == CRD_OK && lead->dense.pending;
-		for (int k = 1; k < n; k++) cs[k]->ark = A;
-		h = A.hprime;
-	}
-	st.t = t;
-	st.h_next = h;
-	if (stats) *stats = st;
-	return rc;
-}
-
-// With a run recorder open: one sample per call, at tout, of the state handed back (plane Y) -- the ensembles' rule; a call for which
-// there is no room is refused before any work.
-static int integrate_adaptive_recorded(crd_ctx *const *cs, int n, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats)
-{
-	crd_recorder *rec = nullptr;
-	if (int rc = recorder_of_call(cs, n, &rec)) return rc;
-	if (rec)
-		if (int rc = recorder_room(rec, 1)) return rc;
-	if (int rc = integrate_adaptive_impl(cs, n, t0, tout, opt, stats)) return rc;
-	return rec ? recorder_sample(rec, crd_ctx::Y, tout) : CRD_OK;
-}
-
-int crd_integrate_adaptive(crd_ctx *c, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats)
-{
-	if (!c) return CRD_EINVAL;
-	if (c->halo < 0) return fail(c, CRD_ESTATE, "multi-slab context is not wired (crd_comm_attach_local / crd_comm_init_rccl)");
-	if (c->halo == CRD_HALO_LOCAL) return fail(c, CRD_ESTATE, "LOCAL groups integrate through crd_group_integrate_adaptive");
-	crd_ctx *one[1] = {c};
-	return integrate_adaptive_recorded(one, 1, t0, tout, opt, stats);
-}
-
-int crd_group_integrate_adaptive(crd_ctx *const *ctxs, int n, double t0, double tout, const crd_adaptive_options *opt, crd_adaptive_stats *stats)
-{
-	if (int rc = check_group(ctxs, n)) return rc;
-	if (n > 1)
-		for (int k = 0; k < n; k++)
-			if (ctxs[k]->halo != CRD_HALO_LOCAL) return fail(ctxs[0], CRD_ESTATE, "group is not attached");
-	return integrate_adaptive_recorded(ctxs, n, t0, tout, opt, stats);
 }
 
 int crd_plan_launches(crd_ctx *c)

@@ -134,7 +134,7 @@ One RK4(3) attempt (CRD_ADAPT_RK43, fused_item<..., EMBED = 1, ...>)
 The propagated solution is classical RK4 formed by the running accumulators of the plain step (ACC_U / ACC_V stay live beside the
 fifth stage): reference and per-point bound B are "One RK4 step"'s, K_ACC included.  The fifth stage is k5 = f(t + h, y_new) on the
 y_new the lane has just formed (U4 / V4 hold a window of it, K4U / K4V hold k4 itself), its absorbing flag the host's absorb[3],
-decided at t + h like stage 4's (crd_steppers.cpp: launch_attempt).  The device's y_new is within B of the reference's, so
+decided at t + h like stage 4's (crd_adaptive.cpp: launch_attempt).  The device's y_new is within B of the reference's, so
 
     e5 = stage_error(t + h, y_new; dY = B)
 
