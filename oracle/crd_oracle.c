@@ -1,7 +1,8 @@
 /*
  * crd_oracle.c -- CPU restatement of CRDModel's RHS hot path.  TEST INFRASTRUCTURE ONLY (see crd_oracle.h).
  * PARITY: f(), initial conditions, geometry, the one-rank decomposition and exchange are pinned bit for bit against the reference's
- * own compiled code at one rank (oracle/ref_build/, tests/test_refprobe_host.py); the adaptive trajectory and np > 1 remain unpinned
+ * own compiled code at one rank (oracle/ref_build/, tests/test_refprobe_host.py), crd_oracle_decomp and the halo strips against its
+ * runs with two and four ranks (tests/test_refranks_host.py); the adaptive trajectory remains unpinned
  * (crd_oracle.h).  Built with -fno-builtin-sin -fno-builtin-cos: the reference's default build calls sin() and cos(), not sincos().
  *
  * Plain C99 + libm (+ OpenMP for the timed multi-core baseline).  All citations are /root/reference paths.

@@ -7,9 +7,11 @@
  * PARITY: f(), the initial conditions, the geometry (ny truncation, dx, dy), the one-rank decomposition and exchange and the output
  * format are PINNED BIT FOR BIT against the reference's own compiled code at one rank: its four programs (/root/reference/src),
  * compiled unmodified against stand-in headers for SUNDIALS, MPI and Boost.PropertyTree whose ARKode only calls the programs' own
- * f() (oracle/ref_build/), wrote tests/golden/refprobe_*.npz, and tests/test_refprobe_host.py requires this file's bits.  Still
- * UNPINNED, exactly two things: ARKode's adaptive step sequence (oracle/arkode_erk.py restates it from the documentation) and runs
- * with more than one rank.  Beside the pin this restatement is held by (i) an independent numpy restatement
+ * f() (oracle/ref_build/), wrote tests/golden/refprobe_*.npz, and tests/test_refprobe_host.py requires this file's bits.  Its
+ * runs as two and as four rank processes (tests/golden/refranks_*.npz) pin crd_oracle_decomp, the rank order and the halo strips the
+ * same way (tests/test_refranks_host.py); three or more ranks in a direction stay outside, the reference's exchange is not the
+ * periodic halo there.  Still UNPINNED, exactly one thing: ARKode's adaptive step sequence (oracle/arkode_erk.py restates it from
+ * the documentation).  Beside the pin this restatement is held by (i) an independent numpy restatement
  * (oracle/crd_oracle_np.py), (ii) analytic
  * known answers the reference's own code implies (steady states, index-space eigenfunctions), and
  * (iii) the shipped .ini parameter sets under data/, including the one result they state (the Goldbeter kinetics are

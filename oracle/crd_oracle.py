@@ -2,7 +2,8 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the product
 (crdmodel_amd/, libcrd.so) never does.  f(), initial conditions and geometry are pinned bit for bit against the reference's own compiled
-code at one rank (oracle/ref_build/, tests/test_refprobe_host.py); the adaptive trajectory and np > 1 remain unpinned -- see crd_oracle.h.
+code at one rank (oracle/ref_build/, tests/test_refprobe_host.py), decomposition and halo strips at two and four ranks
+(tests/test_refranks_host.py); the adaptive trajectory remains unpinned -- see crd_oracle.h.
 
 State vectors cross this interface in the reference's own layout: AoS [u, v] pairs, theta (i) fastest,
 IDX(i, j) = 2 i + 2 j nxl (/root/reference/src/FHNmodel_torus.cpp:60), i.e. numpy shape (nyl, nxl, 2).

@@ -4,7 +4,7 @@
 
 These vectors come from oracle/crd_oracle.c (the CPU restatement), not from a run of the reference; the restatement itself is
 pinned bit for bit against the reference's own compiled f(), initial conditions and geometry at one rank by the refprobe_*.npz
-fixtures, which oracle/ref_build/make_fixtures.py writes (the adaptive trajectory and np > 1 remain unpinned).  They pin (a) the oracle against
+fixtures, which oracle/ref_build/make_fixtures.py writes (two and four ranks: refranks_*.npz; the adaptive trajectory remains unpinned).  They pin (a) the oracle against
 regressions, (b) the independent numpy restatement, and (c) the HIP path on the GPU box, where the oracle's
 shared library is rebuilt from the committed C source.
 

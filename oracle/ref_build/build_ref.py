@@ -47,6 +47,18 @@ def provenance():
         return json.load(f)
 
 
+def stand_in_hashes():
+    """{path under oracle/ref_build: SHA-256} of every stand-in header as it is now."""
+    headers = sorted(os.path.join(d, f) for d, _, fs in os.walk(os.path.join(HERE, "include")) for f in fs)
+    return {os.path.relpath(h, HERE): sha256(h) for h in headers}
+
+
+def current():
+    """True when oracle/_ref/ is built AND was compiled against the stand-in headers as they are now.  Programs compiled against an
+    earlier mpi.h know one rank only: they ignore CRD_REF_MPI_SIZE, and every rank process of a run writes rank 0's files."""
+    return built() and provenance().get("stand_ins") == stand_in_hashes()
+
+
 def build(ref=None, force=False):
     """Returns the output directory, or None where no reference tree exists."""
     ref = reference_dir(ref)
@@ -54,10 +66,9 @@ def build(ref=None, force=False):
         return None
     cxx = shutil.which(os.environ.get("CXX", "g++")) or "g++"
     version = subprocess.run([cxx, "--version"], capture_output=True, text=True, check=True).stdout.splitlines()[0]
-    headers = sorted(os.path.join(d, f) for d, _, fs in os.walk(os.path.join(HERE, "include")) for f in fs)
     record = {"compiler": version, "flags": {lv: ["-" + lv] + FLAGS for lv in LEVELS},
               "sources": {p + ".cpp": sha256(os.path.join(ref, "src", p + ".cpp")) for p in PROGRAMS},
-              "stand_ins": {os.path.relpath(h, HERE): sha256(h) for h in headers}}
+              "stand_ins": stand_in_hashes()}
     if not force and built() and provenance() == record:
         return OUT
     for lv in LEVELS:

@@ -5,7 +5,8 @@ tests/golden/refprobe_<tag>.npz.
 
 Every case runs with the -O0 and with the -O2 build; the two must write identical bytes.  A fixture holds data only: the ini text,
 the probe records handed to the stand-in ARKode, and the rows and header line the reference wrote (README.md has the schema).
-tests/test_refprobe_host.py regenerates every fixture with this module and requires the committed contents.
+tests/test_refprobe_host.py regenerates every fixture with this module and requires the committed contents.  Run as a script it also
+writes the two- and four-rank fixtures, tests/golden/refranks_<tag>.npz (make_rank_fixtures.py).
 """
 import io
 import itertools
@@ -298,5 +299,7 @@ def make_all(out_dir):
 
 if __name__ == "__main__":
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else GOLDEN
-    for name, size in sorted(make_all(out).items()):
+    from oracle.ref_build import make_rank_fixtures  # the same cases' kin at two and four ranks: refranks_<tag>.npz
+
+    for name, size in sorted(make_all(out).items()) + sorted(make_rank_fixtures.make_all(out).items()):
         print("%8d  %s" % (size, name))

@@ -33,10 +33,13 @@ def params(fx, precision):
     return p
 
 
-def check_against_rows(case, got, row, fx, t, y, bounded):
+def check_against_rows(case, got, row, fx, t, y, bounded, cut=None):
     """|got - the reference's row| <= bound + |row - the wide reference| per point and field: the kernel's distance from the wide value
-    plus the reference program's own (which tests/test_refprobe_host.py holds inside the fp64 bound)."""
+    plus the reference program's own (which tests/test_refprobe_host.py holds inside the fp64 bound).  cut: got, row and bounded
+    are a block of the grid and cut(whole) takes that block (tests/test_gpu_refranks.py); y is the whole state either way."""
     wide = eb.rhs_bound(fx.op, t, y, "f64")[0]
+    if cut is not None:
+        wide = cut(wide)
     worst = []
     for f, b in ((0, bounded[1]), (1, bounded[2])):
         err = np.abs(got[..., f].astype(np.longdouble) - row[..., f])

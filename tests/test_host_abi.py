@@ -351,7 +351,9 @@ int main(void) {
 def test_block_decomposition_follows_setupdecomp(tmp_path):
     """The reference's 2-D layout: MPI_Dims_create(np, 2) as SetupDecomp calls it
     (src/FHNmodel_torus.cpp:724-728), block extents (:750-753) against the oracle's restatement of the same lines, the initial
-    conditions of a block = the block of the whole field, and the subdomain header of a block's files."""
+    conditions of a block = the block of the whole field, and the subdomain header of a block's files.  (Against two- and four-rank
+    runs of the reference's own compiled code: tests/test_refranks_host.py, which also shows the one rule for which a block's initial
+    conditions are NOT the block of the whole field -- rand(), not among the four rules below.)"""
     assert [crd.dims_create(n) for n in (1, 2, 3, 4, 6, 7, 8, 9, 12, 16)] == [(1, 1), (2, 1), (3, 1), (2, 2), (3, 2), (7, 1), (4, 2), (3, 3), (4, 3), (4, 4)]
     rng = np.random.default_rng(11)
     for _ in range(60):

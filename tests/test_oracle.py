@@ -2,7 +2,8 @@
 known answers the reference's code implies, and decomposition invariance (what MPI delivers at np in {1,2,4}).
 
 The pin against the reference's own compiled code (f(), initial conditions, geometry, one-rank exchange, output format: bit for bit) is
-tests/test_refprobe_host.py; the adaptive trajectory and np > 1 remain unpinned."""
+tests/test_refprobe_host.py, the pin against its runs with two and four ranks tests/test_refranks_host.py; the adaptive trajectory
+remains unpinned."""
 import numpy as np
 import pytest
 

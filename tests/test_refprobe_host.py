@@ -6,7 +6,8 @@ lines, fixed-step RK4 runs through their f(), and two complete run directories. 
 also handed arrays with one value moved by one ulp at (0, 0), at the theta seam column, in an absorbing row and at the last point,
 and has to fail.  Problem parameters always go ini text -> crd.load_ini -> crd_params -> oracle problem (make_fixtures.load).
 
-Not pinned here, and said so wherever the project speaks of parity: ARKode's adaptive step sequence, and runs with more than one rank.
+Runs with two and four ranks: tests/test_refranks_host.py.  Not pinned, and said so wherever the project speaks of parity: ARKode's
+adaptive step sequence.
 """
 import ctypes as C
 import json
