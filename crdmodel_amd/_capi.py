@@ -136,10 +136,29 @@ class LsolveStats(C.Structure):
                 ("r_norm", C.c_double), ("res_norm", C.c_double)]
 
 
+class BicgstabOptions(C.Structure):
+    """crd_bicgstab_options"""
+
+    _fields_ = [("part", C.c_int32), ("precondition", C.c_int32), ("max_iters", C.c_int32), ("guess", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
+                ("psolve", PsolveOptions)]
+
+
+class BicgstabStats(C.Structure):
+    """crd_bicgstab_stats"""
+
+    _fields_ = [("converged", C.c_int32), ("iterations", C.c_int32), ("half_exit", C.c_int32), ("matvecs", C.c_int32), ("psolves", C.c_int32), ("breakdown", C.c_int32),
+                ("r_norm", C.c_double), ("res_norm", C.c_double), ("true_res_norm", C.c_double)]
+
+
+BICGSTAB_BREAKDOWNS = {"none": 0, "d": 1, "tt": 2, "omega": 3, "rho": 4}  # CRD_BICGSTAB_BREAKDOWN_*
+BICGSTAB_KERNELS = {"apply_dot": 0, "apply_dot2": 1, "s_update": 2, "xr_update": 3, "p_update": 4, "x_half": 5}  # CRD_BICGSTAB_KERNEL_*
+IMEX_SOLVERS = {"gmres": 0, "bicgstab": 1, "bicgstab-warm": 2}  # CRD_IMEX_SOLVER_*
+
+
 class ImexOptions(C.Structure):
     """crd_imex_options"""
 
-    _fields_ = [("scheme", C.c_int32), ("reserved", C.c_int32), ("lsolve", LsolveOptions)]
+    _fields_ = [("scheme", C.c_int32), ("solver", C.c_int32), ("lsolve", LsolveOptions)]
 
 
 class ImexStats(C.Structure):
@@ -231,6 +250,11 @@ _SIGNATURES = {
     "crd_lsolve_device": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(LsolveOptions), _vp, _vp, _vp, C.POINTER(LsolveStats)]),
     "crd_lsolve_host": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(LsolveOptions), _vp, _vp, _vp, C.POINTER(LsolveStats)]),
     "crd_krylov_probe_dots": (C.c_int, [_vp, _vp, C.c_int, _vp, C.POINTER(C.c_double)]),
+    "crd_bicgstab_defaults": (C.c_int, [C.POINTER(BicgstabOptions)]),
+    "crd_bicgstab_info": (C.c_int, [_vp, C.POINTER(BicgstabOptions), C.POINTER(C.c_int64)]),
+    "crd_bicgstab_device": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(BicgstabOptions), _vp, _vp, _vp, C.POINTER(BicgstabStats)]),
+    "crd_bicgstab_host": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(BicgstabOptions), _vp, _vp, _vp, C.POINTER(BicgstabStats)]),
+    "crd_bicgstab_probe": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_double), _vp, _vp, C.POINTER(C.c_double)]),
     "crd_imex_defaults": (C.c_int, [C.POINTER(ImexOptions)]),
     "crd_imex_info": (C.c_int, [_vp, C.POINTER(ImexOptions), C.POINTER(C.c_int64)]),
     "crd_step_imex": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64, C.POINTER(ImexOptions), C.POINTER(ImexStats)]),

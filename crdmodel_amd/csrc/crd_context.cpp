@@ -288,6 +288,7 @@ void crd_destroy(crd_ctx *c)
 	psolve_release(c);
 	lsolve_release(c);
 	imex_release(c);
+	bicgstab_release(c);
 	if (c->scalar_host) (void)hipHostFree(c->scalar_host);
 	for (void *q : {c->cE, c->cWn, c->cP, c->brow, c->stage_in, c->stage_out, c->stage_v, c->ghost_lo, c->ghost_hi, c->edge_lo, c->edge_hi, (void *)c->scalar_dev,
 	                (void *)c->err_partials, c->ghost_col[0], c->ghost_col[1], c->edge_col[0], c->edge_col[1]})

@@ -104,6 +104,7 @@ namespace crd {
 struct PsolveWorkspace;  // crd_multigrid.cpp
 struct LsolveWorkspace;  // crd_krylov.cpp
 struct ImexWorkspace;    // crd_imex.cpp
+struct BicgstabWorkspace;  // crd_bicgstab.cpp
 }
 
 struct crd_ctx {
@@ -130,6 +131,7 @@ struct crd_ctx {
 	crd::PsolveWorkspace *psolve = nullptr;  // levels of crd_psolve_*: planes and coefficient tables (lazy, crd_multigrid.cpp)
 	crd::LsolveWorkspace *lsolve = nullptr;  // basis, work vectors and scalars of crd_lsolve_* (lazy, crd_krylov.cpp)
 	crd::ImexWorkspace *imex = nullptr;      // the step's vectors of crd_step_imex (lazy, crd_imex.cpp)
+	crd::BicgstabWorkspace *bicgstab = nullptr;  // work vectors and scalars of crd_bicgstab_* (lazy, crd_bicgstab.cpp)
 	void *ghost_lo = nullptr, *ghost_hi = nullptr;   // var0 of rows -1 / nyl for the AoS RHS (multi-slab)
 	void *edge_lo = nullptr, *edge_hi = nullptr;     // var0 of rows 0 / nyl-1 packed from an AoS vector
 	// theta-blocks (d0 > 1): var0 of the columns beside the block (ghost) and of its own first / last column (edge), nyl reals each,
@@ -239,6 +241,7 @@ int check_group(crd_ctx *const *ctxs, int n);
 void psolve_release(crd_ctx *c);  // crd_multigrid.cpp: frees the workspace of crd_psolve_* (crd_destroy)
 void lsolve_release(crd_ctx *c);  // crd_krylov.cpp: likewise the workspace of crd_lsolve_*
 void imex_release(crd_ctx *c);    // crd_imex.cpp: likewise the workspace of crd_step_imex
+void bicgstab_release(crd_ctx *c);  // crd_bicgstab.cpp: likewise the workspace of crd_bicgstab_*
 
 // crd_halo.cpp: fill ghost rows [-depth, 0) and [nyl, nyl + depth) of plane `plane_index` from the ring neighbours, on the comm streams
 int exchange_stage_input(crd_ctx *const *cs, int n, int plane_index, int depth, bool with_v);

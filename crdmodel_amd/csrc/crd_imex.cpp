@@ -1,6 +1,6 @@
 // crd_imex.cpp -- crd_step_imex (include/crd.h): IMEX additive Runge-Kutta steps with the diffusion part implicit.  This file owns the
-// step's vectors, kept on the context, and the order of launches: f_D (crd_rhs_part_device), the linear solve (crd_lsolve_device) and
-// the stage close (crd_imex.hip) that carries everything else.  The schemes are crd_imex_tables.h's.  Host code only.
+// step's vectors, kept on the context, and the order of launches: f_D (crd_rhs_part_device), the linear solve (crd_lsolve_device, or
+// crd_bicgstab_device where the options ask for it) and the stage close (crd_imex.hip) that carries everything else.  The schemes are crd_imex_tables.h's.  Host code only.
 #include <cmath>
 
 #include "crd_ctx.h"
@@ -67,16 +67,40 @@ int ensure_workspace(crd_ctx *c, int stages)
 	return CRD_OK;
 }
 
+// the BiCGStab options that `lsolve` stands for (restart is not read)
+crd_bicgstab_options bicgstab_options(const crd_lsolve_options &l, int guess)
+{
+	crd_bicgstab_options b;
+	b.part = l.part;
+	b.precondition = l.precondition;
+	b.max_iters = l.max_iters;
+	b.guess = guess;
+	b.rtol = l.rtol;
+	b.atol = l.atol;
+	b.psolve = l.psolve;
+	return b;
+}
+
+// the chosen solver's own check of its options and of the context, and its workspace
+int solver_info(crd_ctx *c, const crd_imex_options &o, int64_t *bytes)
+{
+	if (o.solver == CRD_IMEX_SOLVER_GMRES) return crd_lsolve_info(c, &o.lsolve, bytes);
+	const crd_bicgstab_options b = bicgstab_options(o.lsolve, 0);
+	return crd_bicgstab_info(c, &b, bytes);
+}
+
 // What the call refuses before any device work; *o the options it runs with, *T their scheme.
 int check_call(crd_ctx *c, double t0, double dt, int64_t nsteps, const crd_imex_options *opt, crd_imex_options *o, imex::Tableau *T)
 {
 	if (opt) *o = *opt;
 	else (void)crd_imex_defaults(o);
 	if (!imex::tableau(o->scheme, T)) return fail(c, CRD_EINVAL, "imex: scheme must be CRD_IMEX_EULER, CRD_IMEX_ARS222 or CRD_IMEX_ARS443");
+	if (o->solver != CRD_IMEX_SOLVER_GMRES && o->solver != CRD_IMEX_SOLVER_BICGSTAB && o->solver != CRD_IMEX_SOLVER_BICGSTAB_WARM)
+		return fail(c, CRD_EINVAL, "imex: solver must be CRD_IMEX_SOLVER_GMRES, CRD_IMEX_SOLVER_BICGSTAB or CRD_IMEX_SOLVER_BICGSTAB_WARM");
 	if (o->lsolve.part != CRD_PART_DIFFUSION) return fail(c, CRD_EINVAL, "imex: lsolve.part must be CRD_PART_DIFFUSION (the implicit part is the diffusion operator)");
 	if (!(dt > 0.0) || !std::isfinite(dt) || !std::isfinite(t0)) return fail(c, CRD_EINVAL, "imex: dt must be positive and finite, t0 finite");
 	if (nsteps < 0) return fail(c, CRD_EINVAL, "imex: nsteps must not be negative");
-	if (int rc = crd_lsolve_info(c, &o->lsolve, nullptr)) {  // its options, and the contexts it refuses: several slabs, theta-blocks
+	if (int rc = solver_info(c, *o, nullptr)) {  // its options, and the contexts it refuses: several slabs, theta-blocks
 		const std::string why = c->err;
 		return fail(c, rc, "imex: " + why);
 	}
@@ -92,6 +116,7 @@ struct Stepper {
 	crd_imex_stats st{};
 	ImexWorkspace *w = nullptr;
 	bool f32 = false;
+	const void *last_k = nullptr;  // the k of the solve before (CRD_IMEX_SOLVER_BICGSTAB_WARM starts the next one from it)
 
 	int absorb_at(double t) const { return absorbing(c, t) && !c->desc.just_diffusion ? 1 : 0; }
 
@@ -146,13 +171,27 @@ struct Stepper {
 			const double ti = t + T.c[i] * dt;
 			void *r = w->FR[T.stages];
 			if (int rc = crd_rhs_part_device(c, ti, CRD_PART_DIFFUSION, w->R, r)) return rc;
-			crd_lsolve_stats ls{};
-			if (int rc = crd_lsolve_device(c, ti, hg, &o.lsolve, nullptr, r, w->k[i], &ls)) return rc;
+			// what the stage's solve reports: {converged, iterations, ||r||, its residual}
+			int converged = 0, iterations = 0;
+			double r_norm = 0.0, res_norm = 0.0;
+			if (o.solver == CRD_IMEX_SOLVER_GMRES) {
+				crd_lsolve_stats ls{};
+				if (int rc = crd_lsolve_device(c, ti, hg, &o.lsolve, nullptr, r, w->k[i], &ls)) return rc;
+				converged = ls.converged, iterations = ls.iterations, r_norm = ls.r_norm, res_norm = ls.res_norm;
+			} else {
+				const bool warm = o.solver == CRD_IMEX_SOLVER_BICGSTAB_WARM && last_k;
+				if (warm && last_k != w->k[i]) HIP_TRY(c, hipMemcpyAsync(w->k[i], last_k, vector_bytes(c), hipMemcpyDeviceToDevice, c->compute));
+				const crd_bicgstab_options b = bicgstab_options(o.lsolve, warm ? 1 : 0);
+				crd_bicgstab_stats bs{};
+				if (int rc = crd_bicgstab_device(c, ti, hg, &b, nullptr, r, w->k[i], &bs)) return rc;
+				converged = bs.converged, iterations = bs.iterations, r_norm = bs.r_norm, res_norm = bs.true_res_norm;
+				last_k = w->k[i];
+			}
 			st.solves++;
-			st.iterations += ls.iterations;
-			if (ls.iterations > st.max_iterations) st.max_iterations = ls.iterations;
-			if (ls.r_norm > 0.0 && !(ls.res_norm / ls.r_norm <= st.worst_residual)) st.worst_residual = ls.res_norm / ls.r_norm;
-			if (!ls.converged) return stopped(n, i, "the linear solve did not converge in " + std::to_string(ls.iterations) + " iterations");
+			st.iterations += iterations;
+			if (iterations > st.max_iterations) st.max_iterations = iterations;
+			if (r_norm > 0.0 && !(res_norm / r_norm <= st.worst_residual)) st.worst_residual = res_norm / r_norm;
+			if (!converged) return stopped(n, i, "the linear solve did not converge in " + std::to_string(iterations) + " iterations");
 			if (int rc = close(i, ti)) return rc;
 		}
 		double *sink = c->scalar_sink();
@@ -204,7 +243,7 @@ int crd_imex_defaults(crd_imex_options *opt)
 {
 	if (!opt) return CRD_EINVAL;
 	opt->scheme = CRD_IMEX_ARS222;
-	opt->reserved = 0;
+	opt->solver = CRD_IMEX_SOLVER_GMRES;
 	return crd_lsolve_defaults(&opt->lsolve);
 }
 
@@ -215,7 +254,7 @@ int crd_imex_info(crd_ctx *c, const crd_imex_options *opt, int64_t *bytes)
 	imex::Tableau T;
 	if (int rc = check_call(c, 0.0, 1.0, 0, opt, &o, &T)) return rc;
 	int64_t solve = 0;
-	if (int rc = crd_lsolve_info(c, &o.lsolve, &solve)) return rc;
+	if (int rc = solver_info(c, o, &solve)) return rc;
 	if (bytes) *bytes = (int64_t)workspace_bytes(c, T.stages) + solve;
 	return CRD_OK;
 }

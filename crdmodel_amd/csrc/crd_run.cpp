@@ -5,6 +5,7 @@
 // they do.  Time integration is fixed-step RK4 on the GPU (libcrd) by default; --adaptive runs the reference's integrator,
 // ARKode's default explicit pair and controller restated (CRD_ADAPT_ARKODE), --adaptive-rk43 the RK4(3) pair of earlier rounds,
 // --imex euler|ars222|ars443 IMEX steps with the diffusion part implicit at the run's fixed dt (crd_step_imex; a lone single slab).
+// --imex-solver gmres|bicgstab|bicgstab-warm  the linear solver of its stages (CRD_IMEX_SOLVER_*; only with --imex).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -601,6 +602,7 @@ int step_interval(const Options &o, const crd_run_config &cfg, const Cadence &c,
 		crd_imex_options io;
 		crd_imex_defaults(&io);
 		io.scheme = o.imex;
+		if (o.imex_solver >= 0) io.solver = o.imex_solver;
 		crd_imex_stats is{};
 		rc = crd_step_imex(run->ctx[0], t, c.dt, c.steps_per_output, &io, &is);
 		tally->steps_taken += is.steps;
@@ -725,8 +727,8 @@ void rate_summary(const Options &o, const crd_run_config &cfg, const crd_grid &g
 	if (cfg.adaptive) std::cout << "\n   steps = " << tally.adaptive_steps << " (+" << tally.adaptive_rejected << " rejected)";
 	if (o.imex >= 0 && steps_taken > 0 && stepping_s > 0.0) {
 		char line[256];
-		std::snprintf(line, sizeof line, "\n   rate: %lld IMEX steps in %.6f s of stepping = %.1f steps/s; %lld linear solves, %lld GMRES iterations", steps_taken, stepping_s,
-		              (double)steps_taken / stepping_s, tally.imex_solves, tally.imex_iterations);
+		std::snprintf(line, sizeof line, "\n   rate: %lld IMEX steps in %.6f s of stepping = %.1f steps/s; %lld linear solves, %lld %s iterations", steps_taken, stepping_s,
+		              (double)steps_taken / stepping_s, tally.imex_solves, tally.imex_iterations, o.imex_solver > CRD_IMEX_SOLVER_GMRES ? "BiCGStab" : "GMRES");
 		std::cout << line;
 	} else if (steps_taken > 0 && stepping_s > 0.0) {
 		// compulsory-byte model of a step: both fields read once and written once (the one-launch stepper's traffic; the four

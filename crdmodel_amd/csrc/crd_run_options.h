@@ -48,6 +48,9 @@ struct Options {
 	// --imex euler|ars222|ars443: a lone single-slab run stepped by crd_step_imex (CRD_IMEX_*) at the run's fixed dt; -1: not given.
 	// (Not in the usage text, whose bytes the recorded refusals of tests/golden/driver_refusals.json pin: README.md and INTEGRATION.md name it.)
 	int imex = -1;
+	// --imex-solver gmres|bicgstab|bicgstab-warm: the linear solver of every stage (CRD_IMEX_SOLVER_*); valid only with --imex; -1: not
+	// given, crd_imex_defaults' (GMRES).  Not in the usage text either, for the same reason.
+	int imex_solver = -1;
 };
 
 [[noreturn]] inline void usage(const char *argv0, bool alias)
@@ -246,6 +249,7 @@ inline void check_ensemble_options(const Options &o)
 // ever.  What the ini adds is check_imex_config's (crd_run.cpp).
 inline void check_imex_options(const Options &o)
 {
+	if (o.imex < 0 && o.imex_solver >= 0) usage_error("--imex-solver chooses the linear solver of an IMEX run: only with --imex");
 	if (o.imex < 0) return;
 	if (!o.ensemble.empty()) usage_error("--imex steps a lone single-slab run: not with --ensemble");
 	if (o.gpus > 1) usage_error("--imex steps a lone single-slab run: not with --gpus " + std::to_string(o.gpus));
@@ -313,6 +317,10 @@ inline void parse_options(int argc, char *argv[], Options *out)
 			const std::string v = next();
 			o.imex = v == "euler" ? CRD_IMEX_EULER : v == "ars222" ? CRD_IMEX_ARS222 : v == "ars443" ? CRD_IMEX_ARS443 : -1;
 			if (o.imex < 0) usage_error("--imex takes euler, ars222 or ars443 (got '" + v + "')");
+		} else if (s == "--imex-solver") {
+			const std::string v = next();
+			o.imex_solver = v == "gmres" ? CRD_IMEX_SOLVER_GMRES : v == "bicgstab" ? CRD_IMEX_SOLVER_BICGSTAB : v == "bicgstab-warm" ? CRD_IMEX_SOLVER_BICGSTAB_WARM : -1;
+			if (o.imex_solver < 0) usage_error("--imex-solver takes gmres, bicgstab or bicgstab-warm (got '" + v + "')");
 		} else if (s == "--decomp") {
 			const std::string v = next();
 			if (v == "mpi") o.decomp_mpi = true;

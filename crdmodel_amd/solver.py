@@ -332,6 +332,34 @@ class Slab:
         self._check(lib().crd_lsolve_info(self._h, C.byref(opt), C.byref(nbytes)), "crd_lsolve_info")
         return nbytes.value
 
+    @classmethod
+    def _bicgstab_options(cls, part="diffusion", precondition=True, max_iters=200, guess=False, rtol=1e-8, atol=0.0, **psolve_options):
+        opt = capi.BicgstabOptions()
+        opt.part, opt.precondition, opt.max_iters, opt.guess, opt.rtol, opt.atol = _part(part), int(precondition), max_iters, int(guess), rtol, atol
+        opt.psolve = cls._psolve_options(**dict(dict(pre=2, post=2, coarse=8, max_levels=16, omega=0.8), **psolve_options))
+        return opt
+
+    def lsolve_bicgstab(self, t, gamma, r, y=None, guess=None, part="diffusion", precondition=True, max_iters=200, rtol=1e-8, atol=0.0, **psolve_options):
+        """(z, stats) of (I - gamma J_part(t, y)) z = r by right-preconditioned BiCGStab on the device (crd_bicgstab_host): a short
+        recurrence with eight work vectors, one iteration two matvecs and two cycles.  guess: a vector laid out like r to start from
+        (None: from zero).  stats is the crd_bicgstab_stats structure: converged, iterations, half_exit, matvecs, psolves, breakdown,
+        r_norm, res_norm (the recurrence's), true_res_norm (||r - A z|| by one more matvec).  Neither max_iters nor a breakdown is an
+        error: stats.converged is 0 and z the last consistent iterate."""
+        r = self._vector(r)
+        y = None if y is None else self._vector(y)
+        z = np.empty_like(r) if guess is None else np.array(self._vector(guess), copy=True)
+        st = capi.BicgstabStats()
+        opt = self._bicgstab_options(part, precondition, max_iters, guess is not None, rtol, atol, **psolve_options)
+        self._check(lib().crd_bicgstab_host(self._h, t, gamma, C.byref(opt), None if y is None else y.ctypes.data, r.ctypes.data, z.ctypes.data, C.byref(st)),
+                    "crd_bicgstab_host")
+        return z, st
+
+    def lsolve_bicgstab_info(self, part="diffusion", precondition=True, max_iters=200, rtol=1e-8, atol=0.0, **psolve_options):
+        """Device bytes of the workspace Slab.lsolve_bicgstab keeps on the context (crd_bicgstab_info)."""
+        opt, nbytes = self._bicgstab_options(part, precondition, max_iters, False, rtol, atol, **psolve_options), C.c_int64()
+        self._check(lib().crd_bicgstab_info(self._h, C.byref(opt), C.byref(nbytes)), "crd_bicgstab_info")
+        return nbytes.value
+
     # -- time stepping -----------------------------------------------------------------------------------------
     def set_stepper(self, stepper):
         s = STEPPERS[stepper] if isinstance(stepper, str) else stepper
@@ -342,18 +370,20 @@ class Slab:
         if sync:
             self.synchronize()
 
-    def _imex_options(self, scheme, lsolve_options):
+    def _imex_options(self, scheme, lsolve_options, solver="gmres"):
         opt = capi.ImexOptions()
         opt.scheme = capi.IMEX_SCHEMES[scheme] if isinstance(scheme, str) else scheme
+        opt.solver = capi.IMEX_SOLVERS[solver] if isinstance(solver, str) else solver
         opt.lsolve = self._lsolve_options(**lsolve_options)
         return opt
 
-    def step_imex(self, t0, dt, nsteps, scheme="ars222", **lsolve_options):
+    def step_imex(self, t0, dt, nsteps, scheme="ars222", solver="gmres", **lsolve_options):
         """nsteps IMEX steps of size dt on the resident state, the diffusion part implicit (crd_step_imex): scheme "euler", "ars222" or
-        "ars443" (or a CRD_IMEX_* value); lsolve_options are Slab.lsolve's and reach every stage's solve.  Returns the crd_imex_stats
+        "ars443" (or a CRD_IMEX_* value); solver "gmres", "bicgstab" or "bicgstab-warm" (each stage's solve started from the one before;
+        or a CRD_IMEX_SOLVER_* value); lsolve_options are Slab.lsolve's and reach every stage's solve.  Returns the crd_imex_stats
         structure: steps, t, solves, iterations, max_iterations, failed_step, failed_stage, worst_residual, max_abs_u.  A solve that
         does not converge raises CrdError (CRD_ESTATE) with that structure as its `stats`; the state is the last completed step's."""
-        opt, st = self._imex_options(scheme, lsolve_options), capi.ImexStats()
+        opt, st = self._imex_options(scheme, lsolve_options, solver), capi.ImexStats()
         rc = lib().crd_step_imex(self._h, t0, dt, nsteps, C.byref(opt), C.byref(st))
         if rc != capi.OK:
             err = CrdError(rc, "crd_step_imex", lib().crd_last_error(self._h).decode())
@@ -361,9 +391,9 @@ class Slab:
             raise err
         return st
 
-    def imex_info(self, scheme="ars222", **lsolve_options):
-        """Device bytes crd_step_imex with these options keeps on the context, the solve's workspace included (crd_imex_info)."""
-        opt, nbytes = self._imex_options(scheme, lsolve_options), C.c_int64()
+    def imex_info(self, scheme="ars222", solver="gmres", **lsolve_options):
+        """Device bytes crd_step_imex with these options keeps on the context, the chosen solver's workspace included (crd_imex_info)."""
+        opt, nbytes = self._imex_options(scheme, lsolve_options, solver), C.c_int64()
         self._check(lib().crd_imex_info(self._h, C.byref(opt), C.byref(nbytes)), "crd_imex_info")
         return nbytes.value
 

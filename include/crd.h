@@ -390,6 +390,81 @@ int crd_lsolve_host(crd_ctx *ctx, double t, double gamma, const crd_lsolve_optio
  * vectors: `count` AoS vectors back to back, w: one, all HOST memory in the context's precision; out: `count` doubles. */
 int crd_krylov_probe_dots(crd_ctx *ctx, const void *vectors, int count, const void *w, double *out);
 
+/* The same system by BiCGStab: (I - gamma J_part(t, y)) z = r, right-preconditioned, A and M those of crd_lsolve_*.  A short
+ * recurrence: no basis, no orthogonalisation, eight work vectors whatever the iteration count; one iteration is TWO A and TWO M.
+ * tol = rtol ||r|| + atol, ||r|| the 2-norm over the whole vector.  CRD_PART_DIFFUSION runs on var0: var1 of every work vector is +0
+ * and z_var1 = r_var1 bit for bit.
+ *   Start.  x = 0 and res = r (var1 masked), no matvec; with guess = 1: x = the caller's z (DIFFUSION: its var0) and
+ *           res = r - fma(-gamma, J x, x) through one matvec.  rhat = res, rho = <rhat, res>, p = res.  ||res|| <= tol: 0 iterations,
+ *           converged.
+ *   Iteration i = 1 .. max_iters:
+ *      1. phat = M p
+ *      2. v = fma(-gamma, J phat, phat);  d = <rhat, v>
+ *      3. alpha = rho / d
+ *      4. s = fma(-alpha, v, res);  ||s||^2 of the stored s
+ *      5. ||s|| <= tol:  x = fma(alpha, phat, x); half exit, converged
+ *      6. shat = M s
+ *      7. t = fma(-gamma, J shat, shat);  <t, s>, <t, t>
+ *      8. omega = <t, s> / <t, t>
+ *      9. x = fma(omega, shat, fma(alpha, phat, x))
+ *     10. res = fma(-omega, t, s);  ||res||^2 and rho' = <rhat, res> of the stored res
+ *     11. ||res|| <= tol: converged
+ *     12. beta = (rho' / rho) (alpha / omega);  rho = rho'
+ *     13. p = fma(beta, fma(-omega, v, p), res)
+ *   Five fused kernels carry that (crd_bicgstab.hip): 2 and 7 in place over the J v buffer with their dots; 4; 9 - 10 in one pass; 13; 5.
+ *   Scalars: alpha, omega, beta are formed in double on the host from the reductions the device leaves, rounded ONCE to the context's
+ *   precision and passed by value; the same rounded alpha (omega) updates x and the residual.  Vector arithmetic is in the context's
+ *   precision, every multiply-add fused; reductions are in double, per-block partials summed in a fixed order, no atomics: the bits
+ *   repeat from run to run.
+ *   Breakdown: the host looks at every scalar before the kernel that uses it is launched.  A zero or non-finite d (or alpha),
+ *   <t, t>, omega, rho' (or a non-finite beta) ends the call with status 0, converged = 0 and breakdown = CRD_BICGSTAB_BREAKDOWN_*;
+ *   z is the last consistent iterate -- at <t, t> or omega x = fma(alpha, phat, x) is applied first, since s is its residual
+ *   (half_exit = 1, the iteration counts).  An iteration that breaks down at d does not count.
+ * Reaching max_iters is NOT an error (converged = 0, z the last iterate); gamma == 0 returns z = r; r == 0 returns z = 0; a
+ * non-finite ||r|| returns converged = 0 without an iteration.  No convergence is promised for CRD_PART_FULL where I - gamma J is
+ * indefinite: the recurrences may then end in a breakdown.  Every loop is bounded by max_iters.
+ * After the loop one more matvec forms ||r - A z|| (counted in matvecs): true_res_norm.  res_norm stays the recurrence's own, and
+ * converged is judged on the recurrence.
+ * opt == NULL: the defaults (DIFFUSION, preconditioned, max_iters 200, guess 0, rtol 1e-8, atol 0, crd_psolve_defaults).
+ * Refusals and contexts: those of crd_lsolve_* (there is no restart), and guess outside {0, 1}.  Workspace: eight vectors (res, rhat,
+ * p, v, s, t, phat, shat), the partials and a page-locked scalar block -- its own allocation, never that of crd_lsolve_*, made by the
+ * first call, freed by crd_destroy; crd_bicgstab_info reports its device bytes.  The call WAITS for its work.
+ * The device vectors of crd_bicgstab_device (y, r, z) must be 16-byte aligned, as hipMalloc returns them: the kernels move 16 bytes
+ * per thread.
+ * stats (may be NULL): iterations completed (each two matvecs, a half exit one); half_exit = 1 when z is the iterate of step 5;
+ * matvecs / psolves = launches of J v / of the cycle. */
+enum { CRD_BICGSTAB_BREAKDOWN_NONE = 0, CRD_BICGSTAB_BREAKDOWN_D = 1, CRD_BICGSTAB_BREAKDOWN_TT = 2, CRD_BICGSTAB_BREAKDOWN_OMEGA = 3, CRD_BICGSTAB_BREAKDOWN_RHO = 4 };
+typedef struct crd_bicgstab_options {
+	int32_t part;          /* CRD_PART_DIFFUSION (default) or CRD_PART_FULL */
+	int32_t precondition;  /* 1 (default): M = the crd_psolve cycle for I - gamma J_D; 0: none */
+	int32_t max_iters;     /* default 200 */
+	int32_t guess;         /* 0 (default): from x = 0; 1: from the caller's z */
+	double rtol, atol;     /* default 1e-8, 0 */
+	crd_psolve_options psolve;
+} crd_bicgstab_options;
+typedef struct crd_bicgstab_stats {
+	int32_t converged, iterations, half_exit, matvecs, psolves, breakdown;
+	double r_norm, res_norm, true_res_norm;
+} crd_bicgstab_stats;
+int crd_bicgstab_defaults(crd_bicgstab_options *opt);
+int crd_bicgstab_info(crd_ctx *ctx, const crd_bicgstab_options *opt, int64_t *workspace_bytes);
+int crd_bicgstab_device(crd_ctx *ctx, double t, double gamma, const crd_bicgstab_options *opt, const void *y_aos_dev, const void *r_aos_dev, void *z_aos_dev,
+                        crd_bicgstab_stats *stats);
+int crd_bicgstab_host(crd_ctx *ctx, double t, double gamma, const crd_bicgstab_options *opt, const void *y_aos, const void *r_aos, void *z_aos, crd_bicgstab_stats *stats);
+/* For the test suite's gate on each fused kernel alone: runs kernel `kernel` once on HOST vectors in the context's precision, given
+ * back to back in `in`, with `scalars` rounded as the solve rounds them, and returns its output vectors back to back in `out` and its
+ * reductions in `sums`:
+ *   CRD_BICGSTAB_KERNEL_APPLY_DOT   in jv, x, b       scalars gamma         out fma(-gamma, jv, x)   sums <b, out>
+ *   CRD_BICGSTAB_KERNEL_APPLY_DOT2  in jv, x, b       scalars gamma         out fma(-gamma, jv, x)   sums <out, b>, <out, out>
+ *   CRD_BICGSTAB_KERNEL_S_UPDATE    in v, res         scalars alpha         out s                    sums ||s||^2
+ *   CRD_BICGSTAB_KERNEL_XR_UPDATE   in x, phat, shat, t, s, rhat   scalars alpha, omega   out x, res sums ||res||^2, <rhat, res>
+ *   CRD_BICGSTAB_KERNEL_P_UPDATE    in p, v, res      scalars beta, omega   out p                    no sums
+ *   CRD_BICGSTAB_KERNEL_X_HALF      in x, phat        scalars alpha         out x                    no sums
+ * var0_only (0 / 1) masks var1 of the two apply kernels' output as CRD_PART_DIFFUSION does. */
+enum { CRD_BICGSTAB_KERNEL_APPLY_DOT = 0, CRD_BICGSTAB_KERNEL_APPLY_DOT2 = 1, CRD_BICGSTAB_KERNEL_S_UPDATE = 2, CRD_BICGSTAB_KERNEL_XR_UPDATE = 3,
+       CRD_BICGSTAB_KERNEL_P_UPDATE = 4, CRD_BICGSTAB_KERNEL_X_HALF = 5 };
+int crd_bicgstab_probe(crd_ctx *ctx, int kernel, int var0_only, const double *scalars, const void *in, void *out, double *sums);
+
 /* Fast path that never leaves the GPU: nsteps classical RK4 steps of size dt on the context's resident state,
  * stage k of step n evaluated at t0 + n dt + c_k dt (replaces the ARKode(...) call, src/FHNmodel_torus.cpp:423).
  * Asynchronous; crd_synchronize() waits.  With several slabs every context of the run must make the same call: stepping is
@@ -432,11 +507,18 @@ int crd_step_rk4(crd_ctx *ctx, double t0, double dt, int64_t nsteps);
  * call, kept on the context, freed by crd_destroy; crd_imex_info reports the bytes of both together.
  * stats (may be NULL): steps completed; t = t0 + steps dt; solves and GMRES iterations in total; max_iterations of one solve;
  * failed_step / failed_stage (-1: none); worst_residual = the largest res_norm / r_norm of a solve; max_abs_u = max |var0| of the
- * final state (what crd_state_max_abs reports). */
+ * final state (what crd_state_max_abs reports).
+ * solver: CRD_IMEX_SOLVER_GMRES (the default) is everything above.  CRD_IMEX_SOLVER_BICGSTAB solves every stage with
+ * crd_bicgstab_device instead, from x = 0: `lsolve` then gives part, precondition, max_iters, rtol, atol and psolve, and restart is
+ * not read.  CRD_IMEX_SOLVER_BICGSTAB_WARM starts each stage's solve from the previous stage's k (guess = 1), stage 1 from the
+ * previous step's last k once this call has taken a step, and from x = 0 otherwise.  With either, iterations and max_iterations count
+ * BiCGStab iterations -- each is two matvecs and two cycles -- and worst_residual takes true_res_norm / r_norm.  Any other value:
+ * CRD_EINVAL.  crd_imex_info reports the step's vectors and the chosen solver's workspace alone. */
 enum { CRD_IMEX_EULER = 0, CRD_IMEX_ARS222 = 1, CRD_IMEX_ARS443 = 2 };
+enum { CRD_IMEX_SOLVER_GMRES = 0, CRD_IMEX_SOLVER_BICGSTAB = 1, CRD_IMEX_SOLVER_BICGSTAB_WARM = 2 };
 typedef struct crd_imex_options {
 	int32_t scheme;    /* CRD_IMEX_*; default CRD_IMEX_ARS222 */
-	int32_t reserved;
+	int32_t solver;    /* CRD_IMEX_SOLVER_*; default CRD_IMEX_SOLVER_GMRES */
 	crd_lsolve_options lsolve;  /* crd_lsolve_defaults; part must be CRD_PART_DIFFUSION */
 } crd_imex_options;
 typedef struct crd_imex_stats {

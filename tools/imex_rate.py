@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """What an IMEX step (crd_step_imex) costs on one MI355X, and where it starts to pay against the fixed-step RK4 kernel.
 
-    tools/imex_rate.py measure  > measure.txt                                             (one MI355X; host clock around calls that wait)
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/imex_rate.py workload DIR/closes.json     (a run of its own)
+    tools/imex_rate.py measure [--solver gmres|bicgstab|bicgstab-warm] > measure.txt      (one MI355X; host clock around calls that wait)
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/imex_rate.py workload DIR/closes.json [SOLVER]    (a run of its own)
     tools/imex_rate.py report DIR >> measure.txt                                          (no GPU: reads the trace)
     -> profiles/imex/rate.txt, with a reading written under it
 
@@ -15,7 +15,8 @@ measure: FHN torus N x N fp64 (N = 8192; env N), the reference's initial wave.
     Break-even: the multiple at which an IMEX step costs what the RK4 steps covering the same time cost.
 workload / report: two steps of ars222 and of ars443 at 1000 x crd_stable_dt under a kernel trace; the stage-close launches are matched, in
   order, with the vector crossings counted from crd_imex.hip for their stage, and priced at the device's copy rate
-  (profiles/hbm_streams.json: copy_16B_per_lane_gbs, the yardstick of profiles/krylov/rate.txt)."""
+  (profiles/hbm_streams.json: copy_16B_per_lane_gbs, the yardstick of profiles/krylov/rate.txt).  With SOLVER bicgstab or bicgstab-warm
+  the same trace holds the fused kernels of crd_bicgstab.hip: the report prices each at its counted crossings beside the closes."""
 import csv
 import ctypes as C
 import glob
@@ -54,7 +55,7 @@ def problem():
     return crd, p, y0
 
 
-def measure():
+def measure(solver="gmres"):
     import torch
 
     crd, p, y0 = problem()
@@ -64,7 +65,7 @@ def measure():
     sd = crd.stable_dt(p)
     vector = 2.0 * N * N * 8
     copy_gbs = json.load(open(os.path.join(ROOT, "profiles", "hbm_streams.json")))["copy_16B_per_lane_gbs"]
-    print("# tools/imex_rate.py measure: FHN torus %d x %d fp64, %s, kernel table %s; crd_stable_dt = %.6g; vector %.0f MB" % (N, N, torch.cuda.get_device_name(0), crd.kernel_table_digest(), sd, vector / 2 ** 20))
+    print("# tools/imex_rate.py measure --solver %s: FHN torus %d x %d fp64, %s, kernel table %s; crd_stable_dt = %.6g; vector %.0f MB" % (solver, N, N, torch.cuda.get_device_name(0), crd.kernel_table_digest(), sd, vector / 2 ** 20))
     with crd.Slab(p) as s:
         s.upload(y0)
         s.plan_launches()
@@ -76,7 +77,7 @@ def measure():
         rk4_ms = (time.perf_counter() - t0) * 1e3 / STEPS
         plan = s.launch_plan()
         print("rk4: %.4f ms per step of crd_stable_dt (%d steps, %d steps per launch): %.4g ms per unit of simulated time" % (rk4_ms, STEPS, plan["steps_per_launch"], rk4_ms / sd), flush=True)
-        print("imex workspace: ars222 %.0f MB, ars443 %.0f MB (the solve's %.0f MB included)" % (s.imex_info("ars222") / 2 ** 20, s.imex_info("ars443") / 2 ** 20, s.lsolve_info() / 2 ** 20))
+        print("imex workspace: ars222 %.0f MB, ars443 %.0f MB (the solve's %.0f MB included)" % (s.imex_info("ars222", solver=solver) / 2 ** 20, s.imex_info("ars443", solver=solver) / 2 ** 20, (s.lsolve_info() if solver == "gmres" else s.lsolve_bicgstab_info()) / 2 ** 20))
         r = torch.randn((N, N, 2), dtype=torch.float64, device="cuda")
         out = torch.empty_like(r)
         best = []
@@ -96,14 +97,14 @@ def measure():
             for m in multiples:
                 dt = m * sd
                 s.upload(y0)
-                s.step_imex(0.0, dt, 1, scheme)
+                s.step_imex(0.0, dt, 1, scheme, solver=solver)
                 t0 = time.perf_counter()
-                st = s.step_imex(dt, dt, IMEX_STEPS, scheme)
+                st = s.step_imex(dt, dt, IMEX_STEPS, scheme, solver=solver)
                 ms = (time.perf_counter() - t0) * 1e3 / IMEX_STEPS
                 per_time = ms / dt
                 rows.append((scheme, m, ms, per_time))
-                print("imex %s at %g x crd_stable_dt (dt = %.4g): %.1f ms per step, %.1f iterations per solve (most %d), worst residual %.2g ||r||, max |u| %.3f; f_D %.1f ms of it; "
-                      "%.4g ms per unit of simulated time = %.2f x RK4's" % (scheme, m, dt, ms, st.iterations / st.solves, st.max_iterations, st.worst_residual, st.max_abs_u, STAGES[scheme] * fd_ms,
+                print("imex %s (%s) at %g x crd_stable_dt (dt = %.4g): %.1f ms per step, %.1f iterations per solve (most %d), worst residual %.2g ||r||, max |u| %.3f; f_D %.1f ms of it; "
+                      "%.4g ms per unit of simulated time = %.2f x RK4's" % (scheme, solver, m, dt, ms, st.iterations / st.solves, st.max_iterations, st.worst_residual, st.max_abs_u, STAGES[scheme] * fd_ms,
                                                                              per_time, per_time / (rk4_ms / sd)), flush=True)
         T = 4000 * sd
         print("time to T = 4000 x crd_stable_dt = %.4g (IMEX: T / dt steps at the measured cost of a step, extrapolated): RK4 %.1f ms; ars222 %s" % (
@@ -115,11 +116,17 @@ def measure():
             q0, q1 = a0 / (m0 * rk4_ms), a1 / (m1 * rk4_ms)
             if q0 > 1 >= q1:
                 even = m0 + (m1 - m0) * (q0 - 1) / (q0 - q1)
-        print("break-even (ars222 against RK4 at crd_stable_dt): %s" % ("%.0f x crd_stable_dt (interpolated between the two multiples around it)" % even if even else
+        print("break-even (ars222, %s, against RK4 at crd_stable_dt): %s" % (solver, "%.0f x crd_stable_dt (interpolated between the two multiples around it)" % even if even else
                                                                         ("below %g x" % ars[0][0] if ars[0][1] / (ars[0][0] * rk4_ms) <= 1 else "not reached up to %g x" % ars[-1][0])))
 
 
-def workload(sidecar):
+# vector crossings of the kernels of crd_bicgstab.hip, counted from their loops: reads + writes (start: r in, res, rhat, p out -- or r, x,
+# J x in and one out with a guess and for the true residual: 4 either way)
+BCG_CROSSINGS = {"crd_bcg_apply_dot_kernel": 4, "crd_bcg_s_update_kernel": 3, "crd_bcg_xr_update_kernel": 8, "crd_bcg_p_update_kernel": 4, "crd_bcg_x_half_kernel": 3,
+                 "crd_bcg_start_kernel": 4}
+
+
+def workload(sidecar, solver="gmres"):
     crd, p, y0 = problem()
     sd = crd.stable_dt(p)
     closes = []
@@ -128,11 +135,11 @@ def workload(sidecar):
             dt = TRACE_MULTIPLE * sd
             s.upload(y0)
             for call, steps in ((0, 1), (1, 2)):  # a warm step, then the two that count
-                st = s.step_imex(call * dt, dt, steps, scheme)
+                st = s.step_imex(call * dt, dt, steps, scheme, solver=solver)
                 for _ in range(steps):
                     closes += [dict(scheme=scheme, stage=i, crossings=crossings(scheme, i), warm=call == 0) for i in range(STAGES[scheme] + 1)]
             print("workload %s: %d iterations in %d solves" % (scheme, st.iterations, st.solves), flush=True)
-    json.dump(dict(n=N, closes=closes), open(sidecar, "w"))
+    json.dump(dict(n=N, solver=solver, closes=closes), open(sidecar, "w"))
 
 
 def report(directory):
@@ -166,15 +173,46 @@ def report(directory):
             scheme, stage, cr, cr * vector / 1e9, ms, len(times), " ".join("%.3f" % t for t in times), cr * vector / (ms * 1e-3) / 1e9, ms / at_copy))
     for scheme, ms in sorted(total.items()):
         print("closes of one %s step: %.3f ms" % (scheme, ms))
+    # the kernels of crd_bicgstab.hip, each launch attributed to the stage whose close follows it (the sidecar's list, in order): the
+    # launches of the warm-up steps are left out exactly as their closes are
+    import re
+
+    bcg, at = {}, 0
+    for r in rows:
+        if "crd_imex_close_kernel" in r[name]:
+            at += 1
+            continue
+        kernel = next((k for k in BCG_CROSSINGS if k in r[name]), None)
+        if kernel is None or at >= len(closes) or closes[at]["warm"]:
+            continue
+        label, cr = kernel, BCG_CROSSINGS[kernel]
+        if kernel == "crd_bcg_apply_dot_kernel":
+            m = re.search(r"crd_bcg_apply_dot_kernel<\w+, *(true|false)>|crd_bcg_apply_dot_kernelI[df]Lb([01])E", r[name])
+            if not m:
+                sys.exit("cannot tell the one-dot from the two-dot apply kernel in %r" % r[name])
+            label += " (two dots)" if (m.group(1) == "true" or m.group(2) == "1") else " (one dot)"
+        if kernel == "crd_bcg_start_kernel" and side.get("solver") != "bicgstab":
+            cr = 0  # with a guess the first start of a solve reads three vectors, not one: not priced here
+        bcg.setdefault((label, cr), []).append((int(r[end]) - int(r[start])) / 1e6)
+    for (kernel, cr), times in sorted(bcg.items()):
+        ms = sum(times) / len(times)
+        if cr == 0:
+            print("bicgstab %s: %.3f ms (mean of %d launches), not priced" % (kernel, ms, len(times)))
+            continue
+        at_copy = cr * vector / (copy_gbs * 1e9) * 1e3
+        print("bicgstab %s: %d crossings = %.2f GB, %.3f ms (mean of %d launches, %.3f .. %.3f): %.0f GB/s, %.2f x its time at the copy rate" % (
+            kernel, cr, cr * vector / 1e9, ms, len(times), min(times), max(times), cr * vector / (ms * 1e-3) / 1e9, ms / at_copy))
     timed = [r for r in rows if "crd_imex" not in r[name]]
     print("# the other %d launches of the trace (f_D, and the solves' J_D v, cycles and vector kernels) took %.1f ms in all, warm steps included" % (len(timed), sum((int(r[end]) - int(r[start])) / 1e6 for r in timed)))
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 2 and sys.argv[1] == "measure":
+    if len(sys.argv) == 4 and sys.argv[1] == "measure" and sys.argv[2] == "--solver" and sys.argv[3] in ("gmres", "bicgstab", "bicgstab-warm"):
+        measure(sys.argv[3])
+    elif len(sys.argv) == 2 and sys.argv[1] == "measure":
         measure()
-    elif len(sys.argv) == 3 and sys.argv[1] == "workload":
-        workload(sys.argv[2])
+    elif len(sys.argv) in (3, 4) and sys.argv[1] == "workload":
+        workload(sys.argv[2], *sys.argv[3:])
     elif len(sys.argv) == 3 and sys.argv[1] == "report":
         report(sys.argv[2])
     else:

@@ -4,6 +4,11 @@ J_D v and one V-cycle measured in the same process, and the same system solved t
 the matvec and the cycle on the device and every vector through the host.
 
     tools/lsolve_rate.py > profiles/krylov/rate.txt        (one MI355X)
+    tools/lsolve_rate.py --solver both >> profiles/krylov/rate.txt     (the same, and BiCGStab on the same system in the same process)
+
+--solver gmres (the default) | bicgstab | both.  BiCGStab (crd_bicgstab_device) is timed the same way: one iteration -- two J_D v, two
+cycles, the five fused kernels and four reads of the host -- as T(k + 1) - T(k) at rtol = 0, and a whole solve at rtol 1e-8 (fp32: 1e-5).
+Its fused kernels move 23 vector crossings per iteration (crd_bicgstab.hip).
 
 FHN torus 8192^2 fp64 and fp32 and 4096^2 fp64 (CASES overrides: "8192:f64,8192:f32,4096:f64"), gamma = 2000 x crd_stable_dt, rows free,
 restart 30.  Inner iteration j (the basis holds j + 1 vectors) is timed as T(j + 1) - T(j), T(k) the host's clock around one
@@ -63,7 +68,40 @@ def scipy_solve(s, t, gamma, r, rtol):
     return dt, count[0], info, res
 
 
+def bicgstab_rate(s, n, precision, t, gamma, r, z, parts, vector, copy_gbs):
+    """One BiCGStab iteration at three depths (they cost the same: there is no basis) and a whole solve, on the system GMRES was given."""
+    h = s.handle
+    opt, st = crd.Slab._bicgstab_options(rtol=0.0, max_iters=1), _capi.BicgstabStats()
+
+    def solve(k, rtol=0.0):
+        opt.max_iters, opt.rtol = k, rtol
+        t0 = time.perf_counter()
+        assert L.crd_bicgstab_device(h, t, gamma, C.byref(opt), None, ptr(r), ptr(z), C.byref(st)) == 0
+        return (time.perf_counter() - t0) * 1e3
+
+    solve(2)
+    print("fhn %dx%d %s bicgstab workspace %.0f MB (lsolve: %.0f MB)" % (n, n, precision, s.lsolve_bicgstab_info() / 2 ** 20, s.lsolve_info() / 2 ** 20), flush=True)
+    for k in (1, 5, 10):
+        lo, hi = min(solve(k) for _ in range(REPEATS)), min(solve(k + 1) for _ in range(REPEATS))
+        assert st.iterations == k + 1 and st.breakdown == 0
+        it = hi - lo
+        rest = it - 2 * parts["J_D v"] - 2 * parts["V-cycle"]
+        nbytes = 23 * vector
+        print("fhn %dx%d %s bicgstab iteration %2d: %.3f ms = 2 J_D v %.3f + 2 V-cycles %.3f + the fused kernels and the host's four reads %.3f ms; those move 23 vectors = %.2f GB: %.0f GB/s, "
+              "%.2f x their time at the copy rate" % (n, n, precision, k + 1, it, 2 * parts["J_D v"], 2 * parts["V-cycle"], rest, nbytes / 1e9, nbytes / (rest * 1e-3) / 1e9,
+                                                 rest / (nbytes / (copy_gbs * 1e9) * 1e3)), flush=True)
+    rtol = 1e-8 if precision == "f64" else 1e-5
+    ms = min(solve(200, rtol) for _ in range(REPEATS))
+    halves = 2 * st.iterations - st.half_exit
+    print("fhn %dx%d %s bicgstab solve to rtol %g: %d iterations (%d half-steps, %d matvecs, %d cycles), %.1f ms on the device = %.2f ms per iteration (converged %d, breakdown %d, "
+          "recurrence residual %.3g ||r||, true residual %.3g ||r||)" % (n, n, precision, rtol, st.iterations, halves, st.matvecs, st.psolves, ms, ms / max(st.iterations, 1), st.converged,
+                                                                         st.breakdown, st.res_norm / st.r_norm, st.true_res_norm / st.r_norm), flush=True)
+
+
 def main():
+    solver = sys.argv[sys.argv.index("--solver") + 1] if "--solver" in sys.argv else "gmres"
+    if solver not in ("gmres", "bicgstab", "both"):
+        sys.exit("--solver takes gmres, bicgstab or both")
     copy_gbs = json.load(open(os.path.join(ROOT, "profiles", "hbm_streams.json")))["copy_16B_per_lane_gbs"]
     print("# tools/lsolve_rate.py: inner iteration j = T(j + 1) - T(j), T(k) the host clock around crd_lsolve_device(rtol 0, max_iters k), best of %d; J_D v and the cycle:" % REPEATS)
     print("# %d calls back to back + synchronise, best of %d batches.  %s, kernel table %s" % (BATCH, REPEATS, torch.cuda.get_device_name(0), crd.kernel_table_digest()))
@@ -105,7 +143,7 @@ def main():
                     best.append((time.perf_counter() - t0) * 1e3 / BATCH)
                 parts[name] = min(best)
             print("fhn %dx%d %s J_D v %.4f ms, V-cycle %.4f ms" % (n, n, precision, parts["J_D v"], parts["V-cycle"]), flush=True)
-            for j in DEPTHS:
+            for j in DEPTHS if solver != "bicgstab" else ():
                 lo, hi = min(solve(j) for _ in range(REPEATS)), min(solve(j + 1) for _ in range(REPEATS))
                 assert st.iterations == j + 1 and st.restarts == 0
                 it = hi - lo
@@ -117,7 +155,9 @@ def main():
             # a whole solve at rtol 1e-8 (fp32: 1e-5), on the device and (where asked) through scipy
             rtol = 1e-8 if precision == "f64" else 1e-5
             ms = min(solve(200, rtol) for _ in range(REPEATS))
-            print("fhn %dx%d %s solve to rtol %g: %d iterations, %.1f ms on the device (converged %d, residual %.3g ||r||)" % (n, n, precision, rtol, st.iterations, ms, st.converged, st.res_norm / st.r_norm), flush=True)
+            print("fhn %dx%d %s solve to rtol %g: %d iterations, %.1f ms on the device = %.2f ms per iteration (converged %d, residual %.3g ||r||)" % (n, n, precision, rtol, st.iterations, ms, ms / max(st.iterations, 1), st.converged, st.res_norm / st.r_norm), flush=True)
+            if solver != "gmres":
+                bicgstab_rate(s, n, precision, t, gamma, r, z, parts, vector, copy_gbs)
             if spec in scipy_cases:
                 sec, its, info, res = scipy_solve(s, 1.0, gamma_f, r.cpu().numpy(), rtol)
                 print("fhn %dx%d %s the same system through scipy gmres (matvec and cycle on the device, vectors through the host): %d iterations, %.1f ms (info %d, residual %.3g ||r||): "
