@@ -168,6 +168,25 @@ class ImexStats(C.Structure):
                 ("failed_stage", C.c_int32), ("t", C.c_double), ("worst_residual", C.c_double), ("max_abs_u", C.c_double)]
 
 
+class ImexAdaptiveOptions(C.Structure):
+    """crd_imex_adaptive_options"""
+
+    _fields_ = [("imex", ImexOptions)] + [(f, C.c_double) for f in ("rtol", "atol", "h0", "h_max", "safety", "bias", "growth", "shrink")] + [("max_steps", C.c_int64)]
+
+
+class ImexAdaptiveStats(C.Structure):
+    """crd_imex_adaptive_stats"""
+
+    _fields_ = [("imex", ImexStats)] + [(f, C.c_int64) for f in ("accepted", "rejected", "attempts", "recorded")] + \
+               [(f, C.c_double) for f in ("h_first", "h_last", "h_next", "h_min", "h_max", "err_last", "t")]
+
+
+class ImexAttempt(C.Structure):
+    """crd_imex_attempt"""
+
+    _fields_ = [("t", C.c_double), ("h", C.c_double), ("err", C.c_double), ("accepted", C.c_int32), ("iterations", C.c_int32)]
+
+
 OBSERVE_MAX_PROBES = 16  # CRD_OBSERVE_MAX_PROBES
 
 
@@ -258,6 +277,9 @@ _SIGNATURES = {
     "crd_imex_defaults": (C.c_int, [C.POINTER(ImexOptions)]),
     "crd_imex_info": (C.c_int, [_vp, C.POINTER(ImexOptions), C.POINTER(C.c_int64)]),
     "crd_step_imex": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64, C.POINTER(ImexOptions), C.POINTER(ImexStats)]),
+    "crd_imex_adaptive_defaults": (C.c_int, [C.POINTER(ImexAdaptiveOptions)]),
+    "crd_integrate_imex": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(ImexAdaptiveOptions), C.POINTER(ImexAdaptiveStats), C.POINTER(ImexAttempt), C.c_int64]),
+    "crd_imex_estimate_probe": (C.c_int, [_vp, C.POINTER(C.c_double), _vp, _vp, C.POINTER(C.c_double)]),
     "crd_set_stepper": (C.c_int, [_vp, C.c_int]),
     "crd_step_rk4": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int64]),
     "crd_synchronize": (C.c_int, [_vp]),

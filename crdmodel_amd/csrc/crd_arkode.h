@@ -30,10 +30,11 @@ constexpr const char *kErrFailure = "adaptive integration: the error test failed
 
 // arkAdapt with the PID method and no explicit-stability function: eta = h_new / h.  e = (this step's biased error, the previous
 // accepted step's, the one before that).
-inline double pid_eta(double h, const double e[3], double etamax, double safety, double etamin, double h_cap)
+// `order`: the embedding's (an int divides the gains exactly as kEmbeddingOrder does: the order-3 call keeps its bits).
+inline double pid_eta(double h, const double e[3], double etamax, double safety, double etamin, double h_cap, int order)
 {
 	const double e1 = std::fmax(e[0], kTiny), e2 = std::fmax(e[1], kTiny), e3 = std::fmax(e[2], kTiny);
-	double h_acc = h * std::pow(e1, -kK1 / kEmbeddingOrder) * std::pow(e2, kK2 / kEmbeddingOrder) * std::pow(e3, -kK3 / kEmbeddingOrder);
+	double h_acc = h * std::pow(e1, -kK1 / order) * std::pow(e2, kK2 / order) * std::pow(e3, -kK3 / order);
 	h_acc *= safety;
 	h_acc = std::fmin(std::fabs(h_acc), std::fabs(etamax * h));
 	h_acc = std::fmax(std::fabs(h_acc), std::fabs(etamin * h));
@@ -42,6 +43,7 @@ inline double pid_eta(double h, const double e[3], double etamax, double safety,
 	if (std::isfinite(h_cap)) eta /= std::fmax(1.0, std::fabs(h) * eta / h_cap);  // hmax_inv
 	return eta;
 }
+inline double pid_eta(double h, const double e[3], double etamax, double safety, double etamin, double h_cap) { return pid_eta(h, e, etamax, safety, etamin, h_cap, kEmbeddingOrder); }
 
 // The controller's memory between calls, as ARKodeMem keeps it between ARKode() calls: valid while the resident state is the one the
 // integrator left (`live`), dropped by whatever replaces that state.
@@ -85,21 +87,21 @@ inline const char *begin_step(Memory &A, double t, int64_t steps_this_call, int6
 
 // A failed error test (dsm > 1 or NaN) of the step's attempt number *nef: false on the kMaxNef-th failure (ARK_ERR_FAILURE), else
 // the smaller step to try next is in A.h.
-inline bool reject(Memory &A, double dsm, int *nef, const crd_adaptive_options &o, double h_cap, crd_adaptive_stats &st)
+inline bool reject(Memory &A, double dsm, int *nef, const crd_adaptive_options &o, double h_cap, crd_adaptive_stats &st, int order = kEmbeddingOrder)
 {
 	++*nef;
 	st.rejected++;
 	if (*nef == kMaxNef) return false;
 	A.etamax = 1.0;  // no growth for the rest of this step, and none after it
 	const double e[3] = {std::isfinite(dsm) ? dsm * o.bias : 1e300, A.ehist[0], A.ehist[1]};
-	double eta = pid_eta(A.h, e, A.etamax, o.safety, o.shrink, h_cap);
+	double eta = pid_eta(A.h, e, A.etamax, o.safety, o.shrink, h_cap, order);
 	if (*nef >= kSmallNef) eta = std::fmin(eta, kEtamxf);
 	A.h *= eta;
 	return true;
 }
 
 // A passed error test: arkPrepareNextStep / arkCompleteStep.  t advances to the end of the step.
-inline void accept(Memory &A, double dsm, const crd_adaptive_options &o, double h_cap, double &t, crd_adaptive_stats &st)
+inline void accept(Memory &A, double dsm, const crd_adaptive_options &o, double h_cap, double &t, crd_adaptive_stats &st, int order = kEmbeddingOrder)
 {
 	A.ehist[2] = A.ehist[1];
 	A.ehist[1] = A.ehist[0];
@@ -108,7 +110,7 @@ inline void accept(Memory &A, double dsm, const crd_adaptive_options &o, double 
 		A.hprime = A.h;
 		A.eta = 1.0;
 	} else {
-		A.eta = pid_eta(A.h, A.ehist, A.etamax, o.safety, o.shrink, h_cap);
+		A.eta = pid_eta(A.h, A.ehist, A.etamax, o.safety, o.shrink, h_cap, order);
 		A.hprime = A.h * A.eta;
 	}
 	A.etamax = o.growth;

@@ -22,6 +22,12 @@ struct Tableau {
 	double c[kMaxStages + 1] = {};
 	double AE[kMaxStages][kMaxStages] = {};  // [i - 1][j], j = 0 .. i - 1
 	double AI[kMaxStages][kMaxStages] = {};  // [i - 1][j - 1], j = 1 .. i
+	// The embedded solution yhat = y_n + dt sum_j bhat_j (FR_j + k_j), ONE weight vector for both parts (embedded_order 0: the scheme
+	// has none), and the error estimate's rows e = y_{n+1} - yhat = dt sum_j dE_j FR_j + dt sum_j dI_j k_j, d = b - bhat per part.
+	int embedded_order = 0;
+	double bhat[kMaxStages + 1] = {};  // [j], j = 0 .. s
+	double dE[kMaxStages + 1] = {};    // [j], j = 0 .. s
+	double dI[kMaxStages] = {};        // [j - 1], j = 1 .. s
 };
 
 inline bool tableau(int scheme, Tableau *out)
@@ -51,6 +57,12 @@ inline bool tableau(int scheme, Tableau *out)
 		T.AI[1][0] = 1.0 / 6.0, T.AI[1][1] = 0.5;
 		T.AI[2][0] = -0.5, T.AI[2][1] = 0.5, T.AI[2][2] = 0.5;
 		T.AI[3][0] = 1.5, T.AI[3][1] = -1.5, T.AI[3][2] = 0.5, T.AI[3][3] = 0.5;
+		// order 2 (sum bhat = 1, bhat.c = 1/2; both matrices have row sums c), not 3 (bhat.c^2 = 1/4), damped at infinity
+		// (1 - bhat_I^T A_I^-1 e = 0); bhat_4 = 0, so FR_4 is never formed.  Every entry is exact in binary.
+		T.embedded_order = 2;
+		T.bhat[1] = 2.5, T.bhat[3] = -1.5;
+		T.dE[0] = 0.25, T.dE[1] = -0.75, T.dE[2] = 0.75, T.dE[3] = -0.25;
+		T.dI[0] = -1.0, T.dI[1] = -1.5, T.dI[2] = 2.0, T.dI[3] = 0.5;
 	} else {
 		return false;
 	}
@@ -78,6 +90,25 @@ inline int row_terms(const Tableau &T, int next, double dt, bool f32, Term *out)
 		if (e != 0.0) out[n++] = Term{j, true, e};
 		if (j == 0) continue;
 		const double i = rounded(dt * T.AI[next - 1][j - 1], f32);
+		if (i != 0.0) out[n++] = Term{j, false, i};
+	}
+	return n;
+}
+
+// The terms of the error estimate e = sum coefficient x (FR_j or k_j), in the order the kernel adds them: as row_terms -- j ascending
+// over 0 .. s, at each j the explicit term and then the implicit one, each coefficient dt d formed in double and rounded once; terms
+// whose rounded coefficient is exactly zero are left out.  Returns their number (at most kMaxEstimateTerms); 0 for a scheme without
+// an embedded solution.
+constexpr int kMaxEstimateTerms = 2 * kMaxStages + 1;
+inline int estimate_terms(const Tableau &T, double dt, bool f32, Term *out)
+{
+	int n = 0;
+	if (T.embedded_order == 0) return n;
+	for (int j = 0; j <= T.stages; j++) {
+		const double e = rounded(dt * T.dE[j], f32);
+		if (e != 0.0) out[n++] = Term{j, true, e};
+		if (j == 0) continue;
+		const double i = rounded(dt * T.dI[j - 1], f32);
 		if (i != 0.0) out[n++] = Term{j, false, i};
 	}
 	return n;

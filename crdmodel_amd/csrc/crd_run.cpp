@@ -6,6 +6,8 @@
 // ARKode's default explicit pair and controller restated (CRD_ADAPT_ARKODE), --adaptive-rk43 the RK4(3) pair of earlier rounds,
 // --imex euler|ars222|ars443 IMEX steps with the diffusion part implicit at the run's fixed dt (crd_step_imex; a lone single slab).
 // --imex-solver gmres|bicgstab|bicgstab-warm  the linear solver of its stages (CRD_IMEX_SOLVER_*; only with --imex).
+// --imex-adaptive  with --imex ars443: error-controlled steps from the ini's rtol / atol, output interval by output interval
+//                  (crd_integrate_imex); a positive dt is the first step.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -24,7 +26,7 @@
 
 namespace {
 
-void banner(const crd_run_config &cfg, const crd_grid &g, int n_slabs, int64_t nxl0, int64_t nyl0, double s0, double s1, double dt, int64_t steps_per_output, int imex)
+void banner(const crd_run_config &cfg, const crd_grid &g, int n_slabs, int64_t nxl0, int64_t nyl0, double s0, double s1, double dt, int64_t steps_per_output, int imex, bool imex_adaptive)
 {
 	// Same lines as src/FHNmodel_torus.cpp:249-275 (and the Goldbeter variant, src/GoldbeterModel_torus.cpp:266-303),
 	// with rtol / atol replaced by the fixed step.
@@ -52,6 +54,8 @@ void banner(const crd_run_config &cfg, const crd_grid &g, int n_slabs, int64_t n
 	if (fhn && torus) std::cout << "   Wave inside = " << cfg.wave_inside << "\n";
 	if (cfg.adaptive == 2) std::cout << "   integrator = adaptive RK4(3) on GPU\n   rtol = " << cfg.rtol << "\n   atol = " << cfg.atol << "\n";
 	else if (cfg.adaptive) std::cout << "   integrator = ARKode-style ERK on GPU (Zonneveld 5(3)4, PID controller)\n   rtol = " << cfg.rtol << "\n   atol = " << cfg.atol << "\n";
+	else if (imex_adaptive)
+		std::cout << "   integrator = IMEX ARS(4,4,3) on GPU (diffusion implicit), embedded order 2, PID controller\n   rtol = " << cfg.rtol << "\n   atol = " << cfg.atol << "\n";
 	else if (imex >= 0)
 		std::cout << "   integrator = IMEX " << (imex == CRD_IMEX_EULER ? "Euler" : imex == CRD_IMEX_ARS222 ? "ARS(2,2,2)" : "ARS(4,4,3)") << " on GPU (diffusion implicit), dt = " << dt << " ("
 		          << steps_per_output << " steps per output)\n";
@@ -598,6 +602,16 @@ int step_interval(const Options &o, const crd_run_config &cfg, const Cadence &c,
 		tally->adaptive_steps += as.accepted;
 		tally->adaptive_rejected += as.rejected;
 		tally->steps_taken += as.accepted + as.rejected;
+	} else if (o.imex_adaptive) {
+		const crd_imex_adaptive_options ao = imex_adaptive_options(o, cfg, tally->adaptive_h);
+		crd_imex_adaptive_stats as{};
+		rc = crd_integrate_imex(run->ctx[0], t, (iout + 1 == c.Nt) ? cfg.t_final : (iout + 1) * c.dTout, &ao, &as, nullptr, 0);
+		tally->adaptive_h = as.h_next;
+		tally->adaptive_steps += as.accepted;
+		tally->adaptive_rejected += as.rejected;
+		tally->steps_taken += as.attempts;
+		tally->imex_solves += as.imex.solves;
+		tally->imex_iterations += as.imex.iterations;
 	} else if (o.imex >= 0) {
 		crd_imex_options io;
 		crd_imex_defaults(&io);
@@ -682,7 +696,7 @@ bool output_interval(const Options &o, const crd_run_config &cfg, const crd_grid
 	int rc = step_interval(o, cfg, c, iout, run, tally);
 	rc = download_interval(o, iout, rc, run, &blown);
 	if (rc != CRD_OK || blown) {
-		if (rc != CRD_OK) die(o.imex >= 0 ? "crd_step_imex" : "crd_group_step_rk4", rc, run->ctx[0]);
+		if (rc != CRD_OK) die(o.imex_adaptive ? "crd_integrate_imex" : o.imex >= 0 ? "crd_step_imex" : "crd_group_step_rk4", rc, run->ctx[0]);
 		std::cerr << "Solver failure, stopping integration\n";  // src/FHNmodel_torus.cpp:433
 		*status = 1;
 		return false;
@@ -724,7 +738,7 @@ void rate_summary(const Options &o, const crd_run_config &cfg, const crd_grid &g
 	if (o.quiet) return;
 	const long long steps_taken = tally.steps_taken;
 	const double stepping_s = tally.stepping_s;
-	if (cfg.adaptive) std::cout << "\n   steps = " << tally.adaptive_steps << " (+" << tally.adaptive_rejected << " rejected)";
+	if (cfg.adaptive || o.imex_adaptive) std::cout << "\n   steps = " << tally.adaptive_steps << " (+" << tally.adaptive_rejected << " rejected)";
 	if (o.imex >= 0 && steps_taken > 0 && stepping_s > 0.0) {
 		char line[256];
 		std::snprintf(line, sizeof line, "\n   rate: %lld IMEX steps in %.6f s of stepping = %.1f steps/s; %lld linear solves, %lld %s iterations", steps_taken, stepping_s,
@@ -751,7 +765,7 @@ void check_imex_config(const Options &o, const crd_run_config &cfg)
 	if (o.imex < 0) return;
 	if (cfg.n_gpus > 1) usage_error("--imex steps a lone single-slab run: the ini asks for [Solver] gpus = " + std::to_string(cfg.n_gpus) + " (pass --gpus 1)");
 	if (cfg.adaptive) usage_error("--imex steps at the run's fixed dt: the ini asks for [Solver] adaptive = " + std::to_string(cfg.adaptive) + " (pass --fixed)");
-	if (!(cfg.dt > 0))
+	if (!(cfg.dt > 0) && !o.imex_adaptive)
 		usage_error("--imex needs the run's fixed step: give --dt DT or a positive [Solver] dt (dt = 0 asks for dtSafety x the stable step of RK4, which is what an IMEX run is there to exceed)");
 }
 
@@ -785,7 +799,7 @@ int run_lone(const Options &o, const crd_run_config &cfg)
 		if (run.recut) crd_block_extents(g.nx, g.ny, f / run.fd1, run.fd0, f % run.fd1, run.fd1, &b.is, &b.ie, &b.js, &b.je);
 		else b = run.crect[(size_t)f];
 	}
-	if (!o.quiet) banner(cfg, g, run.F, run.frect[0].ie - run.frect[0].is + 1, run.frect[0].je - run.frect[0].js + 1, s0, s1, c.dt, c.steps_per_output, o.imex);
+	if (!o.quiet) banner(cfg, g, run.F, run.frect[0].ie - run.frect[0].is + 1, run.frect[0].je - run.frect[0].js + 1, s0, s1, c.dt, c.steps_per_output, o.imex, o.imex_adaptive);
 	if (open_files(o, cfg, g, &run) || upload(o, cfg, g, &run)) return 1;
 	if (!cfg.adaptive && o.imex < 0 && plan_launches(o, &run)) return 1;
 	if (o.observe) {

@@ -51,6 +51,9 @@ struct Options {
 	// --imex-solver gmres|bicgstab|bicgstab-warm: the linear solver of every stage (CRD_IMEX_SOLVER_*); valid only with --imex; -1: not
 	// given, crd_imex_defaults' (GMRES).  Not in the usage text either, for the same reason.
 	int imex_solver = -1;
+	// --imex-adaptive: the IMEX run finds its own steps from the ini's rtol / atol (crd_integrate_imex); valid only with --imex ars443.
+	// Not in the usage text either.
+	bool imex_adaptive = false;
 };
 
 [[noreturn]] inline void usage(const char *argv0, bool alias)
@@ -250,6 +253,7 @@ inline void check_ensemble_options(const Options &o)
 inline void check_imex_options(const Options &o)
 {
 	if (o.imex < 0 && o.imex_solver >= 0) usage_error("--imex-solver chooses the linear solver of an IMEX run: only with --imex");
+	if (o.imex_adaptive && o.imex != CRD_IMEX_ARS443) usage_error("--imex-adaptive controls the error of ARS(4,4,3), the one scheme with an embedded solution: only with --imex ars443");
 	if (o.imex < 0) return;
 	if (!o.ensemble.empty()) usage_error("--imex steps a lone single-slab run: not with --ensemble");
 	if (o.gpus > 1) usage_error("--imex steps a lone single-slab run: not with --gpus " + std::to_string(o.gpus));
@@ -317,6 +321,8 @@ inline void parse_options(int argc, char *argv[], Options *out)
 			const std::string v = next();
 			o.imex = v == "euler" ? CRD_IMEX_EULER : v == "ars222" ? CRD_IMEX_ARS222 : v == "ars443" ? CRD_IMEX_ARS443 : -1;
 			if (o.imex < 0) usage_error("--imex takes euler, ars222 or ars443 (got '" + v + "')");
+		} else if (s == "--imex-adaptive") {
+			o.imex_adaptive = true;
 		} else if (s == "--imex-solver") {
 			const std::string v = next();
 			o.imex_solver = v == "gmres" ? CRD_IMEX_SOLVER_GMRES : v == "bicgstab" ? CRD_IMEX_SOLVER_BICGSTAB : v == "bicgstab-warm" ? CRD_IMEX_SOLVER_BICGSTAB_WARM : -1;
@@ -422,6 +428,19 @@ inline crd_adaptive_options adaptive_options(const crd_run_config &cfg, double h
 	ao.method = cfg.adaptive == 2 ? CRD_ADAPT_RK43 : CRD_ADAPT_ARKODE;
 	ao.h0 = cfg.adaptive == 2 ? h_next : 0.0;
 	ao.dense_output = 1;  // ARK_NORMAL: output times do not shorten steps, the row written is the interpolant at tout
+	return ao;
+}
+
+// --imex ars443 --imex-adaptive: one crd_integrate_imex call per output interval with the ini's rtol / atol, as --adaptive takes them;
+// the first call's h0 is the run's dt where that is positive (0: crd_stable_dt), every later one the previous call's h_next.
+inline crd_imex_adaptive_options imex_adaptive_options(const Options &o, const crd_run_config &cfg, double h_next)
+{
+	crd_imex_adaptive_options ao;
+	crd_imex_adaptive_defaults(&ao);
+	if (o.imex_solver >= 0) ao.imex.solver = o.imex_solver;
+	ao.rtol = cfg.rtol;
+	ao.atol = cfg.atol;
+	ao.h0 = h_next > 0.0 ? h_next : (cfg.dt > 0.0 ? cfg.dt : 0.0);
 	return ao;
 }
 

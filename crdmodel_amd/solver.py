@@ -397,6 +397,40 @@ class Slab:
         self._check(lib().crd_imex_info(self._h, C.byref(opt), C.byref(nbytes)), "crd_imex_info")
         return nbytes.value
 
+    def integrate_imex(self, t0, tout, rtol=1e-5, atol=1e-10, h0=0.0, h_max=0.0, safety=0.96, bias=1.5, growth=20.0, shrink=0.1, max_steps=200000, scheme="ars443",
+                       solver="gmres", history=False, lsolve_rtol=1e-8, lsolve_atol=0.0, **lsolve_options):
+        """Error-controlled IMEX integration of the resident state from t0 to tout (crd_integrate_imex): ARS(4,4,3) with its embedded
+        second-order solution, the step sizes found from rtol and atol.  h0: the first step (0: crd_stable_dt); h_max > 0 caps the step;
+        max_steps bounds the attempts, rejected ones included; solver and lsolve_options as Slab.step_imex, but for the solves' own
+        tolerances, which are lsolve_rtol and lsolve_atol here (rtol and atol are the integrator's).  Returns the
+        crd_imex_adaptive_stats structure (imex: crd_step_imex's figures; accepted, rejected, attempts, recorded, h_first, h_last,
+        h_next -- the next call's h0 --, h_min, h_max, err_last, t), and with history=True (or a capacity) the pair (stats, [attempt
+        records: t, h, err = bias x norm, accepted, iterations]).  A call that stops short of tout raises CrdError (CRD_ESTATE) with
+        that structure as its `stats` and the records as its `history`; the state is the last accepted step's."""
+        opt = capi.ImexAdaptiveOptions()
+        opt.imex = self._imex_options(scheme, dict(lsolve_options, rtol=lsolve_rtol, atol=lsolve_atol), solver)
+        opt.rtol, opt.atol, opt.h0, opt.h_max, opt.safety, opt.bias, opt.growth, opt.shrink, opt.max_steps = rtol, atol, h0, h_max, safety, bias, growth, shrink, max_steps
+        cap = 0 if not history else (4096 if history is True else int(history))
+        records = (capi.ImexAttempt * cap)() if cap else None
+        st = capi.ImexAdaptiveStats()
+        rc = lib().crd_integrate_imex(self._h, t0, tout, C.byref(opt), C.byref(st), records, cap)
+        taken = [records[i] for i in range(st.recorded)] if cap else []
+        if rc != capi.OK:
+            err = CrdError(rc, "crd_integrate_imex", lib().crd_last_error(self._h).decode())
+            err.stats, err.history = st, taken
+            raise err
+        return (st, taken) if history else st
+
+    def imex_estimate_probe(self, R, k, yn, stored, hg, dt, rtol, atol):
+        """(out, e, sum, max |var0|) of the estimating last close of crd_integrate_imex run alone (crd_imex_estimate_probe): R, k, yn and
+        the seven `stored` vectors FR_0, FR_1, k_1, FR_2, k_2, FR_3, k_3 are laid out like the state, in the slab's precision."""
+        assert len(stored) == 7
+        vecs = np.ascontiguousarray(np.stack([self._vector(x) for x in [R, k, yn] + list(stored)]))
+        out = np.empty((2,) + vecs.shape[1:], dtype=vecs.dtype)
+        scalars, result = (C.c_double * 4)(hg, dt, rtol, atol), (C.c_double * 2)()
+        self._check(lib().crd_imex_estimate_probe(self._h, scalars, vecs.ctypes.data, out.ctypes.data, result), "crd_imex_estimate_probe")
+        return out[0], out[1], result[0], result[1]
+
     def step_rk4_timed(self, t0, dt, nsteps):
         ms, kms, lps = C.c_double(), C.c_double(), C.c_int()
         self._check(lib().crd_step_rk4_timed(self._h, t0, dt, nsteps, C.byref(ms), C.byref(kms), C.byref(lps)), "crd_step_rk4_timed")

@@ -530,6 +530,72 @@ int crd_imex_defaults(crd_imex_options *opt);
 int crd_imex_info(crd_ctx *ctx, const crd_imex_options *opt, int64_t *workspace_bytes);
 int crd_step_imex(crd_ctx *ctx, double t0, double dt, int64_t nsteps, const crd_imex_options *opt, crd_imex_stats *stats);
 
+/* Error-controlled IMEX integration from t0 to tout with CRD_IMEX_ARS443 and its embedded second-order solution: the caller gives rtol
+ * and atol, the step sizes are found.  An error-controlled step costs no solve and no f_R beyond crd_step_imex's.
+ * The pair.  One weight vector for both parts, bhat = (0, 5/2, 0, -3/2, 0):
+ *   yhat = y_n + dt [ 5/2 (FR_1 + k_1) - 3/2 (FR_3 + k_3) ]
+ * of order 2 (sum bhat = 1, bhat.c = 1/2; both matrices have row sums c), not of order 3 (bhat.c^2 = 1/4), damped at infinity
+ * (1 - bhat_I^T A_I^-1 e = 0 on the implicit 4 x 4 block), and without FR_4.  The estimate is e = y_{n+1} - yhat
+ *   e = dt sum_{j=0..3} dE_j FR_j + dt sum_{j=1..4} dI_j k_j,   dE = (1/4, -3/4, 3/4, -1/4),   dI = (-1, -3/2, 2, 1/2),
+ * formed per real in the context's precision with dt dE_j and dt dI_j rounded as the step's coefficients are: the FIRST term one rounded
+ * product, every further term one fma, in the order FR_0, FR_1, k_1, FR_2, k_2, FR_3, k_3, k_4 (j ascending, explicit before implicit;
+ * a term whose coefficient is exactly zero is skipped).
+ * CRD_IMEX_EULER and CRD_IMEX_ARS222 have no estimate and are refused: the only first-order implicit weights of ARS(2,2,2) that are
+ * damped at infinity are b_I itself, and an estimate built on them is blind to the diffusion error (identically zero with justDiffusion).
+ * The norm.  w = rtol |y_n| + atol per real of the step's START y_n (ARKode's ewt), q = ((double)e / w)^2, every operation in double
+ * and rounded once; norm = sqrt(sum q / (2 nx ny)) over var0 and var1 of every point.  The sum is left by the kernel that closes the
+ * last stage (crd_imex.hip), reduced in a fixed order without atomics: the bits repeat.  The host reads two doubles per attempt, the
+ * sum and max |var0| of the new state.
+ * An attempt from t_n of size h is crd_step_imex's own code and launches up to the last solve; an ACCEPTED step (norm <= 1) leaves the
+ * bits crd_step_imex(ctx, t_n, h, 1, &opt->imex) leaves -- with CRD_IMEX_SOLVER_BICGSTAB_WARM too, every attempt starting its first
+ * solve from x = 0 as a call of one step does.  A REJECTED attempt (norm > 1, or a norm or max |var0| that is not finite) leaves y_n
+ * untouched and is repeated with a smaller step.
+ * The controller is crd_integrate_adaptive's CRD_ADAPT_ARKODE controller (PID gains 0.58 / 0.21 / 0.1, no change of h for a suggested
+ * growth within [1, 1.5], 0.3 from the second failure of a step on, CRD_ESTATE on the 7th) with the embedding order 2 in its exponents;
+ * the controller sees bias x norm.  h0 > 0 is the first step; h0 = 0 starts from crd_stable_dt; either way the first step may grow by
+ * 10000, later ones by `growth`.  h_max > 0 caps the step, h_max <= 0 means no cap: the diffusion bound means nothing here and the
+ * explicit kinetics' limit is found by the error test.  The last step is shortened to land on tout (a step that would leave less than
+ * 1e-12 |tout| is stretched to it); there is no dense output.  max_steps bounds the ATTEMPTS of a call, rejected ones included.
+ * Steps are NOT clipped at tBoundary: the held rows are those of each stage's own time, and a step across it that is inaccurate is met
+ * by rejecting it.  No controller memory is kept between calls: stats.h_next is what the caller passes as the next call's h0.
+ * A solve that does not converge ends the call with CRD_ESTATE exactly as in crd_step_imex; so do max_steps attempts short of tout, a
+ * step size below 1e-14 |t| and the 7th failure.  The resident state is then that of the last accepted step, and stats says where.
+ * Refused before any device work: what crd_step_imex refuses; CRD_EINVAL for a scheme other than CRD_IMEX_ARS443, rtol or atol negative
+ * or not finite or both zero, tout < t0 or either not finite, h0 < 0, h_max NaN, safety <= 0, bias <= 0, growth < 1, shrink outside
+ * (0, 1), max_steps < 1, history_cap < 0 or history == NULL with history_cap > 0.  opt == NULL: crd_imex_adaptive_defaults.
+ * Workspace: crd_step_imex's, as crd_imex_info reports it with opt->imex (the sum's partials lie in the vector of the solve's
+ * right-hand side, free at the last close).
+ * stats (may be NULL): imex = crd_step_imex's figures over every attempt (steps = accepted; failed_step counts attempts); accepted,
+ * rejected, attempts; h_first = the first attempt's size; h_last, h_min, h_max = the last, smallest, largest accepted step; err_last = bias x norm of
+ * the last attempt; t = the time reached (tout on success); h_next; recorded = records written to history.
+ * history (may be NULL with history_cap 0): one record per attempt in order -- t_n, h, err = bias x norm, accepted 0 / 1, iterations
+ * of the attempt's solves.  When history_cap runs out the call goes on; stats.attempts says how many there were. */
+typedef struct crd_imex_adaptive_options {
+	crd_imex_options imex;  /* crd_imex_defaults with scheme CRD_IMEX_ARS443 */
+	double rtol, atol;      /* 1e-5, 1e-10 */
+	double h0;              /* first step; 0 = crd_stable_dt */
+	double h_max;           /* > 0: cap; <= 0 (default 0): none */
+	double safety, bias, growth, shrink; /* 0.96, 1.5, 20, 0.1: crd_adaptive_options' */
+	int64_t max_steps;      /* 200000 attempts */
+} crd_imex_adaptive_options;
+typedef struct crd_imex_adaptive_stats {
+	crd_imex_stats imex;
+	int64_t accepted, rejected, attempts, recorded;
+	double h_first, h_last, h_next, h_min, h_max, err_last, t;
+} crd_imex_adaptive_stats;
+typedef struct crd_imex_attempt {
+	double t, h, err;
+	int32_t accepted, iterations;
+} crd_imex_attempt;
+int crd_imex_adaptive_defaults(crd_imex_adaptive_options *opt);
+int crd_integrate_imex(crd_ctx *ctx, double t0, double tout, const crd_imex_adaptive_options *opt, crd_imex_adaptive_stats *stats, crd_imex_attempt *history,
+                       int64_t history_cap);
+/* For the test suite's gate on the estimating close alone: runs it once on HOST vectors in the context's precision given back to back in
+ * `in` -- R_s, k_s, y_n, then the stored vectors in the estimate's order FR_0, FR_1, k_1, FR_2, k_2, FR_3, k_3 -- with
+ * scalars = {hg, dt, rtol, atol}, hg rounded to the context's precision and the coefficients formed from dt as an attempt forms them.
+ * out: the new state and e back to back; result: {sum of q, max |var0| of the new state}.  Uses crd_step_imex's workspace. */
+int crd_imex_estimate_probe(crd_ctx *ctx, const double *scalars, const void *in, void *out, double *result);
+
 /* The exchange period E of the one-launch stepper on several slabs: E steps between two halo exchanges, each of 4 E ghost rows
  * of both fields; in between every slab recomputes the shrinking ghost region redundantly (same kernel, same inputs: bit-identical
  * to what the owner computes).  3 <= E <= 16; default 10 where every slab of the run has 256 rows or more, else 8.  A property of the RUN: every context of a LOCAL group / every rank of a

@@ -19,12 +19,13 @@ def main():
         sys.exit("build the library first: %s is not there" % ASM)
     kernels = [k for k in kr.parse(open(ASM).read()) if k["name"].startswith("crd_imex_")]
     print("# tools/imex_resources.py: gfx950, read from the build's device assembly.  Template arguments of the stage close: <Real, model (0 FHN, 1 Goldbeter,")
-    print("# 2 Goldbeter with diffusion only), last stage>.  Blocks of 256 threads; crd_imex_max_kernel: one wavefront.")
+    print("# 2 Goldbeter with diffusion only), last stage>.  Blocks of 256 threads; crd_imex_max_kernel, crd_imex_max_sum_kernel: one wavefront.")
     print("%-48s %5s %5s %6s %7s %5s" % ("# kernel", "VGPR", "SGPR", "LDS B", "scratch", "w/SIMD"))
     for ln in sorted("%-48s %5d %5d %6d %7d %5d" % (k["name"], k["vgprs"], k["sgprs"], k["lds"], k["scratch"], k["occupancy"]) for k in kernels):
         print(ln)
-    if len(kernels) != 13:
-        sys.exit("expected the stage close for three models, two precisions, last stage or not, and the partials' maximum, found %d" % len(kernels))
+    if len(kernels) != 16:
+        sys.exit("expected the stage close for three models, two precisions, last stage or not, the partials' maximum, the estimating close for two "
+                 "precisions and its partials' maximum and sum, found %d" % len(kernels))
     bad = [k["name"] for k in kernels if k["scratch"]]
     if bad:
         sys.exit("scratch in: " + ", ".join(bad))
